@@ -333,20 +333,21 @@ def case_mid():
     print("c2_mid ok", E, N, "max |tm1|", np.abs(tm1).max())
 
 
-def case_np8():
-    run, out = run_reference("c1_np8", "1.0", 400, nranks=8)
-    meshes = [read_mesh(run, r) for r in range(8)]
+def case_np(nranks):
+    name = "c1_np%d" % nranks
+    run, out = run_reference(name, "1.0", 400, nranks=nranks)
+    meshes = [read_mesh(run, r) for r in range(nranks)]
     harbored = []
     per_rank = {}
     sched = open(os.path.join(run, "stat-sched.txt")).read() if os.path.exists(os.path.join(run, "stat-sched.txt")) else ""
     meshstat = open(os.path.join(run, "stat-mesh.txt")).read() if os.path.exists(os.path.join(run, "stat-mesh.txt")) else ""
-    forces = [read_forces(run, r) for r in range(8)]
+    forces = [read_forces(run, r) for r in range(nranks)]
     arrays = {}
     ckfiles = {}
     for f in ("checkpoint.out0", "checkpoint.out1"):
         step, blocks = read_checkpoint(os.path.join(run, "out", "checkpoints", f))
         ckfiles[step] = blocks
-    for r in range(8):
+    for r in range(nranks):
         arrays["elem_ticks_%d" % r] = meshes[r][0]
         arrays["loaded_lnid_%d" % r] = forces[r][0]
         arrays["forces_%d" % r] = forces[r][1]
@@ -354,11 +355,23 @@ def case_np8():
             arrays["ckpt%d_tm2_%d" % (s, r)] = ckfiles[s][r][0]
             arrays["ckpt%d_tm1_%d" % (s, r)] = ckfiles[s][r][1]
     st = read_stations(run)
-    np.savez_compressed(os.path.join(HERE, "c1_np8.npz"), ckpt_steps=np.array(sorted(ckfiles)),
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), ckpt_steps=np.array(sorted(ckfiles)),
                         stations=st, stat_sched=np.array(sched), stat_mesh=np.array(meshstat),
                         dt=1e-3, end_time=1.0, freq=5.0, **arrays)
     shutil.rmtree(run)
-    print("c1_np8 ok")
+    print(name, "ok")
+
+
+def case_cvm():
+    """The material databases of the octree cases that the tests mesh without the reference's tools, as oracle/make_cvm
+    writes them on the reference's own etree + cvm libraries: tests/golden/cvm/<name>.e."""
+    sys.path.insert(0, ROOT)
+    from tests.test_host_partition import _cvm_args
+    os.makedirs(os.path.join(HERE, "cvm"), exist_ok=True)
+    for name in ("c5_basin", "c5_gradient", "c5_three_level"):
+        subprocess.check_call([os.path.join(ROOT, "oracle", "_ref", "make_cvm"), os.path.join(HERE, "cvm", name + ".e")] +
+                              _cvm_args(name))
+    print("cvm ok")
 
 
 def case_two_level():
@@ -503,7 +516,10 @@ CASES = {
     "c1_planes": case_planes,
     "c1_wavefield": case_wavefield,
     "c1_stations_va": case_stations_va,
-    "c1_np8": case_np8,
+    "c1_np8": lambda: case_np(8),
+    # the same run on 4 ranks: few enough processes to share one GPU (tests/test_gpu_reference_link.py)
+    "c1_np4": lambda: case_np(4),
+    "cvm": case_cvm,
     "c2_mid": case_mid,
     "c5_two_level": case_two_level,
     "c5_three_level": case_three_level,

@@ -43,12 +43,13 @@ def test_one_rank_line_carries_its_parity():
     assert c["parity_windows"] >= 4 and c["parity_nodes"] > 4 * 11 ** 3 and c["parity_worst"] <= c["parity_tol"] == 1e-9
 
 
-@pytest.mark.parametrize("world,transport", [(2, "auto"), (8, "ipc"), (2, "host")])
+@pytest.mark.parametrize("world,transport", [(2, "auto"), (4, "ipc"), (2, "host")])
 def test_ranks_sharing_the_gpu_carry_their_parity(world, transport):
     """HQ_BENCH_SHARE_GPU=1: the ranks of `bench.py --gpus N` on one device (RCCL refuses that, so `auto` times the IPC
     transport alone and keeps it).  Every rank's windows sit on ITS partition interfaces: pack, transport, interface
-    update and unpack of the run that was timed are inside the checked cones."""
-    d = _bench("--gpus", str(world), "--workload", "c2" if world == 8 else "m1", "--steps", "10", "--warmup", "3",
+    update and unpack of the run that was timed are inside the checked cones.  At most four ranks: with bench.py's
+    launcher and this process, at most six processes hold the GPU."""
+    d = _bench("--gpus", str(world), "--workload", "c2" if world == 4 else "m1", "--steps", "10", "--warmup", "3",
                env_extra={"HQ_BENCH_SHARE_GPU": "1", "HQ_BENCH_TRANSPORT": transport})
     c = d["config"]
     assert d["n_gpus"] == world and c["finite"]

@@ -10,6 +10,7 @@ import os
 import socket
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -31,17 +32,46 @@ def _free_port():
 
 
 def _launch(tmp_path, world, kind, nsteps, env_extra=None, expect_failure=False):
-    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    env.update(env_extra or {})
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "tests", "_hq_rank_worker.py"), str(tmp_path), kind, str(nsteps)]
-    out = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                         universal_newlines=True, timeout=900)
+    """`world` processes of tests/_hq_rank_worker.py with the variables torch.distributed's launcher sets.  They are
+    started here, not by that launcher: its own process opens the GPU too, and with this one and five ranks that would
+    be seven processes on a GPU that allows six.  A rank that fails gives the others 60 s to leave, then they are
+    stopped.  -> every rank's rank<r>.npz (expect_failure: the ranks' output)"""
+    port = _free_port()
+    worker = os.path.join(ROOT, "tests", "_hq_rank_worker.py")
+    procs, logs = [], []
+    for r in range(world):
+        env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0", RANK=str(r), LOCAL_RANK=str(r),
+                   WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+        env.update(env_extra or {})
+        logs.append(open(os.path.join(str(tmp_path), "worker%d.log" % r), "w+"))
+        procs.append(subprocess.Popen([sys.executable, worker, str(tmp_path), kind, str(nsteps)], cwd=ROOT, env=env,
+                                      stdout=logs[-1], stderr=subprocess.STDOUT))
+    t0, failed_at = time.time(), None
+    while any(p.poll() is None for p in procs):
+        now = time.time()
+        if failed_at is None and any(p.poll() not in (None, 0) for p in procs):
+            failed_at = now
+        if now - t0 > 900 or (failed_at is not None and now - failed_at > 60):
+            for p in procs:
+                if p.poll() is None:
+                    p.terminate()                          # the exact children started above, nothing else
+            for p in procs:
+                try:
+                    p.wait(timeout=20)
+                except subprocess.TimeoutExpired:
+                    p.kill()
+            break
+        time.sleep(0.2)
+    rcs = [p.wait() for p in procs]
+    out = ""
+    for r, f in enumerate(logs):
+        f.seek(0)
+        out += "--- rank %d (rc %d)\n%s" % (r, rcs[r], f.read())
+        f.close()
     if expect_failure:
-        assert out.returncode != 0, "the run was expected to fail"
-        return out.stdout
-    assert out.returncode == 0, out.stdout[-3000:]
+        assert any(rcs), "the run was expected to fail"
+        return out
+    assert not any(rcs), out[-3000:]
     return [np.load(os.path.join(str(tmp_path), "rank%d.npz" % r)) for r in range(world)]
 
 

@@ -572,20 +572,14 @@ def test_from_the_references_mesh_database_to_its_checkpoints(tmp_path):
 @pytest.mark.parametrize("name", ["c5_basin", "c5_gradient"])
 def test_from_the_cvm_database_to_the_references_checkpoints(name, tmp_path):
     """End to end from "the same input etree" WITHOUT the reference's mesher (SURVEY s8 f4's parenthetical, round 6): the
-    CVM database of the golden run -- written here by oracle/make_cvm on the reference's own etree + cvm libraries, as
-    tests/golden/make_golden.py did -- read by hqh_cvm_open, meshed by hqh_octree_generate (Vs rule on setrec's 27-sample
+    CVM database of the golden run -- as oracle/make_cvm wrote it on the reference's own etree + cvm libraries
+    (tests/golden/cvm) -- read by hqh_cvm_open, meshed by hqh_octree_generate (Vs rule on setrec's 27-sample
     record, 2:1 balance), tables by hqh_mesh_from_leaves, the reference's force file streamed by hqh_solver_run: the field
     lands on the checkpoints the REAL psolve wrote from that database (laterally refined basin; the same with a
     material of its own in every database octant)."""
-    import os
-    import subprocess
     from hercules_amd import host
-    from tests.test_host_partition import MAKE_CVM, _cvm_args
-    if not os.path.exists(MAKE_CVM):
-        pytest.skip("oracle/_ref/make_cvm is not built")
-    db = str(tmp_path / "model.e")
-    subprocess.run([MAKE_CVM, db] + _cvm_args(name), check=True)
-    cvm = host.Cvm(db)
+    from tests.test_host_partition import _cvm_database
+    cvm = host.Cvm(_cvm_database(name, tmp_path))
     vp, vs, rho, cell = cvm.grid()
     region = cvm.region
     cvm.close()

@@ -151,23 +151,23 @@ def test_the_reference_program_on_the_library_matches_the_shipped_station_traces
 
 @needs_binaries
 @pytest.mark.parametrize("transport", ["mpi", "ipc"])
-def test_the_reference_program_on_eight_ranks_shares_one_gpu(transport):
-    """mpiexec -np 8 psolve_hq on examples/simple, all eight ranks on this box's one GPU: the reference's own octor
+def test_the_reference_program_on_four_ranks_shares_one_gpu(transport):
+    """mpiexec -np 4 psolve_hq on examples/simple, all four ranks on this box's one GPU: the reference's own octor
     partition, schedule_build messengers (psolve.c:4704-4863) and mpiexec world (psolve.c:7344-7389) feed hq_desc on
     every rank; the halo records travel on the reference's own MPI_Irecv / MPI_Isend / MPI_Waitall (HQ_TRANSPORT=mpi:
-    hq_comm_init_host with the stub's callback, psolve.c:5013-5033) or device to device between the eight processes
+    hq_comm_init_host with the stub's callback, psolve.c:5013-5033) or device to device between the four processes
     (HQ_TRANSPORT=ipc).  Against the per-rank checkpoint stripes and the station traces of the unmodified reference's
-    8-rank run (tests/golden/c1_np8.npz)."""
-    g = H.load("c1_np8")
-    # (stations every 10 steps: between outputs the eight processes enqueue whole batches instead of synchronising on
-    #  the one GPU they time-slice at every step -- 27 s -> a few; the every-step cadence is the one-rank test's)
-    run_hq, log = _run(PSOLVE_HQ, _params(float(g["end_time"]), 400, 10), nranks=8, env_extra={"HQ_TRANSPORT": transport})
+    4-rank run (tests/golden/c1_np4.npz).  Four, not eight: with this process, at most six processes hold the GPU."""
+    g = H.load("c1_np4")
+    # (stations every 10 steps: between outputs the four processes enqueue whole batches instead of synchronising on
+    #  the one GPU they time-slice at every step; the every-step cadence is the one-rank test's)
+    run_hq, log = _run(PSOLVE_HQ, _params(float(g["end_time"]), 400, 10), nranks=4, env_extra={"HQ_TRANSPORT": transport})
     try:
         ck = _rank_stripes(run_hq)
         assert sorted(ck) == [int(s) for s in g["ckpt_steps"]]
         for step in g["ckpt_steps"]:
-            assert len(ck[int(step)]) == 8
-            for r in range(8):
+            assert len(ck[int(step)]) == 4
+            for r in range(4):
                 ref2, ref1 = g["ckpt%d_tm2_%d" % (int(step), r)], g["ckpt%d_tm1_%d" % (int(step), r)]
                 tm2, tm1 = ck[int(step)][r]
                 n = len(ref1)

@@ -449,7 +449,19 @@ def _cvm_args(name):
     return [str(v) for v in a]
 
 
-@pytest.mark.skipif(not os.path.exists(MAKE_CVM), reason="oracle/_ref/make_cvm (oracle/build_ref.sh, the reference's etree + cvm libraries) is not built")
+def _cvm_database(name, tmp_path):
+    """The material database the golden run of `name` meshed: tests/golden/cvm/<name>.e, as oracle/make_cvm wrote it on the
+    reference's own etree + cvm libraries (tests/golden/make_golden.py cvm).  Where make_cvm is built, it writes the
+    database afresh and the stored one must equal it byte for byte."""
+    import subprocess
+    db = os.path.join(H.GOLDEN, "cvm", name + ".e")
+    if os.path.exists(MAKE_CVM):
+        fresh = str(tmp_path / "model.e")
+        subprocess.run([MAKE_CVM, fresh] + _cvm_args(name), check=True)
+        assert open(fresh, "rb").read() == open(db, "rb").read()
+    return db
+
+
 @pytest.mark.parametrize("name", ["c5_basin", "c5_gradient", "c5_three_level"])
 def test_from_the_cvm_database_to_the_references_mesh(name, tmp_path):
     """SURVEY s8 f4's parenthetical, round 6: "the same input etree" without the reference's mesher.  oracle/make_cvm --
@@ -458,10 +470,7 @@ def test_from_the_cvm_database_to_the_references_mesh(name, tmp_path):
     hqh_cvm_query answers as cvm_query would (cvm.c:266-311: the leaf octant that holds the point), hqh_cvm_grid hands
     the model to hqh_octree_generate in the mesh's axes (setrec queries east = y, north = x, psolve.c:1352) -- and out comes
     the reference's mesh, leaf for leaf and record for record."""
-    import subprocess
-    db = str(tmp_path / "model.e")
-    subprocess.run([MAKE_CVM, db] + _cvm_args(name), check=True)
-    cvm = host.Cvm(db)
+    cvm = host.Cvm(_cvm_database(name, tmp_path))
     assert cvm.nleaves == 16 * 16 * 8 and cvm.levels == (4, 4) and cvm.region == (1000.0, 1000.0, 500.0)
     assert cvm.ticksize == 1000.0 / 2 ** 31
     vp, vs, rho, cell = cvm.grid()
