@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- element-updates/s of the explicit time-stepping hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1] [--dump-outputs DIR] [--full]
 
 One "step" = one iteration of the solver_run loop body (psolve.c:4265-4319) over
 the whole mesh: source force, stiffness + Rayleigh damping element force, nodal
@@ -14,7 +14,10 @@ started from a seeded random displacement field so every element is active.
 N > 1 partitions the SAME mesh along the octor block decomposition (strong
 scaling) and exchanges interface-node forces / displacements with RCCL.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
+A plain run does what the headline figure needs: it sets up, warms up, times the K steps, writes
+--dump-outputs and prints ONE JSON line on rank 0.  --full adds what takes runs or time of its own:
+the two rocprofv3 counter passes (roofline.traffic*), the CPU baseline (cpu_baseline) and the oracle
+parity windows behind the timed region (config.parity_*; exit 1 above the bar).
 """
 import argparse
 import csv
@@ -919,15 +922,20 @@ def main():
                     help="seconds of read-only device work (hq_check_finite) before the warm-up steps; 0 = none")
     ap.add_argument("--workload", default=os.environ.get("HQ_BENCH_WORKLOAD", "c3"), choices=sorted(WORKLOADS))
     ap.add_argument("--variant", default="auto", choices=["auto", "scatter", "patch"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also run the rocprofv3 --pmc traffic passes (roofline.traffic*, N = 1), "
+                         "the CPU baseline (cpu_baseline, N = 1) and the oracle parity windows behind the timed region "
+                         "(config.parity_*, exit 1 above the bar); --no-pmc, --no-cpu-baseline and --no-parity leave "
+                         "one of them out.  A plain run leaves them all out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the two rocprofv3 --pmc passes that measure roofline.traffic (N = 1 only)")
+                    help="with --full: skip the two rocprofv3 --pmc passes that measure roofline.traffic (N = 1 only)")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"],
                     help="f32: libhq_solver_f32.so (hq_real = float, the reference's -DSINGLE_PRECISION_SOLVER) -- a separately "
                          "named dtype with its own oracle build and tolerance; never the headline")
-    ap.add_argument("--pmc-dir", default=None, help="keep the rocprofv3 counter CSVs of the traffic passes here")
+    ap.add_argument("--pmc-dir", default=None, help="with --full: keep the rocprofv3 counter CSVs of the traffic passes here")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the oracle cone windows behind the timed region (config.parity_*)")
+                    help="with --full: skip the oracle cone windows behind the timed region (config.parity_*)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N: start the N ranks, let them rendezvous over gloo on the CPU and exit "
@@ -965,13 +973,13 @@ def main():
     # this); the image exports it already -- a launcher that scrubs the environment must not cost the IPC transport
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
-    # Before this process touches the GPU: the traffic passes (child processes under rocprofv3) and
+    # --full, before this process touches the GPU: the traffic passes (child processes under rocprofv3) and
     # the CPU baseline (threads / MPI ranks on the host cores).  N = 1 only.
     pmc = None
-    if rank == 0 and world == 1 and not args.no_pmc:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc:
         pmc = measure_traffic(args, args.pmc_dir)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(single=args.precision == "f32")
 
     import torch
@@ -1170,9 +1178,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         nonfinite = int(t[0])
 
-    # parity that travels with the line: oracle cone windows on THIS context (partition + transport), behind the timed region
+    # --full: parity that travels with the line: oracle cone windows on THIS context (partition + transport), behind the
+    # timed region
     parity = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         try:
             parity = parity_windows(args, box, solver, rank, world)
         except Exception as exc:                            # reported, never silently dropped
@@ -1210,6 +1219,8 @@ def main():
             source = "unmeasured: " + pmc["error"]
         elif world > 1:
             source = "unmeasured: counter passes run at N = 1 only"
+        elif not args.full:
+            source = "unmeasured: plain run (bench.py --full runs the counter passes)"
         else:
             source = "unmeasured: --no-pmc"
         # frac: the bytes the step HAS to move (72 B per node: read u(t), u(t-dt), write u(t+dt)) over the time
