@@ -27,16 +27,20 @@ def _newer(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
-def build_solver(force=False):
+def _build_solver(lib, defines, force):
     srcs = [os.path.join(CSRC, f) for f in ("hq_engine.hip", "hq_kernels.h", "hq_opts.h", "hq_patch.h", "hq_brick.h")]
     srcs.append(os.path.join(ROOT, "include", "hq_solver.h"))
-    if force or _newer(SOLVER_LIB, srcs):
-        cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",
-               "-fvisibility=hidden", "-fopenmp", "-Wno-unused-value"] + \
+    if force or _newer(lib, srcs):
+        cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared"] + defines + \
+              ["-fvisibility=hidden", "-fopenmp", "-Wno-unused-value"] + \
               os.environ.get("HQ_EXTRA_FLAGS", "").split() + \
-              ["-o", SOLVER_LIB, srcs[0], "-Wl,-rpath,/opt/rocm/lib", "-Wl,-Bsymbolic", "-ldl"]
+              ["-o", lib, srcs[0], "-Wl,-rpath,/opt/rocm/lib", "-Wl,-Bsymbolic", "-ldl"]
         subprocess.check_call(cmd, cwd=CSRC)
-    return SOLVER_LIB
+    return lib
+
+
+def build_solver(force=False):
+    return _build_solver(SOLVER_LIB, [], force)
 
 
 SOLVER_LIB_F32 = os.path.join(CSRC, "libhq_solver_f32.so")
@@ -45,15 +49,7 @@ SOLVER_LIB_F32 = os.path.join(CSRC, "libhq_solver_f32.so")
 def build_solver_f32(force=False):
     """The same sources with -DHQ_SINGLE_PRECISION_SOLVER: hq_real = float (the reference's -DSINGLE_PRECISION_SOLVER,
     psolve.h:60-64) -- a separately named library, never the default."""
-    srcs = [os.path.join(CSRC, f) for f in ("hq_engine.hip", "hq_kernels.h", "hq_opts.h", "hq_patch.h", "hq_brick.h")]
-    srcs.append(os.path.join(ROOT, "include", "hq_solver.h"))
-    if force or _newer(SOLVER_LIB_F32, srcs):
-        cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-DHQ_SINGLE_PRECISION_SOLVER",
-               "-fvisibility=hidden", "-fopenmp", "-Wno-unused-value"] + \
-              os.environ.get("HQ_EXTRA_FLAGS", "").split() + \
-              ["-o", SOLVER_LIB_F32, srcs[0], "-Wl,-rpath,/opt/rocm/lib", "-Wl,-Bsymbolic", "-ldl"]
-        subprocess.check_call(cmd, cwd=CSRC)
-    return SOLVER_LIB_F32
+    return _build_solver(SOLVER_LIB_F32, ["-DHQ_SINGLE_PRECISION_SOLVER"], force)
 
 
 def build_host(force=False):

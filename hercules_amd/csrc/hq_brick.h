@@ -104,16 +104,15 @@ struct hq_brick_cfg {
     int ragged_het = 1;          /* HQ_BRICK_RAGGED_HET: (round 6) partly filled tiles of the per-element kernel too               */
 };
 
-static hq_brick_cfg hq_brick_cfg_from_env(void)
+static hq_brick_cfg hq_brick_cfg_of(const hq_options& o)
 {
     hq_brick_cfg c;
-    auto geti = [](const char* n, int def) { return hq_opt_int(n, def); };
-    c.cz = std::max(2, geti("HQ_BRICK_CZ", c.cz));
-    c.minz = std::max(1, geti("HQ_BRICK_MINZ", c.minz));
-    c.minnodes = std::max(1, geti("HQ_BRICK_MINNODES", c.minnodes));
-    c.ragged = geti("HQ_BRICK_RAGGED", c.ragged) != 0;
-    c.minfill = std::min(HQ_BK_THREADS, std::max(1, geti("HQ_BRICK_RAGGED_MINFILL", c.minfill)));
-    c.ragged_het = geti("HQ_BRICK_RAGGED_HET", c.ragged_het) != 0;
+    c.cz = std::max(2, hq_value_or(o.brick_cz, c.cz));
+    c.minz = std::max(1, hq_value_or(o.brick_minz, c.minz));
+    c.minnodes = std::max(1, hq_value_or(o.brick_minnodes, c.minnodes));
+    c.ragged = hq_value_or(o.brick_ragged, c.ragged) != 0;
+    c.minfill = std::min(HQ_BK_THREADS, std::max(1, hq_value_or(o.brick_ragged_minfill, c.minfill)));
+    c.ragged_het = hq_value_or(o.brick_ragged_het, c.ragged_het) != 0;
     return c;
 }
 
@@ -163,14 +162,14 @@ struct hq_mat_src {
     double dt = 0, bbase = 0, thr_damp = 0, thr_vpvs = 0;
 };
 
-static int hq_brick_plan_host(int64_t E, int64_t N, const int32_t* lnid, const int32_t* xyz, const double* c1,
+static int hq_brick_plan_host(const hq_options& o, int64_t E, int64_t N, const int32_t* lnid, const int32_t* xyz, const double* c1,
                               const double* c2, const double* beta, const double* ntab, const char* excl,
                               hq_brick_host* B, const hq_mat_src* MS = nullptr)
 {
     *B = hq_brick_host();
     if (!xyz || E <= 0 || N <= 0) return 0;
-    const hq_brick_cfg cfg = hq_brick_cfg_from_env();
-    const bool verbose = (hq_opt_int("HQ_PATCH_VERBOSE", 0) > 1);
+    const hq_brick_cfg cfg = hq_brick_cfg_of(o);
+    const bool verbose = o.verbose > 1;
     auto t_lap = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!verbose) return;
@@ -179,7 +178,7 @@ static int hq_brick_plan_host(int64_t E, int64_t N, const int32_t* lnid, const i
         t_lap = now;
     };
     const int TX = HQ_BK_TX, TY = HQ_BK_TY;
-    const bool want_het = !(hq_opt_on("HQ_BRICK_NO_HET"));
+    const bool want_het = !hq_set(o.brick_no_het);
     /* the uniform units use the assembled stencil's coefficients: without a verified table (hq_stencil().ok, the gate
      * hq_k_patch_stencil has too) their nodes go to the element-by-element HET units or stay with the patches */
     const bool stencil_ok = hq_stencil().ok;
@@ -208,7 +207,7 @@ static int hq_brick_plan_host(int64_t E, int64_t N, const int32_t* lnid, const i
     lap("edge lengths");
 
     /* elements around every node (any level): a node with four of them can be the interior of a domain face */
-    const bool want_faces = stencil_ok && hq_stencil().face_ok && !hq_opt_flag("HQ_BRICK_NO_FACES") && !hq_opt_flag("HQ_BRICK_NO_NTSAME");
+    const bool want_faces = stencil_ok && hq_stencil().face_ok && !hq_set(o.brick_no_faces) && !hq_set(o.brick_no_ntsame);
     std::vector<uint8_t> touch;
     if (want_faces) {
         touch.assign((size_t)N, 0);
@@ -358,8 +357,8 @@ static int hq_brick_plan_host(int64_t E, int64_t N, const int32_t* lnid, const i
          * level interface or a material boundary that runs along y or z a strip of up to 63 nodes per row is left over,
          * and half a workgroup's lanes in the marching kernel still beat the patches by a wide margin -- then the het tiles */
         /* ... or (the default since the ragged units exist) 64-wide tiles again that need not be full: HQ_BK_RAGGED */
-        const int rag = cfg.ragged && stencil_ok && !hq_opt_flag("HQ_BRICK_NO_NTSAME") ? 1 : 0;
-        const int half = rag || hq_opt_int("HQ_BRICK_HALF_TILES", 1) != 0 ? 1 : 0;
+        const int rag = cfg.ragged && stencil_ok && !hq_set(o.brick_no_ntsame) ? 1 : 0;
+        const int half = rag || hq_value_or(o.brick_half_tiles, 1) != 0 ? 1 : 0;
         /* ... and (round 6) behind the full het tiles a round of RAGGED het tiles: 62 x 7 footprints of which every plane of a
          * run holds >= minfill simple nodes of ANY material (hq_k_brick_het<., RAGGED>) -- on a mesh whose material differs
          * from element to element the one-material ragged columns above find nothing */
@@ -613,7 +612,7 @@ static int hq_brick_plan_host(int64_t E, int64_t N, const int32_t* lnid, const i
      * chunks -- each costs two more planes of loads, but 64 workgroups do not fill 256 CUs (1 M-element box: 0.068 ms
      * per step with 32 planes per unit, 0.039 with 8; 8 M box: 0.164 / 0.172).  HQ_BRICK_CZ fixes it. */
     int cz = cfg.cz;
-    if (!hq_opt_has("HQ_BRICK_CZ")) {
+    if (!hq_given(o.brick_cz)) {
         for (cz = 32; cz > 8; cz /= 2) {
             int64_t n = 0;
             for (auto& c : cols) n += (c.nz + cz - 1) / cz;
@@ -646,8 +645,7 @@ static int hq_brick_plan_host(int64_t E, int64_t N, const int32_t* lnid, const i
     for (size_t u = 0; u < us.size(); u++)
         coff[u + 1] = coff[u] + (cols[(size_t)us[u].col].het ? (int64_t)(us[u].np + 1) * HQ_BH_THREADS * 3 : 0);
     B->coef.assign((size_t)coff[us.size()] + 8, 0.0);
-    const bool try_pack = MS && MS->edata && MS->dt > 0 && !hq_opt_flag("HQ_BRICK_NO_PACK");
-    const bool no_ntsame = hq_opt_flag("HQ_BRICK_NO_NTSAME");     /* read here: the workers of the loop below see no options (hq_opts.h) */
+    const bool try_pack = MS && MS->edata && MS->dt > 0 && !hq_set(o.brick_no_pack);
     if (try_pack) { B->coef32.assign((size_t)coff[us.size()] + 8, 0.0f); B->nt2.assign(2 * (size_t)N, 0.0); }        /* [N]: a unit also LOADS the rows of its two cap planes, which may be anybody's nodes */
     int fault = 0;                                       /* written by many threads: atomic writes only */
     auto set_fault = [&]() {
@@ -768,7 +766,7 @@ static int hq_brick_plan_host(int64_t E, int64_t N, const int32_t* lnid, const i
                     const double* q = ntab + 7 * (int64_t)n;
                     if (q[0] != q0[0] || q[1] != q0[1] || q[4] != q0[4]) { sm = false; break; }
                 }
-        if (sm && !c.het && !no_ntsame) { U.flags |= HQ_BK_NTSAME; same[(size_t)u] = 1; }
+        if (sm && !c.het && !hq_set(o.brick_no_ntsame)) { U.flags |= HQ_BK_NTSAME; same[(size_t)u] = 1; }
         U.m0 = q0[0]; U.m2 = q0[1]; U.m1 = q0[4];
         U.coef = 0;
         }       /* (!c.rag) */
@@ -1485,7 +1483,7 @@ static void hq_brick_launch(const hq_brick_plan* P, const hq_real* u1, const hq_
         const int32_t* sp = P->d_src_ptr ? P->d_src_ptr + first : nullptr;
 #define HQ_BK_ARGS count, per_xcd, P->d_units + first, P->d_tab, u1, u2, un, nt3, sp, P->d_src_ent, (sp ? F : nullptr), dt2, hq_stencil().c
 #ifdef HQ_EXPERIMENT            /* profiles/tools only: unused dynamic LDS so that ONE brick workgroup fits a CU -- does half the residency still stream? */
-        static const unsigned xpad = getenv("HQ_X_BRICK_LDS_PAD") ? (unsigned)atoi(getenv("HQ_X_BRICK_LDS_PAD")) : 0u;
+        const unsigned xpad = getenv("HQ_X_BRICK_LDS_PAD") ? (unsigned)atoi(getenv("HQ_X_BRICK_LDS_PAD")) : 0u;
         if (xpad && k == 0) {
             static bool once = false;
             if (!once) {

@@ -160,7 +160,8 @@ struct hq_dev_schedule {
 };
 
 struct hq_ctx {
-    hq_options opts;                  /* the caller's options, completed with defaults (hq_create_opts) */
+    hq_options opts;                  /* the caller's options as hq_create_opts resolved them: per context, so that a host --
+                                       * or a test process -- can differ between contexts; -1 = the library's default */
     int device = 0;
     hipStream_t stream = nullptr;
     int32_t E = 0, N = 0, ldnnum = 0;
@@ -204,13 +205,6 @@ struct hq_ctx {
     std::vector<hq_ctx*>* group = nullptr;   /* in-process transport (hq_group_link) */
     bool group_owner = false;
     bool share_packed = false;               /* this step's hq_k_interface_update wrote the sharing records as well */
-    /* switches read at hq_create (per context, so that a host -- or a test process -- can differ between contexts) */
-    int opt_brick_stream = -1;               /* HQ_BRICK_STREAM: 1 / 0; -1: on a context that steps alone (no transport), where
-                                              * the shell's patch launch then runs BESIDE the first round of brick workgroups
-                                              * instead of ahead of it */
-    bool opt_fused_share = true;             /* HQ_NO_FUSED_SHARE=1 clears it */
-    int opt_merge_rounds = 2;                /* HQ_PATCH_MERGE_ROUNDS */
-    int opt_brick_light = -1;                /* HQ_BRICK_BY_COMPONENT: 0 / 1; default (-1): where the chain has its own stream */
     struct hq_ipc_state* ipc = nullptr;      /* device-to-device transport between processes (hq_comm_init_ipc) */
     hipEvent_t ev_sent = nullptr;
     /* patch variant with an interface: the exchange chain runs on its own stream
@@ -257,7 +251,6 @@ struct hq_ctx {
      * (hq_info.t_*_us: the library's print_timing_stat, psolve.c:6041-6266) */
     enum { HQ_CLK_STEP0 = 0, HQ_CLK_SHELL1, HQ_CLK_INT0, HQ_CLK_INT1, HQ_CLK_CHAIN0, HQ_CLK_CHAIN1, HQ_CLK_N, HQ_CLK_SLOTS = 64 };
     struct hq_clock_slot { hipEvent_t e[HQ_CLK_N] = {}; bool used[HQ_CLK_N] = {}; bool pending = false; };
-    bool phase_clock = false;
     bool clock_skip = false;          /* this step is not one of a timed batch's sampled steps */
     std::vector<hq_clock_slot> clock;
     size_t clock_at = 0;
@@ -950,7 +943,7 @@ static void hq_clock_harvest_all(hq_ctx* c, bool wait)
     for (auto& sl : c->clock) hq_clock_harvest(c, sl, wait);
 }
 
-static bool hq_clock_on(const hq_ctx* c) { return c->phase_clock || c->timing; }
+static bool hq_clock_on(const hq_ctx* c) { return hq_set(c->opts.phase_timing) || c->timing; }
 
 /* a new step: take the next slot of the ring (the step that used it HQ_CLK_SLOTS steps ago is long done) */
 static void hq_clock_begin(hq_ctx* c)
@@ -958,7 +951,7 @@ static void hq_clock_begin(hq_ctx* c)
     if (!hq_clock_on(c)) return;
     /* a timed batch (bench.py's timed region) samples every fourth step: six more event records per step are host time
      * that a rank of a multi-GPU run, whose step is ~160 us, should not pay in full; hq_options.phase_timing records all */
-    if (!c->phase_clock && (c->step & 3) != 0) {
+    if (!hq_set(c->opts.phase_timing) && (c->step & 3) != 0) {
         c->clock_skip = true;
         return;
     }
@@ -1131,7 +1124,9 @@ static bool hq_use_brick_stream(hq_ctx* c)
      * 0.145 -> 0.153 (2 003 / 491 patches: the two cross-stream waits per step cost more than the thin shell's launch):
      * on by default only where the shell is more than eight rounds of patch workgroups (two per CU) */
     const bool solo = !hq_has_transport(c) && c->nranks == 1 && c->plan.npatches > 16 * c->plan.grid_cus;
-    const bool want = c->opt_brick_stream < 0 ? solo : c->opt_brick_stream != 0;
+    /* (default: on a context that steps alone, where the shell's patch launch then runs BESIDE the first round of brick
+     *  workgroups instead of ahead of it) */
+    const bool want = hq_given(c->opts.brick_stream) ? c->opts.brick_stream != 0 : solo;
     if (!want || !(c->overlap || (!hq_has_transport(c) && c->nranks == 1)) || c->stream_masked || c->bricks.nunits <= 0 || c->plan.npatches <= 0) return false;
     if (!c->bstream) {
         int prio_lo = 0, prio_hi = 0;
@@ -1167,7 +1162,7 @@ static int hq_phase(hq_ctx* c, int ph)
              * patches' launch instead of following it behind a 7 us launch gap -- an eighth of the 64M box has 964
              * patches: 20 + 7 + 14 us in two launches, 27 us in one (rank-alone trace: 175.5 -> 170.7 us per step; the
              * chain then starts 7 us later and still ends 20 us before the brick launch does) */
-            if (c->overlap && !hq_patch_uses_pers(&c->plan) && nb > 0 && nb + ne <= 2 * c->opt_merge_rounds * c->plan.grid_cus) { nb += ne; ne = 0; }
+            if (c->overlap && !hq_patch_uses_pers(&c->plan) && nb > 0 && nb + ne <= 2 * hq_value_or(c->opts.patch_merge_rounds, 2) * c->plan.grid_cus) { nb += ne; ne = 0; }
             const bool bs = hq_use_brick_stream(c);
             if (c->overlap) HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_shared, 0));   /* last step's shared displacements */
             if (bs) {
@@ -1181,7 +1176,7 @@ static int hq_phase(hq_ctx* c, int ph)
             auto launch_bricks = [&]() {
                 if (c->bricks.nunits > 0)
                     hq_brick_launch(&c->bricks, c->d_u[c->now], c->d_u[c->prev], c->d_u[c->spare], c->plan.d_nt3, F, c->dt2,
-                                    bs ? c->bstream : c->stream, c->opt_brick_light < 0 ? c->overlap : c->opt_brick_light != 0);
+                                    bs ? c->bstream : c->stream, hq_given(c->opts.brick_by_component) ? c->opts.brick_by_component != 0 : c->overlap);
                 if (bs) hipEventRecord(c->ev_bricks, c->bstream);
             };
             hq_mark(c);
@@ -1272,7 +1267,7 @@ static int hq_phase(hq_ctx* c, int ph)
             if (c->nOI) {
                 /* the update also packs the displacement sharing (phase 5 then only hands the records on) */
                 hq_ipc_args ia = {};
-                const bool fuse = c->opt_fused_share && !(c->debug_halo && (hq_ipc_ready(c) || c->host_xchg));
+                const bool fuse = !hq_set(c->opts.no_fused_share) && !(c->debug_halo && (hq_ipc_ready(c) || c->host_xchg));
                 double* s_out = fuse ? c->an.d_s_out : nullptr;
                 double* const* s_dst = nullptr;
                 if (fuse && c->group && c->an.d_s_dst && !c->debug_halo) s_dst = c->an.d_s_dst;
@@ -1474,9 +1469,9 @@ static int hq_setup_interface(hq_ctx* c, const hq_desc* d)
         HQ_TRY(upload(ptr, &c->d_oi_ptr));
         HQ_TRY(upload(pos, &c->d_oi_pos));
     }
-    if (hq_patch_set_interface(&c->plan, slot.data(), (int64_t)c->N, &c->bytes) != 0)
+    if (hq_patch_set_interface(c->opts, &c->plan, slot.data(), (int64_t)c->N, &c->bytes) != 0)
         return hq_fail(HQ_ERR_NOMEM, "interface tables: %s", hq_patch_error());
-    if (!hq_opt_flag("HQ_NO_OVERLAP")) {
+    if (!hq_set(c->opts.no_overlap)) {
         /* the exchange chain is short and latency-bound: let its kernels (and RCCL's) get CUs ahead
          * of the thousands of interior patch workgroups queued on the compute stream */
         int prio_lo = 0, prio_hi = 0;
@@ -1494,7 +1489,7 @@ static int hq_setup_interface(hq_ctx* c, const hq_desc* d)
         /* whether the chain really runs beside the interior patches is decided with the transport:
          * hq_comm_init (RCCL between GPUs: yes) / hq_group_link (copies inside one GPU: no, see there) */
         c->can_overlap = true;
-        if (hq_opt_has("HQ_RESERVE_CUS")) c->reserve_cus = std::max(0, hq_opt_int("HQ_RESERVE_CUS", 8));
+        c->reserve_cus = hq_value_or(c->opts.reserve_cus, 8);
     }
     return HQ_OK;
 }
@@ -1554,7 +1549,7 @@ static int hq_field_to_host(hq_ctx* c, const hq_real* dev, hq_real* host)
     return HQ_OK;
 }
 
-static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out);
+static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, hq_ctx** out);
 
 /* the caller's n_t rows (solver_float at the ABI) as the doubles the planners and kernels work with: the caller's own
  * array where hq_real is double, a widened copy in `store` otherwise */
@@ -1582,10 +1577,7 @@ extern "C" int hq_create_opts(const hq_desc* d, int device, const hq_options* op
     if (opts && opts->size < sizeof(uint64_t)) return hq_fail(HQ_ERR_ARG, "hq_options.size is not set (hq_options_init)%s", "");
     hq_options full;
     hq_options_resolve(&full, opts);                   /* the environment is read here, once, and only if allowed */
-    hq_opt_scope scope(&full);
-    int rc = hq_create_impl(d, device, out);
-    if (rc == HQ_OK && out && *out) (*out)->opts = full;
-    return rc;
+    return hq_create_impl(d, device, full, out);
 }
 
 extern "C" int hq_create(const hq_desc* d, int device, hq_ctx** out) { return hq_create_opts(d, device, nullptr, out); }
@@ -1598,7 +1590,7 @@ extern "C" int hq_get_options(hq_ctx* c, hq_options* out, uint64_t size)
     return HQ_OK;
 }
 
-static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
+static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, hq_ctx** out)
 {
     if (!d || !out) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     *out = nullptr;
@@ -1618,6 +1610,7 @@ static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
     hq_ctx* c = new (std::nothrow) hq_ctx();
     if (!c) return hq_fail(HQ_ERR_NOMEM, "out of host memory%s", "");
     c->device = device;
+    c->opts = opts;
     c->E = d->lenum; c->N = d->nharbored; c->ldnnum = d->ldnnum;
     c->dt = d->deltaT; c->dt2 = d->deltaT * d->deltaT;
     c->rank = d->rank; c->nranks = d->nranks > 0 ? d->nranks : 1;
@@ -1675,14 +1668,14 @@ static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
      */
     if (variant == HQ_VARIANT_PATCH && !d->node_xyz) {
         static bool warned = false;
-        if (!warned && !hq_opt_flag("HQ_QUIET")) {
+        if (!warned && !hq_set(opts.quiet)) {
             warned = true;
             fprintf(stderr, "hq_create: hq_desc.node_xyz is NULL -- no bricks, no lattice / stencil patches (fixed runs of the node "
                             "order, element-form kernels only): expect about a third of the throughput; pass node_t.x/y/z\n");
         }
     }
     /* HQ_PATCH_VERBOSE: where hq_create's time goes */
-    const bool verbose = hq_opt_flag("HQ_PATCH_VERBOSE");
+    const bool verbose = hq_set(opts.verbose);
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!verbose) return;
@@ -1699,12 +1692,12 @@ static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
     std::vector<hq_messenger> p_msg[4];
     hq_brick_host BH;
     const hq_real *h_tm1 = d->tm1, *h_tm2 = d->tm2;
-    if (variant == HQ_VARIANT_PATCH && d->node_xyz && !(hq_opt_on("HQ_NO_BRICKS"))) {
+    if (variant == HQ_VARIANT_PATCH && d->node_xyz && !hq_set(opts.no_bricks)) {
         std::vector<char> excl;
         if ((rc = hq_brick_excluded(d, excl)) != HQ_OK) return bail(rc);
         hq_mat_src ms;
         ms.edata = d->edata; ms.dt = d->deltaT; ms.bbase = d->mat_bbase; ms.thr_damp = d->mat_threshold_damping; ms.thr_vpvs = d->mat_threshold_vpvs;
-        if (hq_brick_plan_host(c->E, c->N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab, excl.data(), &BH, &ms) != 0)
+        if (hq_brick_plan_host(opts, c->E, c->N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab, excl.data(), &BH, &ms) != 0)
             return bail(hq_fail(HQ_ERR_ARG, "brick plan: %s", hq_patch_error()));
         lap("brick plan");
     }
@@ -1797,7 +1790,7 @@ static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
 
     if ((rc = hq_dev_alloc(c, &c->d_halo_err, 4)) != HQ_OK) return bail(rc);
     if (hipMemset(c->d_halo_err, 0, 4 * sizeof(int32_t)) != hipSuccess) return bail(hq_fail(HQ_ERR_DEVICE, "memset%s", ""));
-    if (hq_opt_on("HQ_DEBUG_HALO") && c->nranks > 1) {
+    if (hq_set(opts.debug_halo) && c->nranks > 1) {
         /* the reference's -DDEBUG exchange: every halo record carries the global id of its node and the
          * receiver checks it (psolve.c:5002-5007, 5058-5069).  Identity = node_t.gnid where the caller
          * passes it, else a 64-bit mix of the node's coordinates (equal on every rank that harbors it). */
@@ -1885,7 +1878,7 @@ static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
                     }
             }
         c->plan.ragged_default = true;
-        rc = hq_patch_build(&c->plan, c->E, c->N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab,
+        rc = hq_patch_build(opts, &c->plan, c->E, c->N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab,
                             dn, seed0.data(), &pb, BH.nb);
         lap("patch plan");
         if (rc == 0 && BH.nb > 0) rc = hq_brick_upload(&c->bricks, BH, &pb);
@@ -1903,11 +1896,6 @@ static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
         lap("schedules, interface");
     }
     if (hipDeviceSynchronize() != hipSuccess) return bail(hq_fail(HQ_ERR_DEVICE, "upload failed%s", ""));
-    c->opt_brick_stream = hq_opt_has("HQ_BRICK_STREAM") ? (hq_opt_on("HQ_BRICK_STREAM") ? 1 : 0) : -1;
-    c->opt_fused_share = !(hq_opt_on("HQ_NO_FUSED_SHARE"));
-    c->phase_clock = hq_opt_on("HQ_PHASE_TIMING");
-    if (hq_opt_has("HQ_PATCH_MERGE_ROUNDS")) c->opt_merge_rounds = std::max(0, hq_opt_int("HQ_PATCH_MERGE_ROUNDS", 1));
-    if (hq_opt_has("HQ_BRICK_BY_COMPONENT")) c->opt_brick_light = hq_opt_int("HQ_BRICK_BY_COMPONENT", 0) != 0;
     c->h2d_bytes = c->d2h_bytes = 0;          /* the counters of hq_info start with the first call behind hq_create */
     *out = c;
     return HQ_OK;
@@ -1925,9 +1913,8 @@ static int hq_create_impl(const hq_desc* d, int device, hq_ctx** out)
  */
 extern "C" int hq_plan_check(const hq_desc* d, int64_t report[8])
 {
-    hq_options chk_opts;                              /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
-    hq_options_resolve(&chk_opts, nullptr);
-    hq_opt_scope chk_scope(&chk_opts);
+    hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
+    hq_options_resolve(&opts, nullptr);
     if (!d || !report || d->lenum < 0 || d->nharbored <= 0 || (d->lenum && !d->lnid))
         return hq_fail(HQ_ERR_ARG, "inconsistent mesh description%s", "");
     const int64_t E = d->lenum, N = d->nharbored;
@@ -1945,11 +1932,10 @@ extern "C" int hq_plan_check(const hq_desc* d, int64_t report[8])
     }
     hq_dangling dn;
     dn.n = (int32_t)l_id.size(); dn.id = l_id.data(); dn.ptr = l_ptr.data(); dn.anchor = l_anc.data();
-    hq_patch_cfg cfg = hq_patch_cfg_from_env();
-    if (dn.n > 0 && cfg.vmax == 0) cfg.vmax = 384;
+    bool want_lattice = false;
+    const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, d->node_xyz != nullptr, &want_lattice);
     hq_patch_host H;
-    const bool want_lattice = !hq_opt_flag("HQ_PATCH_NO_LATTICE") && d->node_xyz && cfg.pmax >= HQ_LAT_ACC;
-    if (hq_patch_plan_host(cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
+    if (hq_patch_plan_host(opts, cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
         return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
     const hq_lattice_tab& T = hq_lattice();
     int64_t nlat = 0, passes = 0, lpasses = 0, instr = 0, bad = 0;
@@ -2000,7 +1986,7 @@ extern "C" int hq_plan_check(const hq_desc* d, int64_t report[8])
             }
     }
     for (int64_t n = 0; n < N; n++) if (covered[(size_t)n] != 1) bad++;
-    if (hq_opt_flag("HQ_PATCH_VERBOSE")) {                      /* owned-node histogram of the patches */
+    if (hq_set(opts.verbose)) {                                 /* owned-node histogram of the patches */
         int64_t hist[8] = { 0 }, hp[8] = { 0 };
         for (auto& D : H.desc) {
             int b = D.nown <= 8 ? 0 : D.nown <= 64 ? 1 : D.nown <= 128 ? 2 : D.nown <= 256 ? 3 : D.nown < 512 ? 4 : D.nown == 512 ? 5 : D.nown <= 640 ? 6 : 7;
@@ -2042,9 +2028,8 @@ extern "C" int hq_stencil_coefficients(double out[16])
  */
 extern "C" int hq_stencil_plan_check(const hq_desc* d, int64_t report[6])
 {
-    hq_options chk_opts;                              /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
-    hq_options_resolve(&chk_opts, nullptr);
-    hq_opt_scope chk_scope(&chk_opts);
+    hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
+    hq_options_resolve(&opts, nullptr);
     if (!d || !report || d->lenum < 0 || d->nharbored <= 0 || (d->lenum && !d->lnid) || !d->node_xyz)
         return hq_fail(HQ_ERR_ARG, "inconsistent mesh description (node_xyz is needed)%s", "");
     const int64_t E = d->lenum, N = d->nharbored;
@@ -2062,11 +2047,10 @@ extern "C" int hq_stencil_plan_check(const hq_desc* d, int64_t report[6])
     }
     hq_dangling dn;
     dn.n = (int32_t)l_id.size(); dn.id = l_id.data(); dn.ptr = l_ptr.data(); dn.anchor = l_anc.data();
-    hq_patch_cfg cfg = hq_patch_cfg_from_env();
-    if (dn.n > 0 && cfg.vmax == 0) cfg.vmax = 384;
+    bool want_lattice = false;
+    const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, true, &want_lattice);
     hq_patch_host H;
-    const bool want_lattice = !hq_opt_flag("HQ_PATCH_NO_LATTICE") && cfg.pmax >= HQ_LAT_ACC;
-    if (hq_patch_plan_host(cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
+    if (hq_patch_plan_host(opts, cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
         return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
     int64_t ntab = 0, nfull = 0, nbnd_tot = 0, ncorner = 0, bad = 0;
 #pragma omp parallel for schedule(dynamic, 64) reduction(+ : ntab, nfull, nbnd_tot, ncorner, bad)
@@ -2194,9 +2178,8 @@ static thread_local int64_t g_brick_check_extra[4];    /* the last check's ragge
 
 extern "C" int hq_brick_plan_check(const hq_desc* d, int64_t report[8])
 {
-    hq_options chk_opts;                              /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
-    hq_options_resolve(&chk_opts, nullptr);
-    hq_opt_scope chk_scope(&chk_opts);
+    hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
+    hq_options_resolve(&opts, nullptr);
     if (!d || !report || d->lenum < 0 || d->nharbored <= 0 || (d->lenum && !d->lnid) || !d->node_xyz || !d->eTable || !d->nTable)
         return hq_fail(HQ_ERR_ARG, "inconsistent mesh description (node_xyz is needed)%s", "");
     const int64_t E = d->lenum, N = d->nharbored;
@@ -2215,7 +2198,7 @@ extern "C" int hq_brick_plan_check(const hq_desc* d, int64_t report[8])
     ms.edata = d->edata; ms.dt = d->deltaT; ms.bbase = d->mat_bbase; ms.thr_damp = d->mat_threshold_damping; ms.thr_vpvs = d->mat_threshold_vpvs;
     std::vector<double> nt64;
     const double* ntab = hq_ntable64(d, nt64);
-    if (hq_brick_plan_host(E, N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab, excl.data(), &B, &ms) != 0)
+    if (hq_brick_plan_host(opts, E, N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab, excl.data(), &B, &ms) != 0)
         return hq_fail(HQ_ERR_ARG, "brick plan: %s", hq_patch_error());
     int64_t bad = 0, nchecked = 0;
     for (int k = 0; k < 8; k++) report[k] = 0;
@@ -2407,13 +2390,13 @@ extern "C" int hq_brick_plan_check(const hq_desc* d, int64_t report[8])
         }
         hq_dangling dn;
         dn.n = (int32_t)l_id.size(); dn.id = l_id.data(); dn.ptr = l_ptr.data(); dn.anchor = l_anc.data();
-        hq_patch_cfg cfg = hq_patch_cfg_from_env();
-        if (dn.n > 0 && cfg.vmax == 0) cfg.vmax = 384;
+        bool want_lattice = false;                   /* (not asked for: behind bricks the shell is planned without) */
+        const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, true, &want_lattice);
         hq_patch_host Ha, Hb;
         std::vector<int32_t> all((size_t)E);
         for (int64_t e = 0; e < E; e++) all[(size_t)e] = (int32_t)e;
-        if (hq_patch_plan_host(cfg, E, N, p_lnid.data(), p_xyz.data(), dn, false, &Ha, B.nb) != 0 ||
-            hq_patch_plan_host(cfg, E, N, p_lnid.data(), p_xyz.data(), dn, false, &Hb, B.nb, &all) != 0)
+        if (hq_patch_plan_host(opts, cfg, E, N, p_lnid.data(), p_xyz.data(), dn, false, &Ha, B.nb) != 0 ||
+            hq_patch_plan_host(opts, cfg, E, N, p_lnid.data(), p_xyz.data(), dn, false, &Hb, B.nb, &all) != 0)
             return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
         if (Ha.pelem != Hb.pelem || Ha.halo != Hb.halo || Ha.pidx != Hb.pidx || Ha.desc.size() != Hb.desc.size() || Ha.ds_ent != Hb.ds_ent) bad++;
         for (size_t q = 0; q < Ha.desc.size() && q < Hb.desc.size(); q++)
@@ -2596,7 +2579,7 @@ static int hq_mask_compute_stream(hq_ctx* c)
     /* opt-in (HQ_CU_MASK=1): measured on one rank of an 8-way split of the 64M box alone on the GPU
      * (profiles/r03/rank_alone_trace.txt), the chain's kernels then do run beside the brick launch, but that launch
      * -- 512 workgroups for 496 slots -- takes 164 us instead of 122: a second, nearly empty round */
-    if (!(hq_opt_on("HQ_CU_MASK"))) return HQ_OK;
+    if (!hq_set(c->opts.cu_mask)) return HQ_OK;
     hipDeviceProp_t prop;
     HQ_HIP(hipGetDeviceProperties(&prop, c->device));
     const int ncu = prop.multiProcessorCount;
@@ -2634,7 +2617,6 @@ extern "C" int hq_comm_unique_id(void* id128)
 
 extern "C" int hq_comm_init(hq_ctx* c, const void* id128)
 {
-    hq_opt_scope opt_scope(c ? &c->opts : nullptr);
     if (!c || !id128) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
     HQ_TRY(hq_rccl_load());
@@ -2643,7 +2625,7 @@ extern "C" int hq_comm_init(hq_ctx* c, const void* id128)
     memcpy(&id, id128, sizeof id);
     HQ_NCCL(g_rccl.CommInitRank(&c->comm, c->nranks, id, c->rank));
     /* between GPUs the exchange is latency the interior patches can hide: run the chain on its own stream */
-    c->overlap = c->can_overlap && !(hq_opt_off("HQ_OVERLAP"));
+    c->overlap = c->can_overlap && c->opts.overlap != 0;
     return hq_mask_compute_stream(c);
 }
 
@@ -2675,13 +2657,12 @@ extern "C" int hq_comm_selftest(hq_ctx* c, int32_t count)
 
 extern "C" int hq_comm_init_host(hq_ctx* c, hq_host_exchange_fn fn, void* user)
 {
-    hq_opt_scope opt_scope(c ? &c->opts : nullptr);
     if (!c || !fn) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
     c->host_xchg = fn;
     c->host_user = user;
     /* as between GPUs: the chain on its own stream, so that the host waits for the exchange stream only */
-    c->overlap = c->can_overlap && !(hq_opt_off("HQ_OVERLAP"));
+    c->overlap = c->can_overlap && c->opts.overlap != 0;
     return hq_mask_compute_stream(c);
 }
 
@@ -2756,9 +2737,10 @@ static int hq_ipc_prepare(hq_ctx* c)
      * holds it either, so remote stores are seen as well -- for runtimes that will not export a fine-grained
      * allocation), and coarse-grained as the last resort (ranks of ONE device only).  HQ_IPC_COARSE=1 / HQ_IPC_ARENA=
      * fine | uncached | coarse pins the kind (tests). */
-    bool coarse = hq_opt_on("HQ_IPC_COARSE");
+    const char* coarse_env = hq_opt_env_only(c->opts, "HQ_IPC_COARSE");
+    bool coarse = coarse_env && atoi(coarse_env) != 0;
     int first_kind = coarse ? 2 : 0, last_kind = 2;
-    if (hq_opt_has("HQ_IPC_ARENA")) first_kind = last_kind = std::min(2, std::max(0, hq_opt_int("HQ_IPC_ARENA", 0)));
+    if (hq_given(c->opts.ipc_arena)) first_kind = last_kind = std::min(2, c->opts.ipc_arena);
     for (int attempt = first_kind; attempt <= last_kind; attempt++) {
         hipError_t e = attempt == 0 ? hipExtMallocWithFlags(&I->arena, I->arena_bytes, hipDeviceMallocFinegrained)
                      : attempt == 1 ? hipExtMallocWithFlags(&I->arena, I->arena_bytes, hipDeviceMallocUncached)
@@ -2797,15 +2779,13 @@ static int hq_ipc_prepare(hq_ctx* c)
     B.reserved = (int32_t)(dump_off / 8);
     if (c->debug_halo)
         for (int x = 0; x < 4; x++) I->d_in_id[x] = (int64_t*)((char*)I->arena + B.id_off[x]);
-    if (hq_opt_double("HQ_IPC_TIMEOUT_MS", 0.0) > 0)
-        I->timeout_ticks = (unsigned long long)(hq_opt_double("HQ_IPC_TIMEOUT_MS", 0.0) * 1.0e5);
+    if (hq_set(c->opts.ipc_timeout_ms)) I->timeout_ticks = (unsigned long long)(c->opts.ipc_timeout_ms * 1.0e5);
     c->ipc = I;
     return HQ_OK;
 }
 
 extern "C" int hq_comm_ipc_export(hq_ctx* c, void* blob)
 {
-    hq_opt_scope opt_scope(c ? &c->opts : nullptr);
     if (!c || !blob) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     HQ_TRY(hq_ipc_prepare(c));
     memset(blob, 0, HQ_IPC_BLOB_BYTES);
@@ -2898,15 +2878,14 @@ static int hq_ipc_connect(hq_ctx* c, const char* blobs)
     }
     I->ready = true;
     I->loopback = loop;
-    if (loop && hq_opt_has("HQ_LOOPBACK_DELAY_US")) I->delay_ticks = (unsigned long long)(hq_opt_double("HQ_LOOPBACK_DELAY_US", 0.0) * 100.0);
+    if (loop && hq_given(c->opts.loopback_delay_us)) I->delay_ticks = (unsigned long long)(c->opts.loopback_delay_us * 100.0);
     /* as between GPUs: the chain on its own stream beside the interior work */
-    c->overlap = c->can_overlap && !(hq_opt_off("HQ_OVERLAP"));
+    c->overlap = c->can_overlap && c->opts.overlap != 0;
     return hq_mask_compute_stream(c);
 }
 
 extern "C" int hq_comm_init_ipc(hq_ctx* c, const void* blobs)
 {
-    hq_opt_scope opt_scope(c ? &c->opts : nullptr);
     if (!c || !blobs) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     if (!c->ipc) return hq_fail(HQ_ERR_STATE, "hq_comm_init_ipc needs the blobs of hq_comm_ipc_export (this rank's among them)%s", "");
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
@@ -2925,7 +2904,6 @@ extern "C" int hq_comm_init_ipc_n(hq_ctx* c, const void* blobs, int32_t nblobs)
 
 extern "C" int hq_comm_init_loopback(hq_ctx* c)
 {
-    hq_opt_scope opt_scope(c ? &c->opts : nullptr);
     if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     HQ_TRY(hq_ipc_prepare(c));
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
@@ -2936,7 +2914,6 @@ extern "C" int hq_comm_init_loopback(hq_ctx* c)
 
 extern "C" int hq_group_link(hq_ctx** ctxs, int32_t n)
 {
-    hq_opt_scope opt_scope((ctxs && n > 0 && ctxs[0]) ? &ctxs[0]->opts : nullptr);      /* the group follows its first member's options */
     if (!ctxs || n < 1) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
     for (int32_t i = 0; i < n; i++) {
         if (!ctxs[i] || ctxs[i]->rank != i || ctxs[i]->nranks != n)
@@ -2973,7 +2950,7 @@ extern "C" int hq_group_link(hq_ctx** ctxs, int32_t n)
      * COPIES (hipMemcpyAsync), whose coherence with the destination device's L2 the runtime answers for -- plain peer
      * stores into coarse-grained memory do not have it; the IPC transport with its fine-grained arena is the
      * peer-store path between devices */
-    const bool direct = one_device && !hq_opt_flag("HQ_GROUP_COPIES");
+    const bool direct = one_device && !hq_set(ctxs[0]->opts.group_copies);      /* the group follows its first member's options */
     if (direct) {
         for (int32_t i = 0; i < n; i++) {
             hq_ctx* c = ctxs[i];
@@ -3019,7 +2996,7 @@ extern "C" int hq_group_link(hq_ctx** ctxs, int32_t n)
      * the device anyway -- and pay for its events: the 64M box in 8 in-process partitions steps in 2.54 ms on one
      * stream per partition against 3.28 ms with the chain on a second one (round 2; HQ_OVERLAP=1 forces it, which is
      * how the GPU tests cover that path without a second GPU). */
-    const bool ov = hq_opt_on("HQ_OVERLAP");
+    const bool ov = hq_set(ctxs[0]->opts.overlap);
     for (int32_t i = 0; i < n; i++) { ctxs[i]->group = g; ctxs[i]->overlap = ov && ctxs[i]->can_overlap; }
     for (size_t k = 0; k < tables.size(); k++) {
         hq_dev_schedule* s = tables[k].which ? &tables[k].c->dn : &tables[k].c->an;

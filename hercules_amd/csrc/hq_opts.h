@@ -1,13 +1,11 @@
 /*
- * hq_opts.h -- how the planners and the engine read their settings: hq_options (include/hq_solver.h; the typed,
- * per-context form, after the reference's explicit Param struct psolve.c:193-284) with the HQ_* environment variables
- * as overrides for experiments where the caller allows them (hq_options.allow_env).  One resolver, run once per context
- * at hq_create_opts (hq_options_resolve): the field, overridden by the environment where allowed; else the default.
+ * hq_opts.h -- where a context's settings come from: hq_options (include/hq_solver.h; the typed, per-context form, after
+ * the reference's explicit Param struct psolve.c:193-284) with the HQ_* environment variables as overrides for
+ * experiments where the caller allows them (hq_options.allow_env).  One resolver, run once per context at hq_create_opts
+ * (hq_options_resolve): the field, overridden by the environment where allowed; else -1 = the library's default.
  *
- * The options "in force" are a thread-local pointer: hq_create_opts points it at the caller's struct while it plans,
- * every later entry point that reads a setting points it at the context's copy (hq_opt_scope).  Planners are called
- * with it in place; they never call getenv themselves.  The pointer is thread-local: read every setting BEFORE an
- * OpenMP region, never inside one (a worker thread sees no options at all).
+ * Nothing else is kept here: the resolved struct lives in the context (hq_ctx.opts), planners and set-up code take it
+ * as a `const hq_options&` parameter and read its fields.  g_opt_table is the only place that names a field's variable.
  */
 #ifndef HQ_OPTS_H
 #define HQ_OPTS_H
@@ -41,10 +39,6 @@ static const hq_opt_entry g_opt_table[] = {
 #undef HQ_OPT_I
 #undef HQ_OPT_D
 
-/* the RESOLVED options in force on this thread (hq_options_resolve): nothing below reads the environment for a setting
- * that has a field */
-static thread_local const hq_options* g_opt_in_force = nullptr;
-
 static void hq_options_defaults(hq_options* o)
 {
     o->size = sizeof(hq_options);
@@ -64,12 +58,6 @@ static void hq_options_adopt(hq_options* dst, const hq_options* src)
     const size_t n = (size_t)(src->size < sizeof(hq_options) ? src->size : sizeof(hq_options));
     if (n > sizeof(uint64_t)) memcpy((char*)dst + sizeof(uint64_t), (const char*)src + sizeof(uint64_t), n - sizeof(uint64_t));
     dst->size = sizeof(hq_options);
-}
-
-static const hq_opt_entry* hq_opt_find(const char* env)
-{
-    for (const hq_opt_entry& e : g_opt_table) if (!strcmp(e.env, env)) return &e;
-    return nullptr;
 }
 
 /* HQ_IPC_ARENA in the environment is a word; a switch that is set but empty (HQ_PATCH_NO_ISO=) is on */
@@ -102,62 +90,16 @@ static void hq_options_resolve(hq_options* out, const hq_options* caller)
     }
 }
 
-/* settings without a field (diagnostics of experiment builds: HQ_PATCH_NT, HQ_PATCH_DIAG, HQ_IPC_COARSE, ...): from the
- * environment, and only where the options in force allow it */
-static const char* hq_opt_env_only(const char* env)
-{
-    if (!g_opt_in_force || g_opt_in_force->allow_env != 1) return nullptr;
-    const char* v = getenv(env);
-    return v;
-}
+/* a resolved field: given at all (not "default")?  its value or the default?  a switch that is on (the environment's
+ * HQ_X=, HQ_X=1 came in as 1, HQ_X=0 as 0)?  The same for int32_t and double fields. */
+template <typename T> static inline bool hq_given(T f) { return f >= 0; }
+template <typename T> static inline T hq_value_or(T f, T def) { return f >= 0 ? f : def; }
+template <typename T> static inline bool hq_set(T f) { return f > 0; }
 
-/* was the setting given at all (a field that is not "default")? */
-static bool hq_opt_has(const char* env)
+/* a setting without a field (HQ_IPC_COARSE): the environment's word where these options allow it, else null */
+static inline const char* hq_opt_env_only(const hq_options& o, const char* env)
 {
-    const hq_opt_entry* e = hq_opt_find(env);
-    if (!e) { const char* v = hq_opt_env_only(env); return v && *v; }
-    if (!g_opt_in_force) return false;
-    return e->kind == 0 ? *(const int32_t*)((const char*)g_opt_in_force + e->off) >= 0
-                        : *(const double*)((const char*)g_opt_in_force + e->off) >= 0.0;
+    return o.allow_env == 1 ? getenv(env) : nullptr;
 }
-
-static int hq_opt_int(const char* env, int def)
-{
-    const hq_opt_entry* e = hq_opt_find(env);
-    if (!e) { const char* v = hq_opt_env_only(env); return v && *v ? atoi(v) : def; }
-    if (g_opt_in_force && e->kind == 0) {
-        const int32_t f = *(const int32_t*)((const char*)g_opt_in_force + e->off);
-        if (f >= 0) return f;
-    }
-    return def;
-}
-
-static double hq_opt_double(const char* env, double def)
-{
-    const hq_opt_entry* e = hq_opt_find(env);
-    if (!e) { const char* v = hq_opt_env_only(env); return v && *v ? atof(v) : def; }
-    if (g_opt_in_force && e->kind == 1) {
-        const double f = *(const double*)((const char*)g_opt_in_force + e->off);
-        if (f >= 0.0) return f;
-    }
-    return def;
-}
-
-static bool hq_opt_on(const char* env) { return hq_opt_int(env, 0) != 0; }
-/* explicitly switched off */
-static bool hq_opt_off(const char* env) { return hq_opt_has(env) && hq_opt_int(env, 1) == 0; }
-/* a switch: on where its field is > 0 (the environment's HQ_X=, HQ_X=1 came in as 1, HQ_X=0 as 0) */
-static bool hq_opt_flag(const char* env)
-{
-    const hq_opt_entry* e = hq_opt_find(env);
-    if (!e) { const char* v = hq_opt_env_only(env); return v && strcmp(v, "0") != 0; }
-    return g_opt_in_force && e->kind == 0 && *(const int32_t*)((const char*)g_opt_in_force + e->off) > 0;
-}
-
-struct hq_opt_scope {
-    const hq_options* saved;
-    explicit hq_opt_scope(const hq_options* o) : saved(g_opt_in_force) { g_opt_in_force = o; }
-    ~hq_opt_scope() { g_opt_in_force = saved; }
-};
 
 #endif /* HQ_OPTS_H */

@@ -47,14 +47,10 @@ static inline int omp_get_thread_num(void) { return 0; }
 
 /* Tuning knobs (environment overrides HQ_PATCH_THREADS / _PMAX / _PMERGE / _NLMAX are
  * read once per plan; defaults from the sweeps in profiles/). */
-/* Lattice-SUBSET patches (domain faces, dashpots, far-face cubes, partition interfaces) through hq_k_patch_stencil too,
- * not only the full lattices?  Measured (docs/LABNOTES.md): 2-3 % faster than the element form on the whole 64 M box, 9 % on
- * its eight in-process partitions -- the default is yes.  HQ_PATCH_RAGGED=0: element form; 2: stencil form except for
- * patches with partition-interface nodes.  -> -1 (not set) or the value. */
-static inline int hq_patch_ragged_env(void)
-{
-    return hq_opt_int("HQ_PATCH_RAGGED", -1);         /* 2: as 1, but patches with partition-interface nodes keep the element form */
-}
+/* hq_options.patch_ragged: lattice-SUBSET patches (domain faces, dashpots, far-face cubes, partition interfaces) through
+ * hq_k_patch_stencil too, not only the full lattices?  Measured (docs/LABNOTES.md): 2-3 % faster than the element form on
+ * the whole 64 M box, 9 % on its eight in-process partitions -- the default is yes.  0: element form; 2: as 1, but patches
+ * with partition-interface nodes keep the element form. */
 
 struct hq_patch_cfg {
     int threads = 512;    /* workgroup size                                          */
@@ -66,30 +62,6 @@ struct hq_patch_cfg {
     int vmax    = 0;      /* extra force accumulators for hanging nodes whose anchors */
                           /* the patch owns (set by the planner when the mesh has any) */
 };
-
-static hq_patch_cfg hq_patch_cfg_from_env(void)
-{
-    hq_patch_cfg c;
-    auto geti = [](const char* n, int def) { return hq_opt_int(n, def); };
-    c.threads = geti("HQ_PATCH_THREADS", c.threads);
-    c.pmax = geti("HQ_PATCH_PMAX", c.pmax);
-    c.pmerge = geti("HQ_PATCH_PMERGE", c.pmerge);
-    c.psplit = geti("HQ_PATCH_PSPLIT", 0);
-    c.nlmax = geti("HQ_PATCH_NLMAX", c.nlmax);
-    if (c.threads < 64) c.threads = 64;
-    if (c.threads > HQ_PATCH_MAX_THREADS) c.threads = HQ_PATCH_MAX_THREADS;
-    c.threads &= ~63;
-    if (c.pmax < 8) c.pmax = 8;
-    if (c.pmerge > c.pmax) c.pmerge = c.pmax;
-    if (c.psplit > c.pmax || c.psplit < 8) c.psplit = c.pmax;
-    if (c.pmerge < 1) c.pmerge = 1;
-    if (c.nlmax < c.pmax + 8) c.nlmax = c.pmax + 8;
-    if (c.nlmax > 0x7fff) c.nlmax = 0x7fff;          /* HQ_PIDX_ROW: 15-bit rows in the element row */
-    c.vmax = geti("HQ_PATCH_VMAX", c.vmax);
-    /* LDS: (6 nlmax + 3 (pmax + vmax)) doubles must fit 160 KiB */
-    while ((6 * (size_t)c.nlmax + 3 * (size_t)(c.pmax + c.vmax)) * 8 > 160 * 1024) c.nlmax -= 8;
-    return c;
-}
 
 struct hq_patch_desc {
     int32_t base;        /* first owned node (global id)          */
@@ -160,7 +132,7 @@ struct hq_patch_plan {
     uint16_t* d_lat_row = nullptr;   /* [1024] LDS row of thread t's local node in a lattice patch             */
     int32_t  ne = 0, ns = 0, nr = 0; /* d_order = nb interface patches | ne other element-form patches | nr stencil patches with
                                       * interface nodes | ns other stencil patches */
-    bool     ragged_default = false; /* set by the caller before hq_patch_build: see hq_patch_ragged_env */
+    bool     ragged_default = false; /* set by the caller before hq_patch_build: what hq_options.patch_ragged = -1 means */
     int32_t  ns_rg = 0;              /* of the ns: ragged patches of <= 512 nodes, between the full lattices and the big ones */
     int32_t  nr_big = 0, ns_big = 0; /* of the nr / ns: patches of more than 512 owned nodes, at the end of their part */
     int32_t  nragged = 0, nstencil = 0;  /* STENCIL patches (nr + ns entries: two for a patch of more than 512 nodes), RAGGED ones among them */
@@ -181,7 +153,7 @@ struct hq_patch_plan {
     int32_t  grid_cus = 256;         /* persistent workgroups to launch: the device's CU count, a multiple of 8 */
     int32_t  max_nacc = 0;           /* accumulator rows the patches need (owned + hanging nodes on owned anchors; 729 for lattices) */
     bool     seeded = false;         /* hq_k_patch_seed: nt3 carries negative mass_simple for nodes whose seed is 0 */
-    int32_t  pipe = 6;               /* HQ_PATCH_PIPE at plan time                                              */
+    int32_t  pipe = 6;               /* hq_options.patch_pipe at plan time, or what hq_patch_build chose         */
     std::vector<char> patch_lat;     /* host copy of the lattice flags                                         */
     int32_t  nb = 0;
     int32_t* d_ds_ptr = nullptr;     /* hanging-node force distribution (compute_adjust) per patch */
@@ -195,13 +167,6 @@ struct hq_patch_plan {
     std::vector<int32_t> patch_base; /* host copy of desc[].base for lookups */
     std::vector<int32_t> patch_nown;
 };
-
-/* HQ_PATCH_PIPE: 6 (default) = hq_k_patch_seed where the plan fits it (else hq_k_patch_pers, else hq_k_patch_step),
- * 4 = hq_k_patch_pers where it fits, 0 = hq_k_patch_step always */
-static int hq_patch_kernel_choice(void)              /* read when a plan is built and kept in it (hq_patch_plan.pipe) */
-{
-    return hq_opt_int("HQ_PATCH_PIPE", 6);
-}
 
 static thread_local std::string g_patch_err;
 static const char* hq_patch_error(void) { return g_patch_err.c_str(); }
@@ -695,12 +660,40 @@ static void hq_patch_candidates(int64_t E, const int32_t* lnid, const hq_danglin
     for (auto& v : part) cand.insert(cand.end(), v.begin(), v.end());
 }
 
-static int hq_patch_plan_host(const hq_patch_cfg& cfg, int64_t E, int64_t N, const int32_t* lnid,
+/* the planner's configuration out of the options, as hq_create and the plan checks use it: `hanging` = the mesh has
+ * hanging nodes the patches distribute themselves, `have_xyz` = the caller passed node coordinates.  *want_lattice: plan
+ * with lattice patches (hq_patch_build asks in addition whether a persistent kernel can run them). */
+static hq_patch_cfg hq_patch_cfg_of(const hq_options& o, bool hanging, bool have_xyz, bool* want_lattice)
+{
+    hq_patch_cfg c;
+    c.threads = hq_value_or(o.patch_threads, c.threads);
+    c.pmax = hq_value_or(o.patch_pmax, c.pmax);
+    c.pmerge = hq_value_or(o.patch_pmerge, c.pmerge);
+    c.psplit = hq_value_or(o.patch_psplit, 0);
+    c.nlmax = hq_value_or(o.patch_nlmax, c.nlmax);
+    if (c.threads < 64) c.threads = 64;
+    if (c.threads > HQ_PATCH_MAX_THREADS) c.threads = HQ_PATCH_MAX_THREADS;
+    c.threads &= ~63;
+    if (c.pmax < 8) c.pmax = 8;
+    if (c.pmerge > c.pmax) c.pmerge = c.pmax;
+    if (c.psplit > c.pmax || c.psplit < 8) c.psplit = c.pmax;
+    if (c.pmerge < 1) c.pmerge = 1;
+    if (c.nlmax < c.pmax + 8) c.nlmax = c.pmax + 8;
+    if (c.nlmax > 0x7fff) c.nlmax = 0x7fff;          /* HQ_PIDX_ROW: 15-bit rows in the element row */
+    c.vmax = hq_value_or(o.patch_vmax, c.vmax);
+    /* LDS: (6 nlmax + 3 (pmax + vmax)) doubles must fit 160 KiB */
+    while ((6 * (size_t)c.nlmax + 3 * (size_t)(c.pmax + c.vmax)) * 8 > 160 * 1024) c.nlmax -= 8;
+    if (hanging && c.vmax == 0) c.vmax = 384;
+    *want_lattice = !hq_set(o.patch_no_lattice) && have_xyz && c.pmax >= HQ_LAT_ACC;
+    return c;
+}
+
+static int hq_patch_plan_host(const hq_options& o, const hq_patch_cfg& cfg, int64_t E, int64_t N, const int32_t* lnid,
                               const int32_t* xyz, const hq_dangling& dn, bool want_lattice, hq_patch_host* H, int64_t n0 = 0,
                               std::vector<int32_t>* cand_cache = nullptr)
 {
     /* HQ_PATCH_VERBOSE >= 3: where the planner's own time goes */
-    const bool lap_on = hq_opt_int("HQ_PATCH_VERBOSE", 0) > 2;
+    const bool lap_on = o.verbose > 2;
     auto lap_t = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!lap_on) return;
@@ -886,7 +879,7 @@ static int hq_patch_plan_host(const hq_patch_cfg& cfg, int64_t E, int64_t N, con
         {
             std::unordered_map<uint64_t, std::vector<int32_t>> seen;
             int32_t ndistinct = 0;
-            const bool dedup = !hq_opt_flag("HQ_PATCH_NO_DEDUP");
+            const bool dedup = !hq_set(o.patch_no_dedup);
             for (int32_t p = 0; p < P; p++) {
                 hq_patch_desc& D = H->desc[p];
                 D.pidx_off = D.pair_off;
@@ -964,7 +957,7 @@ struct hq_pair_data {
 __device__ unsigned long long* g_hq_stamps = nullptr;
 __device__ unsigned long long* g_hq_wg = nullptr;      /* [grid][2]: shader clock at workgroup start / exit */
 #define HQ_WG_STAMP(k) do { if (threadIdx.x == 0 && g_hq_wg) g_hq_wg[2 * blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-static void hq_patch_report_stamps(void);
+static void hq_patch_report_stamps(const struct hq_patch_plan* P);
 #define HQ_STAMP(k) do { if (DIAG == 6 && threadIdx.x == 0 && g_hq_stamps) g_hq_stamps[8 * (size_t)p + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 #ifndef HQ_STAMP_TID
 #define HQ_STAMP_TID 0     /* the thread whose view of the phases is recorded */
@@ -978,25 +971,17 @@ static void hq_patch_report_stamps(void);
 
 typedef unsigned int hq_u32x4 __attribute__((ext_vector_type(4)));
 
-template <bool NT, typename T>
-__device__ __forceinline__ T hq_ld(const T* p)
-{
-    if (NT) return __builtin_nontemporal_load(p);
-    return *p;
-}
-
 /* element row: local node ids at pidx[gi], coefficients at [gc] */
-template <bool NT>
 __device__ __forceinline__ hq_pair_data hq_pair_load(const uint4* __restrict__ pidx, const double* __restrict__ pc1,
                                                      const double* __restrict__ pc2,
                                                      const double* __restrict__ pbeta, int64_t gi, int64_t gc)
 {
     hq_pair_data d;
-    hq_u32x4 r = hq_ld<NT>(reinterpret_cast<const hq_u32x4*>(pidx) + gi);
+    hq_u32x4 r = reinterpret_cast<const hq_u32x4*>(pidx)[gi];
     d.raw.x = r.x; d.raw.y = r.y; d.raw.z = r.z; d.raw.w = r.w;
-    d.beta = hq_ld<NT>(&pbeta[gc]);
-    d.c1 = hq_ld<NT>(&pc1[gc]);
-    d.c2 = hq_ld<NT>(&pc2[gc]);
+    d.beta = pbeta[gc];
+    d.c1 = pc1[gc];
+    d.c2 = pc2[gc];
     return d;
 }
 
@@ -1013,7 +998,7 @@ __device__ __forceinline__ hq_pair_data hq_pair_load(const uint4* __restrict__ p
  * 5 = conflict-free LDS gathers.  Measured on the 64M box (ms/step): full 3.09, (1) 1.78,
  * (2) 2.14, (3) 2.85, (4) 3.00, (5) 2.83 -- the memory phases alone run at the HBM rate,
  * the element loop adds ~1.3 ms that two workgroups per CU do not overlap (round 2 work). */
-template <bool NT, int DIAG>
+template <int DIAG>
 __global__ void __launch_bounds__(HQ_PATCH_MAX_THREADS, 4)
 hq_k_patch_step(int32_t npatches, int32_t per_xcd, const int32_t* __restrict__ order, int32_t nlmax,
                 const hq_patch_desc* __restrict__ desc,
@@ -1044,7 +1029,7 @@ hq_k_patch_step(int32_t npatches, int32_t per_xcd, const int32_t* __restrict__ o
     const int32_t* __restrict__ hl = halo + (int64_t)p * hstride;
     int32_t hid[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) hid[k] = hq_ld<NT>(&hl[(k * T + tid) / 3]);
+    for (int k = 0; k < 4; k++) hid[k] = hl[(k * T + tid) / 3];
     const hq_patch_desc D = desc[p];
     const int own3 = D.nown * 3, halo3 = D.nhalo * 3;
     for (int i = own3 + tid; i < 3 * D.nacc; i += T) s_f[i] = 0.0;   /* hanging nodes on owned anchors */
@@ -1057,7 +1042,7 @@ hq_k_patch_step(int32_t npatches, int32_t per_xcd, const int32_t* __restrict__ o
     const int o2off = 3 * (nlmax / 2);
     hq_pair_data cur;
     const int cstep = (D.flags & HQ_PATCH_UNIFORM) ? 0 : 1;     /* uniform patch: every row reads coefficient 0 */
-    if (tid < D.npairs) cur = hq_pair_load<NT>(pidx, pc1, pc2, pbeta, D.pidx_off + tid, D.pair_off + cstep * tid);
+    if (tid < D.npairs) cur = hq_pair_load(pidx, pc1, pc2, pbeta, D.pidx_off + tid, D.pair_off + cstep * tid);
 
     {   /* stage: owned nodes are one contiguous run of doubles, halo nodes a gather */
         const hq_real* g1 = u1g + 3 * (int64_t)D.base;
@@ -1072,7 +1057,7 @@ hq_k_patch_step(int32_t npatches, int32_t per_xcd, const int32_t* __restrict__ o
                 if (i < halo3) {
                     int h = i / 3, d = i - 3 * h;
                     int32_t id = hid[k];
-                    if (i0 > 0) id = hq_ld<NT>(&hl[h]);
+                    if (i0 > 0) id = hl[h];
                     int64_t g = 3 * (int64_t)id + d;
                     b1[k] = u1g[g]; b2[k] = u2g[g];
                 }
@@ -1101,20 +1086,20 @@ hq_k_patch_step(int32_t npatches, int32_t per_xcd, const int32_t* __restrict__ o
     if (tid < D.nown) {
         if (iso) {
             const double* q = nt3 + 3 * ((int64_t)D.base + ((D.flags & HQ_PATCH_NTSAME) ? 0 : tid));
-            np[0] = hq_ld<NT>(q);                /* (no copies of loaded values here: a copy waits */
-            np[1] = hq_ld<NT>(q + 1);            /*  for the load; the axes pick at the update)    */
-            np[4] = hq_ld<NT>(q + 2);
+            np[0] = q[0];                        /* (no copies of loaded values here: a copy waits */
+            np[1] = q[1];                        /*  for the load; the axes pick at the update)    */
+            np[4] = q[2];
         } else {
             const double* q = nt + 7 * ((int64_t)D.base + tid);
 #pragma unroll
-            for (int k = 0; k < 7; k++) np[k] = hq_ld<NT>(q + k);
+            for (int k = 0; k < 7; k++) np[k] = q[k];
         }
     }
 
     for (int q = tid; q < (DIAG == 1 ? 0 : D.npairs); q += T) {
         hq_pair_data nxt;
         if (q + T < D.npairs)
-            nxt = hq_pair_load<NT>(pidx, pc1, pc2, pbeta, D.pidx_off + q + T, D.pair_off + cstep * (q + T));
+            nxt = hq_pair_load(pidx, pc1, pc2, pbeta, D.pidx_off + q + T, D.pair_off + cstep * (q + T));
         const uint4 raw = cur.raw;
         const double beta = cur.beta;
         int l[8];
@@ -1185,8 +1170,7 @@ hq_k_patch_step(int32_t npatches, int32_t per_xcd, const int32_t* __restrict__ o
             const double m2 = iso ? np[1] : np[1 + d], m1 = iso ? np[4] : np[4 + d];
             const double x1 = wf ? s_u2[3 * n + d] : s_u1[3 * n + d], x2 = wf ? s_u2[o2off + 3 * n + d] : s_u2[3 * n + d];
             double f = s_f[3 * n + d] + (m2 * x1 - m1 * x2);
-            if (NT) __builtin_nontemporal_store((hq_real)(f / np[0]), out + d);
-            else out[d] = f / np[0];
+            out[d] = f / np[0];
         }
     }
     if (if_ptr) {   /* partition interface: hand the partial force to the exchange (psolve.c:4301) */
@@ -2116,7 +2100,7 @@ static void hq_patch_free(hq_patch_plan* P)
     hq_st_timing_print(P);
 #endif
 #ifdef HQ_PATCH_PROFILING
-    if (P->npatches) hq_patch_report_stamps();
+    if (P->npatches) hq_patch_report_stamps(P);
 #endif
     void* ptrs[] = { P->d_desc, P->d_pidx, P->d_pc1, P->d_pc2, P->d_pbeta, P->d_halo, P->d_src_ptr, P->d_src_ent,
                      P->d_if_ptr, P->d_if_ent, P->d_order, P->d_nt3, P->d_ds_ptr, P->d_ds_ent, P->d_tickets, P->d_lat_row,
@@ -2188,12 +2172,12 @@ static int hq_patch_build_order(hq_patch_plan* P, const int32_t* if_ptr, int64_t
 
 static bool hq_patch_uses_pers(const hq_patch_plan* P);
 
-static int hq_patch_build(hq_patch_plan* P, int64_t E, int64_t N, const int32_t* lnid, const int32_t* xyz,
+static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int64_t N, const int32_t* lnid, const int32_t* xyz,
                           const double* c1, const double* c2, const double* beta, const double* ntab,
                           const hq_dangling& dn, const char* seed0, int64_t* bytes, int64_t n0 = 0)
 {
     hq_patch_host H;
-    const bool plap_on = hq_opt_int("HQ_PATCH_VERBOSE", 0) > 1;
+    const bool plap_on = o.verbose > 1;
     auto plap_t = std::chrono::steady_clock::now();
     auto plap = [&](const char* what) {
         if (!plap_on) return;
@@ -2202,12 +2186,13 @@ static int hq_patch_build(hq_patch_plan* P, int64_t E, int64_t N, const int32_t*
         plap_t = now;
     };
     P->n0 = n0;
-    P->cfg = hq_patch_cfg_from_env();
-    P->pipe = hq_patch_kernel_choice();
-    if (dn.n > 0 && P->cfg.vmax == 0) {
-        P->cfg.vmax = 384;
-        while ((6 * (size_t)P->cfg.nlmax + 3 * (size_t)(P->cfg.pmax + P->cfg.vmax)) * 8 > 160 * 1024) P->cfg.nlmax -= 8;
-    }
+    bool want_lattice = false;
+    P->cfg = hq_patch_cfg_of(o, dn.n > 0, xyz != nullptr, &want_lattice);
+    /* (the hanging nodes' accumulators, where the mesh has any, count against the LDS too) */
+    while ((6 * (size_t)P->cfg.nlmax + 3 * (size_t)(P->cfg.pmax + P->cfg.vmax)) * 8 > 160 * 1024) P->cfg.nlmax -= 8;
+    /* 6 (default) = hq_k_patch_seed where the plan fits it (else hq_k_patch_pers, else hq_k_patch_step), 4 = hq_k_patch_pers
+     * where it fits, 0 = hq_k_patch_step always */
+    P->pipe = hq_value_or(o.patch_pipe, 6);
     /* lattice patches exist for hq_k_patch_pers only: plan with them when the configuration can run it,
      * and again without if this mesh's patches then turn out not to fit it (> 1024 elements in one) */
     auto pers_fits = [&](int32_t nrows, int32_t max_npairs) {
@@ -2215,16 +2200,15 @@ static int hq_patch_build(hq_patch_plan* P, int64_t E, int64_t N, const int32_t*
                max_npairs <= HQ_PERS_THREADS &&
                (12 * (size_t)nrows + 3 * (size_t)(P->cfg.pmax + P->cfg.vmax) + 36) * sizeof(double) <= 160 * 1024;
     };
-    bool want_lattice = !hq_opt_flag("HQ_PATCH_NO_LATTICE") && xyz && P->cfg.pmax >= HQ_LAT_ACC &&
-                        pers_fits(std::max(P->cfg.nlmax, HQ_LAT_ROWS), 0);
+    want_lattice = want_lattice && pers_fits(std::max(P->cfg.nlmax, HQ_LAT_ROWS), 0);
     std::vector<int32_t> cand;                       /* the shell's elements: found once, used by every plan below */
     for (;;) {
-        if (hq_patch_plan_host(P->cfg, E, N, lnid, xyz, dn, want_lattice, &H, n0, &cand) != 0) return -1 /* HQ_ERR_ARG */;
+        if (hq_patch_plan_host(o, P->cfg, E, N, lnid, xyz, dn, want_lattice, &H, n0, &cand) != 0) return -1 /* HQ_ERR_ARG */;
         /* behind bricks the patches are the shell of the mesh -- a few thousand, 15 per CU on the 64M box: the
          * persistent kernels' prologue and work queue cost more than they save there, and one workgroup per patch
          * (hq_k_patch_step, two per CU) fills the device at once: 64M box 1.104 -> 1.060 ms per step, 8M box
          * 0.159 -> 0.148 on the same box.  HQ_PATCH_PIPE overrides. */
-        if (n0 > 0 && !hq_opt_has("HQ_PATCH_PIPE") && P->pipe != 0 && H.desc.size() <= 16384) {
+        if (n0 > 0 && !hq_given(o.patch_pipe) && P->pipe != 0 && H.desc.size() <= 16384) {
             P->pipe = 0;
             if (want_lattice) { want_lattice = false; H = hq_patch_host(); continue; }
         }
@@ -2261,7 +2245,7 @@ static int hq_patch_build(hq_patch_plan* P, int64_t E, int64_t N, const int32_t*
         nt3[3 * n] = (P->seeded && seed0[n]) ? -ntab[7 * n] : ntab[7 * n];
         nt3[3 * n + 1] = ntab[7 * n + 1]; nt3[3 * n + 2] = ntab[7 * n + 4];
     }
-    const bool use_iso = !hq_opt_flag("HQ_PATCH_NO_ISO");
+    const bool use_iso = !hq_set(o.patch_no_iso);
     int32_t nntsame = 0;
     for (auto& D : H.desc) {
         bool iso = use_iso;
@@ -2271,14 +2255,14 @@ static int hq_patch_build(hq_patch_plan* P, int64_t E, int64_t N, const int32_t*
         }
         D.flags = (D.flags & HQ_PATCH_LATTICE) | (iso ? HQ_PATCH_ISO : 0);
         /* interior of a homogeneous region: one n_t row serves the whole patch (bitwise equal rows) */
-        bool same = iso && D.nown > 0 && !hq_opt_flag("HQ_PATCH_NO_NTSAME");
+        bool same = iso && D.nown > 0 && !hq_set(o.patch_no_ntsame);
         for (int32_t n = D.base + 1; n < D.base + D.nown && same; n++)
             same = memcmp(&nt3[3 * (size_t)n], &nt3[3 * (size_t)D.base], 24) == 0;
         if (same) { D.flags |= HQ_PATCH_NTSAME; nntsame++; }
     }
     int32_t nuniform = 0;
-    const bool wform = !(hq_opt_off("HQ_PATCH_WFORM"));
-    if (!hq_opt_flag("HQ_PATCH_NO_UNIFORM")) {
+    const bool wform = o.patch_wform != 0;
+    if (!hq_set(o.patch_no_uniform)) {
         for (auto& D : H.desc) {
             bool uni = D.npairs > 0;
             const int32_t e0 = D.npairs > 0 ? H.pelem[(size_t)D.pair_off] : 0;
@@ -2304,8 +2288,8 @@ static int hq_patch_build(hq_patch_plan* P, int64_t E, int64_t N, const int32_t*
      * distribute (full_only: only the full lattice without dashpot) */
     std::vector<uint32_t> rg_tab;
     std::vector<int64_t> rg_off(H.desc.size(), 0);       /* table offset + 2^40 x boundary nodes */
-    if (hq_stencil().ok && xyz && !hq_opt_flag("HQ_PATCH_NO_STENCIL")) {
-        const bool full_only = !(hq_patch_ragged_env() >= 0 ? hq_patch_ragged_env() != 0 : P->ragged_default);
+    if (hq_stencil().ok && xyz && !hq_set(o.patch_no_stencil)) {
+        const bool full_only = !(hq_given(o.patch_ragged) ? o.patch_ragged != 0 : P->ragged_default);
         std::vector<std::vector<uint32_t>> tabs(H.desc.size());
         std::vector<int32_t> nbnds(H.desc.size(), 0);
 #pragma omp parallel for schedule(dynamic, 64)
@@ -2342,7 +2326,7 @@ static int hq_patch_build(hq_patch_plan* P, int64_t E, int64_t N, const int32_t*
     {
         int nst = 0;
         for (auto& D : H.desc) nst += (D.flags & HQ_PATCH_STENCIL) != 0;
-        if (hq_opt_flag("HQ_PATCH_VERBOSE"))
+        if (hq_set(o.verbose))
         fprintf(stderr, "hq patch plan: %zu patches (%d lattice, %d stencil), %d distinct local connectivities, %d with uniform coefficients, %d with one n_t row\n",
                 H.desc.size(), P->nlattice, nst, H.ndistinct, nuniform, nntsame);
     }
@@ -2462,7 +2446,7 @@ static int hq_patch_set_source(hq_patch_plan* P, int32_t nloaded, const int32_t*
 }
 
 /* slot[n] >= 0 for nodes on the partition interface */
-static int hq_patch_set_interface(hq_patch_plan* P, const int32_t* slot, int64_t nnodes, int64_t* bytes)
+static int hq_patch_set_interface(const hq_options& o, hq_patch_plan* P, const int32_t* slot, int64_t nnodes, int64_t* bytes)
 {
     std::vector<int32_t> ptr((size_t)P->npatches + 1, 0), ent;
     for (int32_t p = 0; p < P->npatches; p++) {
@@ -2478,7 +2462,7 @@ static int hq_patch_set_interface(hq_patch_plan* P, const int32_t* slot, int64_t
     bool any_st_if = false;
     for (int32_t p = 0; p < P->npatches; p++)
         if (ptr[p + 1] > ptr[p] && (P->h_flags[p] & HQ_PATCH_STENCIL)) {
-            if (hq_patch_ragged_env() == 2) { P->h_flags[p] &= ~(HQ_PATCH_STENCIL | HQ_PATCH_RAGGED); continue; }
+            if (o.patch_ragged == 2) { P->h_flags[p] &= ~(HQ_PATCH_STENCIL | HQ_PATCH_RAGGED); continue; }
             P->h_flags[p] |= HQ_PATCH_RAGGED;                /* hands partial forces on: launched ahead of the exchange */
             any_st_if = true;
         }
@@ -2501,13 +2485,13 @@ static int hq_patch_set_interface(hq_patch_plan* P, const int32_t* slot, int64_t
 static unsigned long long* g_hq_stamp_buf = nullptr;
 static unsigned long long* g_hq_wg_buf = nullptr;
 static int32_t g_hq_stamp_n = 0;
-static void hq_patch_report_stamps(void)
+static void hq_patch_report_stamps(const hq_patch_plan* P)
 {
     if (!g_hq_stamp_buf) return;
     std::vector<unsigned long long> h((size_t)g_hq_stamp_n * 8);
     hipDeviceSynchronize();
     hipMemcpy(h.data(), g_hq_stamp_buf, 64 * (size_t)g_hq_stamp_n, hipMemcpyDeviceToHost);
-    static const int pipe_ = hq_patch_kernel_choice() == 0 ? 0 : (hq_patch_kernel_choice() == 6 ? 6 : 4);
+    const int pipe_ = P->pipe == 0 ? 0 : (P->pipe == 6 ? 6 : 4);
     const char* name0[6] = { "descriptor", "issue+wait staging, LDS write", "barrier 1", "element loop", "src/ds + barrier 2", "update + stores issued" };
     const char* name4[6] = { "row wait + node loads issued", "element section", "row/n_t loads, src/ds, barrier", "wait node data, LDS write", "update + stores issued", "barrier" };
     const char* name6[6] = { "node requests issued, descriptor", "gather + arithmetic", "row/n_t requests, atomics, image + seeds", "barrier", "update + stores issued", "-" };
@@ -2565,16 +2549,16 @@ static void hq_patch_launch(const hq_patch_plan* P, int32_t first, int32_t count
 {
     if (count <= 0) return;
 #ifdef HQ_EXPERIMENT            /* profiles/tools only: what a step costs WITHOUT its shell (results are wrong) */
-    { static const bool skip = getenv("HQ_X_NO_SHELL") != nullptr; if (skip) return; }
+    if (getenv("HQ_X_NO_SHELL")) return;
 #endif
     int per_xcd = (count + 7) / 8;
     /* the LDS image as large as the plan's patches need it (a thin shell stages far fewer than cfg.nlmax nodes) */
     const int32_t step_nl = P->step_nl > 0 ? P->step_nl : P->cfg.nlmax;
     const int32_t step_na = P->step_nl > 0 && P->max_nacc > 0 ? P->max_nacc : P->cfg.pmax + P->cfg.vmax;
     size_t lds = (6 * (size_t)step_nl + 3 * (size_t)step_na) * sizeof(double);
-    static const bool nt_hint = hq_opt_on("HQ_PATCH_NT");
-#ifdef HQ_PATCH_PROFILING
-    if (getenv("HQ_PATCH_DIAG") && atoi(getenv("HQ_PATCH_DIAG")) == 6) {
+#ifdef HQ_PATCH_PROFILING   /* ablation builds for profiles/ (HQ_PATCH_DIAG=1..5: results are WRONG by construction) */
+    const int diag = getenv("HQ_PATCH_DIAG") ? atoi(getenv("HQ_PATCH_DIAG")) : 0;
+    if (diag == 6) {
         static unsigned long long* d_st = nullptr;
         if (!d_st) {
             hipMalloc((void**)&d_st, 64 * (size_t)P->npatches);
@@ -2615,15 +2599,14 @@ static void hq_patch_launch(const hq_patch_plan* P, int32_t first, int32_t count
             return;
         }
     }
-    auto kern = nt_hint ? hq_k_patch_step<true, 0> : hq_k_patch_step<false, 0>;
-#ifdef HQ_PATCH_PROFILING   /* ablation builds for profiles/: results are WRONG by construction */
-    static const int diag = hq_opt_int("HQ_PATCH_DIAG", 0);
-    if (diag == 1) kern = hq_k_patch_step<false, 1>;
-    if (diag == 2) kern = hq_k_patch_step<false, 2>;
-    if (diag == 3) kern = hq_k_patch_step<false, 3>;
-    if (diag == 4) kern = hq_k_patch_step<false, 4>;
-    if (diag == 5) kern = hq_k_patch_step<false, 5>;
-    if (diag == 6) kern = hq_k_patch_step<false, 6>;
+    auto kern = hq_k_patch_step<0>;
+#ifdef HQ_PATCH_PROFILING
+    if (diag == 1) kern = hq_k_patch_step<1>;
+    if (diag == 2) kern = hq_k_patch_step<2>;
+    if (diag == 3) kern = hq_k_patch_step<3>;
+    if (diag == 4) kern = hq_k_patch_step<4>;
+    if (diag == 5) kern = hq_k_patch_step<5>;
+    if (diag == 6) kern = hq_k_patch_step<6>;
 #endif
     kern<<<per_xcd * 8, P->cfg.threads, lds, stream>>>(
         count, per_xcd, P->d_order ? P->d_order + first : nullptr, step_nl, P->d_desc, P->d_pidx, P->d_pc1,

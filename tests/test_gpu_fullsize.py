@@ -301,7 +301,7 @@ def test_eight_partitions_of_the_8m_box_match_one_partition(wl, overlap, ragged,
     with ThreadPoolExecutor(8) as pool:
         boxes = list(pool.map(lambda r: host.Box(nx, ny, nz, h, dt, freq, rank=r, nranks=8, lateral_classes=ncls, lateral_amp=amp), range(8)))
     lap("8 rank boxes")
-    # ... and so are the eight hq_create calls (thread-safe by design: errors and options in force are thread-local)
+    # ... and so are the eight hq_create calls (thread-safe by design: errors are thread-local, options are passed as arguments)
     def make(b):
         g = (b.node_ijk[:, 2].astype(np.int64) * (ny + 1) + b.node_ijk[:, 1]) * (nx + 1) + b.node_ijk[:, 0]
         m = lut[g]
