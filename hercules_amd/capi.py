@@ -20,7 +20,8 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_download", "hq_upload", "hq_phase_force", "hq_phase_update", "hq_download_force",
            "hq_run_timed", "hq_dominant_kernel", "hq_plan_check", "hq_stencil_plan_check", "hq_check_finite",
            "hq_stencil_coefficients", "hq_brick_plan_check", "hq_brick_plan_check_n", "hq_comm_init_host",
-           "hq_comm_ipc_export", "hq_comm_init_ipc", "hq_comm_init_loopback"]
+           "hq_comm_ipc_export", "hq_comm_init_ipc", "hq_comm_init_loopback",
+           "hq_record_add", "hq_record_pending", "hq_record_fetch", "hq_record_clear"]
 
 
 class HqError(RuntimeError):
@@ -55,6 +56,11 @@ class _Desc(ctypes.Structure):
                 ("variant", ctypes.c_int32), ("reserved", ctypes.c_int32), ("node_gnid", ctypes.c_void_p),
                 ("edata", ctypes.c_void_p), ("mat_bbase", ctypes.c_double), ("mat_threshold_damping", ctypes.c_double),
                 ("mat_threshold_vpvs", ctypes.c_double)]
+
+
+class _RecorderDesc(ctypes.Structure):
+    _fields_ = [("npoints", ctypes.c_int32), ("ids", ctypes.c_void_p), ("phi", ctypes.c_void_p),
+                ("rate", ctypes.c_int32), ("derivs", ctypes.c_int32), ("capacity", ctypes.c_int32)]
 
 
 class _Info(ctypes.Structure):
@@ -346,6 +352,45 @@ class Solver:
         o = [np.empty((len(ids), 3), self.real) for _ in range(3)]
         _check(self._lib.hq_gather3(self._h, ctypes.c_int32(len(ids)), _ptr(ids), _ptr(o[0]), _ptr(o[1]), _ptr(o[2])), self._lib)
         return tuple(o)
+
+    def record_add(self, ids, phi, rate, derivs=0, capacity=1024):
+        """hq_record_add: a device recorder of the points (ids [n,8], phi [n,8]) -- a sample at the head of every step
+        that is a multiple of `rate`, kept in a ring of `capacity` samples on the device.  Returns its handle."""
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
+        phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
+        if len(ids) != len(phi):
+            raise HqError("record_add: %d rows of ids, %d of phi" % (len(ids), len(phi)))
+        d = _RecorderDesc(len(ids), ids.ctypes.data, phi.ctypes.data, int(rate), int(derivs), int(capacity))
+        h = ctypes.c_int32(-1)
+        _check(self._lib.hq_record_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
+        if not hasattr(self, "_recorders"):
+            self._recorders = {}
+        self._recorders[h.value] = (len(ids), 3 * (1 + int(derivs)))
+        return h.value
+
+    def record_pending(self, handle):
+        """hq_record_pending: (samples taken or enqueued and not yet fetched, step of the oldest or -1)."""
+        n, first = ctypes.c_int32(), ctypes.c_int32()
+        _check(self._lib.hq_record_pending(self._h, ctypes.c_int32(handle), ctypes.byref(n), ctypes.byref(first)), self._lib)
+        return n.value, first.value
+
+    def record_fetch(self, handle, max_samples=None):
+        """hq_record_fetch: (steps [k], values [k, npoints, 3 (1 + derivs)] float64) of the oldest pending samples, at
+        most max_samples (None: all of them); waits for the enqueued steps."""
+        pending, _ = self.record_pending(handle)                # (raises on an unknown handle)
+        npoints, ncomp = self._recorders[handle]
+        want = pending if max_samples is None else min(int(max_samples), pending)
+        steps = np.zeros(max(want, 1), np.int32)
+        vals = np.zeros((max(want, 1), npoints, ncomp))
+        got = ctypes.c_int32()
+        _check(self._lib.hq_record_fetch(self._h, ctypes.c_int32(handle), ctypes.c_int32(want), _ptr(vals), _ptr(steps),
+                                         ctypes.byref(got)), self._lib)
+        return steps[:got.value].copy(), vals[:got.value].copy()
+
+    def record_clear(self):
+        """hq_record_clear: drop every recorder of the context and its device memory."""
+        _check(self._lib.hq_record_clear(self._h), self._lib)
+        self._recorders = {}
 
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)

@@ -256,6 +256,21 @@ struct hq_ctx {
     size_t clock_at = 0;
     double clk_us[5] = { 0, 0, 0, 0, 0 };   /* step, shell, interior, chain, chain behind the interior's end */
     int64_t clk_steps = 0;
+    /* sample recorders (hq_record_add): rings in device memory, accounted on the host -- which steps are due follows
+     * from `step` alone.  ev_recorded exists from the first hq_record_add on: behind a due step's hq_k_record launches,
+     * waited for by the streams whose kernels of that step overwrite the buffer the launches read as u(t - 2 dt) */
+    struct hq_recorder {
+        int32_t id = 0, np = 0, rate = 1, derivs = 0, capacity = 0;
+        int32_t* d_ids = nullptr;     /* [8][np] device numbering */
+        double* d_phi = nullptr;      /* [8][np] */
+        double* d_ring = nullptr;     /* [capacity][np][3 (1 + derivs)] */
+        int32_t head = 0, count = 0;  /* oldest pending slot, pending samples (taken or enqueued) */
+        std::vector<int32_t> steps;   /* [capacity] step number of the sample in each slot */
+        int64_t bytes = 0;            /* device memory of this recorder (part of `bytes`) */
+    };
+    std::vector<hq_recorder> recs;
+    int32_t rec_next_id = 0;
+    hipEvent_t ev_recorded = nullptr;
     /* timing */
     std::vector<hipEvent_t> ev;     /* per-launch marks */
     hipEvent_t ev_span[2] = { nullptr, nullptr };
@@ -612,6 +627,55 @@ __global__ void hq_k_gather(int32_t n, const int32_t* __restrict__ ids,
     int i = t / 3, d = t - 3 * i;
     oa[t] = a[3 * (int64_t)ids[i] + d];
     ob[t] = b[3 * (int64_t)ids[i] + d];
+}
+
+/*
+ * One sample of a recorder (hq_record_add): interpolate_station_displacements (psolve.c:6705-6787) / Old_planes_print
+ * (io_planes.c:176-200) on the device-resident state.  One lane per point, consecutive lanes on consecutive points; ids
+ * and phi are stored transposed ([8][np]) so that a wave reads them in whole lines.  Eight gathers of one 3-vector from
+ * each of u1 = u(t), u2 = u(t - dt), u3 = u(t - 2 dt) as far as `derivs` needs them, every value widened to double first
+ * (hq_real is float in the f32 library), summed in hqh_station_kinematics' exact order of operations (hq_host.c): the
+ * displacement accumulator over the 8 nodes; then phi * u2 taken off node by node, over dt; then phi * u2 off once more
+ * and phi * u3 added, node by node, over dt^2.  Contraction is OFF: the host library is compiled without FMA, and the
+ * samples must equal the host route's bit for bit (tests/test_gpu_recorders.py).
+ * A memory-bound gather of up to 3 x 8 x 24 bytes per point; a plane's points are the bulk of it.
+ */
+__global__ void __launch_bounds__(256)
+hq_k_record(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
+            const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
+            double dt, double dt2, int32_t derivs, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= np) return;
+    int64_t row[8];
+    double w[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
+        w[c] = phi[(int64_t)c * np + p];
+    }
+    double* o = out + (int64_t)p * (3 * (1 + derivs));
+    double d[3] = { 0.0, 0.0, 0.0 };
+#pragma unroll
+    for (int c = 0; c < 8; c++)
+        for (int a = 0; a < 3; a++) d[a] = d[a] + w[c] * (double)u1[row[c] + a];
+    for (int a = 0; a < 3; a++) o[a] = d[a];
+    if (derivs >= 1) {
+#pragma unroll
+        for (int c = 0; c < 8; c++)
+            for (int a = 0; a < 3; a++) d[a] = d[a] - w[c] * (double)u2[row[c] + a];
+        for (int a = 0; a < 3; a++) o[3 + a] = d[a] / dt;
+    }
+    if (derivs == 2) {
+#pragma unroll
+        for (int c = 0; c < 8; c++)
+            for (int a = 0; a < 3; a++) {
+                d[a] = d[a] - w[c] * (double)u2[row[c] + a];
+                d[a] = d[a] + w[c] * (double)u3[row[c] + a];
+            }
+        for (int a = 0; a < 3; a++) o[6 + a] = d[a] / dt2;
+    }
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1145,6 +1209,61 @@ static bool hq_use_brick_stream(hq_ctx* c)
     return true;
 }
 
+/* ---- sample recorders ---- */
+
+/* would the due steps of [c->step, c->step + nsteps) overflow a ring?  Decided before anything is enqueued */
+static int hq_record_check_room(const hq_ctx* c, int32_t nsteps)
+{
+    for (const auto& r : c->recs) {
+        int64_t due = 0;
+        for (int32_t s = 0; s < nsteps; s++) due += ((int64_t)c->step + s) % r.rate == 0;
+        if (r.count + due > r.capacity)
+            return hq_fail(HQ_ERR_STATE, "a recorder's ring would overflow: fetch its samples first (hq_record_fetch)%s", "");
+    }
+    return HQ_OK;
+}
+
+/* free every recorder (the caller has waited for the streams) */
+static void hq_record_drop_all(hq_ctx* c)
+{
+    for (auto& r : c->recs) {
+        if (r.d_ids) hipFree(r.d_ids);
+        if (r.d_phi) hipFree(r.d_phi);
+        if (r.d_ring) hipFree(r.d_ring);
+        c->bytes -= r.bytes;
+    }
+    c->recs.clear();
+    if (c->ev_recorded) { hipEventDestroy(c->ev_recorded); c->ev_recorded = nullptr; }
+}
+
+/* head of a step: one hq_k_record launch per due recorder on the compute stream, behind the waits phase 0 has already
+ * made for the last step's shared displacements and bricks.  On a due step only, the streams whose kernels of THIS
+ * step write into d_u[spare] -- which the launch reads as u(t - 2 dt) -- are held back behind it: the bricks' own stream,
+ * and the exchange chain's (hq_k_interface_update, the unpack).  The patches follow on the compute stream itself. */
+static int hq_record_enqueue(hq_ctx* c, bool brick_stream)
+{
+    bool any = false;
+    for (auto& r : c->recs) {
+        if (c->step % r.rate != 0) continue;
+        if (r.count >= r.capacity) return hq_fail(HQ_ERR_STATE, "a recorder's ring is full%s", "");   /* (hq_record_check_room saw to it) */
+        const int32_t slot = (r.head + r.count) % r.capacity;
+        r.steps[(size_t)slot] = c->step;
+        r.count++;
+        if (r.np <= 0) continue;
+        const int32_t ncomp = 3 * (1 + r.derivs);
+        hq_k_record<<<hq_blocks(r.np, 256), 256, 0, c->stream>>>(
+            r.np, r.d_ids, r.d_phi, c->d_u[c->now], c->d_u[c->prev], r.derivs == 2 ? c->d_u[c->spare] : c->d_u[c->prev],
+            c->dt, c->dt2, r.derivs, r.d_ring + (int64_t)slot * r.np * ncomp);
+        any = true;
+    }
+    if (any && c->variant == HQ_VARIANT_PATCH && ((brick_stream && c->bstream) || (c->overlap && c->cstream))) {
+        HQ_HIP(hipEventRecord(c->ev_recorded, c->stream));
+        if (brick_stream && c->bstream) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_recorded, 0));
+        if (c->overlap && c->cstream) HQ_HIP(hipStreamWaitEvent(c->cstream, c->ev_recorded, 0));
+    }
+    return HQ_OK;
+}
+
 static int hq_phase(hq_ctx* c, int ph)
 {
     const bool patch = (c->variant == HQ_VARIANT_PATCH);
@@ -1173,6 +1292,7 @@ static int hq_phase(hq_ctx* c, int ph)
                 if (c->ev_shared) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_shared, 0));
                 HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_patches, 0));
             }
+            if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, bs));        /* solver_output_planes / _stations, :4279-4280 */
             auto launch_bricks = [&]() {
                 if (c->bricks.nunits > 0)
                     hq_brick_launch(&c->bricks, c->d_u[c->now], c->d_u[c->prev], c->d_u[c->spare], c->plan.d_nt3, F, c->dt2,
@@ -1235,6 +1355,7 @@ static int hq_phase(hq_ctx* c, int ph)
              *  kernel time from the phase clock's events instead, and a timed batch enqueues exactly what hq_run does) */
             hq_mark(c);
         } else {
+            if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, false));
             HQ_TRY(hq_launch_source(c));                                   /* :4288 */
             HQ_TRY(hq_launch_element_scatter(c));                          /* :4290-4291 */
         }
@@ -2480,6 +2601,7 @@ extern "C" int hq_destroy(hq_ctx* c)
                      c->d_gkey, c->d_halo_err, c->an.d_c_out_id, c->an.d_c_in_id, c->an.d_s_out_id, c->an.d_s_in_id,
                      c->dn.d_c_out_id, c->dn.d_c_in_id, c->dn.d_s_out_id, c->dn.d_s_in_id };
     for (void* p : ptrs) if (p) hipFree(p);
+    hq_record_drop_all(c);
     if (c->an.d_cmap_f && c->an.d_cmap_f != c->an.d_cmap) hipFree(c->an.d_cmap_f);
     if (c->an.d_smap_f && c->an.d_smap_f != c->an.d_smap) hipFree(c->an.d_smap_f);
     if (c->dn.d_cmap_f && c->dn.d_cmap_f != c->dn.d_cmap) hipFree(c->dn.d_cmap_f);
@@ -3019,6 +3141,7 @@ extern "C" int hq_group_run(hq_ctx** ctxs, int32_t n, int32_t nsteps)
      * buffers, so a group steps complete or not at all */
     for (hq_ctx* m : *ctxs[0]->group)
         if (!m) return hq_fail(HQ_ERR_STATE, "a member of the group has been destroyed: the others cannot step any more%s", "");
+    for (int32_t i = 0; i < n; i++) HQ_TRY(hq_record_check_room(ctxs[i], nsteps));
     for (int32_t s = 0; s < nsteps; s++)
         for (int ph = 0; ph < HQ_NPHASE; ph++)
             for (int32_t i = 0; i < n; i++) {
@@ -3083,6 +3206,7 @@ extern "C" int hq_run(hq_ctx* c, int32_t nsteps)
     if (!c || nsteps < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
     if (c->group && c->group->size() > 1)
         return hq_fail(HQ_ERR_STATE, "linked contexts are stepped with hq_group_run%s", "");
+    HQ_TRY(hq_record_check_room(c, nsteps));
     HQ_HIP(hipSetDevice(c->device));
     for (int32_t s = 0; s < nsteps; s++) HQ_TRY(hq_step(c));
     HQ_HIP(hipGetLastError());
@@ -3145,6 +3269,7 @@ extern "C" int hq_check_finite(hq_ctx* c, int64_t* nonfinite)
 extern "C" int hq_run_timed(hq_ctx* c, int32_t nsteps, double* total_ms, double* kernel_ms_avg)
 {
     if (!c || nsteps <= 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
+    HQ_TRY(hq_record_check_room(c, nsteps));
     HQ_HIP(hipSetDevice(c->device));
     size_t need = 2 * (size_t)nsteps;
     while (c->ev.size() < need) {
@@ -3257,6 +3382,112 @@ static int hq_gather_impl(hq_ctx* c, int32_t n, const int32_t* lnid, hq_real* o1
     }
     e = hq_quiesce(c);
     if (e != hipSuccess) return hq_fail(HQ_ERR_DEVICE, "gather failed: %s", hipGetErrorString(e));
+    return HQ_OK;
+}
+
+/* ---- sample recorders: entry points (include/hq_solver.h) ---- */
+
+static hq_ctx::hq_recorder* hq_record_find(hq_ctx* c, int32_t handle)
+{
+    for (auto& r : c->recs)
+        if (r.id == handle) return &r;
+    return nullptr;
+}
+
+extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (d->npoints < 0 || d->rate <= 0 || d->capacity <= 0 || d->derivs < 0 || d->derivs > 2 ||
+        (d->npoints > 0 && (!d->ids || !d->phi)))
+        return hq_fail(HQ_ERR_ARG, "bad recorder description%s", "");
+    if (d->derivs == 2 && c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    const int32_t np = d->npoints;
+    for (int64_t i = 0; i < 8 * (int64_t)np; i++)
+        if (d->ids[i] < 0 || d->ids[i] >= c->N) return hq_fail(HQ_ERR_ARG, "node id out of range%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    /* the tables: device numbering, transposed to [8][np] */
+    std::vector<int32_t> ids((size_t)np * 8);
+    std::vector<double> phi((size_t)np * 8);
+    for (int32_t p = 0; p < np; p++)
+        for (int k = 0; k < 8; k++) {
+            const int32_t id = d->ids[8 * (size_t)p + k];
+            ids[(size_t)k * np + p] = c->perm.empty() ? id : c->perm[(size_t)id];
+            phi[(size_t)k * np + p] = d->phi[8 * (size_t)p + k];
+        }
+    hq_ctx::hq_recorder r;
+    r.np = np; r.rate = d->rate; r.derivs = d->derivs; r.capacity = d->capacity;
+    const size_t ring = (size_t)d->capacity * (size_t)np * 3 * (size_t)(1 + d->derivs);
+    const int64_t bytes0 = c->bytes;
+    int rc = hq_dev_alloc(c, &r.d_ids, ids.size());
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &r.d_phi, phi.size());
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &r.d_ring, ring);
+    hipError_t e = hipSuccess;
+    if (rc == HQ_OK && !c->ev_recorded) e = hipEventCreateWithFlags(&c->ev_recorded, hipEventDisableTiming);
+    if (rc == HQ_OK && e == hipSuccess && np > 0) {
+        e = hipMemcpy(r.d_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(r.d_phi, phi.data(), sizeof(double) * phi.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   /* the steps read the tables on other streams */
+    }
+    if (rc != HQ_OK || e != hipSuccess) {
+        if (r.d_ids) hipFree(r.d_ids);
+        if (r.d_phi) hipFree(r.d_phi);
+        if (r.d_ring) hipFree(r.d_ring);
+        c->bytes = bytes0;
+        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_record_add failed: %s", hipGetErrorString(e));
+    }
+    r.bytes = c->bytes - bytes0;
+    c->h2d_bytes += 12 * (int64_t)ids.size();
+    r.steps.assign((size_t)d->capacity, 0);
+    r.id = c->rec_next_id++;
+    *handle = r.id;
+    c->recs.push_back(std::move(r));
+    return HQ_OK;
+}
+
+extern "C" int hq_record_pending(hq_ctx* c, int32_t handle, int32_t* nsamples, int32_t* first_step)
+{
+    if (!c || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const hq_ctx::hq_recorder* r = hq_record_find(c, handle);
+    if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
+    *nsamples = r->count;
+    if (first_step) *first_step = r->count > 0 ? r->steps[(size_t)r->head] : -1;
+    return HQ_OK;
+}
+
+extern "C" int hq_record_fetch(hq_ctx* c, int32_t handle, int32_t max_samples, double* out, int32_t* steps,
+                               int32_t* nfetched)
+{
+    if (!c || !out || !steps || !nfetched || max_samples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
+    hq_ctx::hq_recorder* r = hq_record_find(c, handle);
+    if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
+    *nfetched = 0;
+    const int32_t n = std::min(max_samples, r->count);
+    if (n == 0) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t row = (size_t)r->np * 3 * (size_t)(1 + r->derivs);          /* doubles per sample */
+    const int32_t first = std::min(n, r->capacity - r->head);                /* up to the ring's end, then from its start */
+    if (row > 0) {
+        HQ_HIP(hipMemcpy(out, r->d_ring + (size_t)r->head * row, sizeof(double) * row * (size_t)first, hipMemcpyDeviceToHost));
+        if (n > first)
+            HQ_HIP(hipMemcpy(out + (size_t)first * row, r->d_ring, sizeof(double) * row * (size_t)(n - first), hipMemcpyDeviceToHost));
+    }
+    for (int32_t k = 0; k < n; k++) steps[k] = r->steps[(size_t)((r->head + k) % r->capacity)];
+    c->d2h_bytes += 8 * (int64_t)row * n;
+    r->head = (r->head + n) % r->capacity;
+    r->count -= n;
+    *nfetched = n;
+    return HQ_OK;
+}
+
+extern "C" int hq_record_clear(hq_ctx* c)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (c->recs.empty()) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    hq_record_drop_all(c);
     return HQ_OK;
 }
 

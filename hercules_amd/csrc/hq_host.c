@@ -1409,6 +1409,45 @@ void hqh_source_table(const hqh_run_params* rp, double dt, int32_t step0, int32_
     }
 }
 
+/* hqh_run_params.device_recorders: one device recorder of the run (hq_record_add) and the host buffers one batch's
+ * samples are fetched into.  The ring holds every due step of [step0, end) where that stays within 64 MB, fewer
+ * otherwise (the batches are then cut where it would fill); no recorder at all (handle -1) if no step is due. */
+#define HQH_RING_BYTES ((int64_t)64 << 20)
+typedef struct {
+    int32_t  handle, cap, rate, ncomp, npoints;
+    double*  vals;                                               /* [cap][npoints][ncomp] */
+    int32_t* steps;                                              /* [cap] */
+} hqh_recorder;
+
+static int hqh_recorder_open(hq_ctx* ctx, hqh_recorder* r, int32_t npoints, const int32_t* ids, const double* phi,
+                             int32_t rate, int32_t derivs, int32_t step0, int32_t end)
+{
+    r->handle = -1; r->cap = 0; r->rate = rate; r->ncomp = 3 * (1 + derivs); r->npoints = npoints;
+    r->vals = NULL; r->steps = NULL;
+    const int64_t first = ((int64_t)step0 + rate - 1) / rate * rate;            /* first due step >= step0 */
+    if (first >= end) return HQ_OK;
+    int64_t cap = ((int64_t)end - 1 - first) / rate + 1;                        /* due steps of the run */
+    const int64_t row = 8 * (int64_t)npoints * r->ncomp;                        /* bytes per sample */
+    if (row > 0 && cap * row > HQH_RING_BYTES) cap = HQH_RING_BYTES / row > 0 ? HQH_RING_BYTES / row : 1;
+    r->cap = (int32_t)cap;
+    r->vals = (double*)malloc((size_t)(cap * row > 0 ? cap * row : 8));
+    r->steps = (int32_t*)malloc(sizeof(int32_t) * (size_t)cap);
+    if (!r->vals || !r->steps) return HQ_ERR_NOMEM;
+    hq_recorder_desc d;
+    memset(&d, 0, sizeof d);
+    d.npoints = npoints; d.ids = ids; d.phi = phi; d.rate = rate; d.derivs = derivs; d.capacity = r->cap;
+    return hq_record_add(ctx, &d, &r->handle);
+}
+
+/* the step a batch that starts at `step` with this recorder's ring empty must end at, at the latest */
+static int32_t hqh_recorder_limit(const hqh_recorder* r, int32_t step, int32_t next)
+{
+    if (r->handle < 0) return next;
+    const int64_t first = ((int64_t)step + r->rate - 1) / r->rate * r->rate;
+    const int64_t full = first + (int64_t)r->cap * r->rate;                     /* the (cap + 1)-th due step */
+    return full < next ? (int32_t)full : next;
+}
+
 /*
  * solver_run, psolve.c:4241-4324.  Per step the reference does: swap, outputs
  * (stations read tm1), read source forces, physics + communication.  Here the
@@ -1472,6 +1511,37 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
         if (!w1 || !w2) rc = HQ_ERR_NOMEM;
     }
     int32_t step = step0, end = step0 + nsteps, win_end = step0;
+    /* stations and planes sampled on the device (hqh_run_params.device_recorders): no batch is cut at a print step */
+    const int dev_rec = rp->device_recorders != 0 && (u || pfp);
+    hqh_recorder rst, rpl;
+    memset(&rst, 0, sizeof rst); memset(&rpl, 0, sizeof rpl);
+    rst.handle = rpl.handle = -1;
+    int32_t* pl_ids = NULL;                                      /* the planes' points that are plane_mine, compacted */
+    double* pl_phi = NULL;
+    int64_t* pl_point = NULL;                                    /* ... and where each belongs in pbuf */
+    if (dev_rec && rc == HQ_OK) {
+        hq_info inf;
+        if (step0 < 0 || hq_get_info(ctx, &inf) != HQ_OK) rc = HQ_ERR_ARG;
+        else if (inf.step != step0) rc = HQ_ERR_STATE;           /* the due steps follow the context's own counter */
+        if (rc == HQ_OK && u)
+            rc = hqh_recorder_open(ctx, &rst, rp->nstations, rp->station_ids, rp->station_phi, rp->station_rate,
+                                   rp->station_derivs, step0, end);
+        if (rc == HQ_OK && pfp) {
+            int64_t nm = 0;
+            pl_ids = (int32_t*)malloc(sizeof(int32_t) * 8 * (size_t)(npp ? npp : 1));
+            pl_phi = (double*)malloc(sizeof(double) * 8 * (size_t)(npp ? npp : 1));
+            pl_point = (int64_t*)malloc(sizeof(int64_t) * (size_t)(npp ? npp : 1));
+            if (!pl_ids || !pl_phi || !pl_point) rc = HQ_ERR_NOMEM;
+            for (int64_t q = 0; q < npp && rc == HQ_OK; q++) {
+                if (rp->plane_mine && !rp->plane_mine[q]) continue;
+                memcpy(pl_ids + 8 * nm, rp->plane_ids + 8 * q, sizeof(int32_t) * 8);
+                memcpy(pl_phi + 8 * nm, rp->plane_phi + 8 * q, sizeof(double) * 8);
+                pl_point[nm++] = q;
+            }
+            if (rc == HQ_OK)
+                rc = hqh_recorder_open(ctx, &rpl, (int32_t)nm, pl_ids, pl_phi, rp->plane_rate, 0, step0, end);
+        }
+    }
     int ckpt_number = 0;                                         /* CheckpointNumber, io_checkpoint.c:38,126 */
     const int do_ckpt = rp->checkpoint_rate > 0 && rp->checkpoint_dir != NULL;
     while (step < end && rc == HQ_OK) {
@@ -1496,7 +1566,7 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
                                          cnt, w1, w2, deltaT);
             if (rc != HQ_OK) break;
         }
-        if (pfp && step % rp->plane_rate == 0) {                 /* solver_output_planes, :4279 */
+        if (pfp && !dev_rec && step % rp->plane_rate == 0) {     /* solver_output_planes, :4279 */
             rc = hq_gather(ctx, (int32_t)(npp * 8), rp->plane_ids, pu, NULL);
             if (rc != HQ_OK) break;
             int64_t off = 0;
@@ -1515,7 +1585,7 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
             }
             if (rc != HQ_OK) break;
         }
-        if (u && step % rp->station_rate == 0) {                 /* solver_output_stations, :4280 */
+        if (u && !dev_rec && step % rp->station_rate == 0) {     /* solver_output_stations, :4280 */
             const int dv = rp->station_derivs;
             const size_t blk = 24 * (size_t)rp->nstations;
             rc = dv == 2 ? hq_gather3(ctx, rp->nstations * 8, rp->station_ids, u, u + blk, u + 2 * blk)
@@ -1540,11 +1610,11 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
         }
         int32_t next = end;
         if (F && win_end < next) next = win_end;
-        if (u) {
+        if (u && !dev_rec) {
             int32_t ns = (step / rp->station_rate + 1) * rp->station_rate;
             if (ns < next) next = ns;
         }
-        if (pfp) {
+        if (pfp && !dev_rec) {
             int32_t ns = (step / rp->plane_rate + 1) * rp->plane_rate;
             if (ns < next) next = ns;
         }
@@ -1556,12 +1626,45 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
             int32_t ns = (step / rp->wavefield_rate + 1) * rp->wavefield_rate;
             if (ns < next) next = ns;
         }
+        if (dev_rec) {                                           /* ... and where a ring would fill */
+            next = hqh_recorder_limit(&rst, step, next);
+            next = hqh_recorder_limit(&rpl, step, next);
+        }
         rc = hq_run(ctx, next - step);
         step = next;
+        if (dev_rec && rc == HQ_OK) {
+            /* the batch's samples, in step order; at a step both print at, the planes first (:4279-4280) */
+            int32_t nst = 0, npl = 0, i = 0, j = 0;
+            if (rst.handle >= 0) rc = hq_record_fetch(ctx, rst.handle, rst.cap, rst.vals, rst.steps, &nst);
+            if (rc == HQ_OK && rpl.handle >= 0) rc = hq_record_fetch(ctx, rpl.handle, rpl.cap, rpl.vals, rpl.steps, &npl);
+            while (rc == HQ_OK && (i < nst || j < npl)) {
+                if (j < npl && (i >= nst || rpl.steps[j] <= rst.steps[i])) {
+                    const double* v = rpl.vals + 3 * (size_t)rpl.npoints * (size_t)j;
+                    for (int32_t k = 0; k < rpl.npoints; k++)
+                        memcpy(pbuf + 3 * pl_point[k], v + 3 * (size_t)k, 3 * sizeof(double));
+                    int64_t off = 0;
+                    for (int32_t p = 0; p < rp->nplanes && rc == HQ_OK; p++) {
+                        size_t n = 3 * (size_t)rp->plane_npoints[p];
+                        if (fwrite(pbuf + 3 * off, sizeof(double), n, pfp[p]) != n) rc = HQ_ERR_ARG;
+                        off += rp->plane_npoints[p];
+                    }
+                    j++;
+                } else {
+                    rp->station_fn(rp->station_user, rst.steps[i], rp->nstations,
+                                   rst.vals + (size_t)rst.ncomp * (size_t)rst.npoints * (size_t)i);
+                    i++;
+                }
+            }
+        }
     }
     if (rc == HQ_OK) rc = hq_sync(ctx);
+    if (dev_rec) {
+        int rc2 = hq_record_clear(ctx);
+        if (rc == HQ_OK) rc = rc2;
+    }
     if (pfp) for (int32_t i = 0; i < rp->nplanes; i++) if (pfp[i]) fclose(pfp[i]);
     free(F); free(u); free(disp); free(pu); free(pbuf); free(pfp); free(w1); free(w2);
+    free(rst.vals); free(rst.steps); free(rpl.vals); free(rpl.steps); free(pl_ids); free(pl_phi); free(pl_point);
     return rc;
 }
 

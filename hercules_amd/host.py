@@ -59,7 +59,7 @@ class _RunParams(ctypes.Structure):
                 ("wavefield_rate", ctypes.c_int32), ("wavefield_disp_file", ctypes.c_char_p),
                 ("wavefield_vel_file", ctypes.c_char_p), ("wavefield_total_nodes", ctypes.c_int64),
                 ("wavefield_base_gnid", ctypes.c_int64), ("wavefield_first_owned", ctypes.c_int32),
-                ("wavefield_count", ctypes.c_int32)]
+                ("wavefield_count", ctypes.c_int32), ("device_recorders", ctypes.c_int32)]
 
 
 class _WavefieldInfo(ctypes.Structure):
@@ -137,15 +137,18 @@ def run_params(loaded=None, pattern=None, moment=1.0, rise_time=0.1, source_wind
                station_ids=None, station_phi=None, station_rate=0, station_fn=None, force_file=None,
                planes=None, plane_rate=0, plane_dir=None, checkpoint_rate=0, checkpoint_dir=None,
                station_derivs=0, wavefield_rate=0, wavefield_disp_file=None, wavefield_vel_file=None,
-               wavefield_total_nodes=0, wavefield_owned=None):
+               wavefield_total_nodes=0, wavefield_owned=None, device_recorders=0):
     """wavefield_*: every wavefield_rate steps the owned nodes' displacement / velocity go to their
     place in the 4D file(s) made by wavefield_create; wavefield_owned = (base_gnid, first_owned,
     count) for a partition (None: the whole mesh).
     station_derivs: 0 = the station callback gets displacements [n, 3]; 1 = + velocities [n, 6];
     2 = + accelerations [n, 9] (print_station_velocities / _accelerations).
     planes: list of (ids [n,8], phi [n,8]) or (ids, phi, mine [n]) per output plane, written
-    every plane_rate steps to <plane_dir>/planedisplacements.<i> (the reference's format)."""
+    every plane_rate steps to <plane_dir>/planedisplacements.<i> (the reference's format).
+    device_recorders = 1: stations and planes are sampled on the device (hq_record_add) and fetched batch by batch
+    instead of gathered at every print step; callbacks and files are the same, bit for bit (hq_host.h)."""
     rp = _RunParams()
+    rp.device_recorders = int(device_recorders)
     keep = []
     if checkpoint_rate > 0 and checkpoint_dir is not None:
         rp.checkpoint_rate, rp.checkpoint_dir = int(checkpoint_rate), os.fsencode(checkpoint_dir)

@@ -174,6 +174,15 @@ typedef struct {
     int64_t        wavefield_base_gnid;   /* global id of the first owned node */
     int32_t        wavefield_first_owned; /* its local id */
     int32_t        wavefield_count;       /* owned nodes (contiguous in local and global order) */
+    /* 0: stations and planes are read with one hq_gather[3] per print step, on the host (the batch of steps is cut at
+     * every print step).  1: they are sampled ON THE DEVICE (hq_record_add, hq_solver.h): the stations become one
+     * recorder with station_rate and station_derivs, the points of all planes that are plane_mine another with
+     * plane_rate; batches are cut only at source windows, checkpoints, 4D output steps and where a ring (at most
+     * 64 MB per recorder) would fill; after each batch the samples are fetched, station_fn is called once per sample
+     * in step order and every plane's block is appended to its file.  Callback sequence, values and files are those
+     * of 0, bit for bit.  step0 must be the context's own step counter (the due steps follow it), and the runner
+     * drops EVERY recorder of the context (hq_record_clear) before it returns. */
+    int32_t        device_recorders;
 } hqh_run_params;
 
 /* The reference's 4D output file (out_hdr_t psolve.h:120-186, 136 bytes; then output_steps blocks

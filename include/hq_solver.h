@@ -417,6 +417,43 @@ HQ_API int hq_download(hq_ctx* ctx, hq_real* tm1, hq_real* tm2);
 HQ_API int hq_upload(hq_ctx* ctx, const hq_real* tm1, const hq_real* tm2, int32_t step);
 
 /*
+ * Sample recorders (additive under ABI 6): what solver_output_stations / solver_output_planes read at the top of the
+ * loop body (psolve.c:4279-4280, :6679-6787; io_planes.c:176-200), taken ON THE DEVICE, so that a host which prints
+ * stations every step no longer stops the queue with an hq_gather per print step.  A recorder is a list of points,
+ * each the trilinear sum over the 8 nodes of its element; at the head of every step s with s % rate == 0 -- before any
+ * of that step's kernels, on exactly the state hq_gather3 documents -- one launch of hq_k_record appends one sample to
+ * a ring in device memory:  out[sample][point][3 (1 + derivs)], always double, in both libraries (the f32 library
+ * widens each state value first): displacement; with derivs >= 1 the velocity (u1 - u2) / dt; with derivs == 2 the
+ * acceleration (u1 - 2 u2 + u3) / dt^2 -- summed in hqh_station_kinematics' order of operations without contraction, so
+ * the numbers equal the host route's bit for bit.  Step 0 records the initial state; the state after the last step is
+ * not sampled until a further step begins.
+ * The ring is accounted on the host: which steps are due follows from the step counter alone.  hq_run, hq_group_run
+ * and hq_run_timed count the due steps of the call against the free slots of every recorder BEFORE they enqueue
+ * anything and return HQ_ERR_STATE, with nothing enqueued and the step counter unchanged, if a ring would overflow.
+ * hq_record_fetch waits for the enqueued work (as hq_gather does), delivers the oldest samples first -- at most
+ * max_samples; steps[k] is the step number of out's sample k -- and leaves the rest pending.  hq_record_pending waits
+ * for nothing: *nsamples counts the samples taken or enqueued, *first_step (may be NULL) is the oldest one's step, -1
+ * if there is none.  hq_upload keeps recorders and pending samples; the due steps follow the new step number.
+ * hq_record_clear drops every recorder of the context and its memory (hq_destroy does, too); handles are not reused.
+ * Errors: HQ_ERR_ARG for null pointers, npoints < 0, rate <= 0, capacity <= 0, derivs outside 0..2, an id outside
+ * [0, nharbored), an unknown handle; HQ_ERR_STATE for derivs == 2 in the scatter variant (as hq_gather3).
+ * A context without recorders enqueues exactly what it did before they existed.
+ */
+typedef struct {
+    int32_t        npoints;
+    const int32_t* ids;       /* [npoints][8] local node ids (octor numbering), as hqh_stations returns them */
+    const double*  phi;       /* [npoints][8] trilinear weights */
+    int32_t        rate;      /* a sample at every step that is a multiple of rate (> 0) */
+    int32_t        derivs;    /* 0 displacement; 1 + velocity; 2 + acceleration (patch variant only) */
+    int32_t        capacity;  /* samples the device ring holds (> 0) */
+} hq_recorder_desc;
+HQ_API int hq_record_add(hq_ctx* ctx, const hq_recorder_desc* desc, int32_t* handle);
+HQ_API int hq_record_pending(hq_ctx* ctx, int32_t handle, int32_t* nsamples, int32_t* first_step);
+HQ_API int hq_record_fetch(hq_ctx* ctx, int32_t handle, int32_t max_samples, double* out, int32_t* steps,
+                           int32_t* nfetched);
+HQ_API int hq_record_clear(hq_ctx* ctx);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
