@@ -1627,8 +1627,6 @@ extern "C" int hq_device_count(void)
     return ok;
 }
 
-static int hq_brick_excluded(const hq_desc* d, std::vector<char>& excl);
-
 /* a node-ordered field [N][3] between the caller's numbering and the device's (c->perm; empty: the same) */
 static int hq_field_to_device(hq_ctx* c, const hq_real* host, hq_real* dev)
 {
@@ -1672,17 +1670,7 @@ static int hq_field_to_host(hq_ctx* c, const hq_real* dev, hq_real* host)
 
 static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, hq_ctx** out);
 
-/* the caller's n_t rows (solver_float at the ABI) as the doubles the planners and kernels work with: the caller's own
- * array where hq_real is double, a widened copy in `store` otherwise */
-static const double* hq_ntable64(const hq_desc* d, std::vector<double>& store)
-{
-    if (sizeof(hq_real) == sizeof(double)) return reinterpret_cast<const double*>(d->nTable);
-    const size_t n = 7 * (size_t)d->nharbored;
-    store.resize(n);
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < (int64_t)n; i++) store[(size_t)i] = (double)d->nTable[i];
-    return store.data();
-}
+#include "hq_prepare.h"
 
 extern "C" void hq_options_init(hq_options* o, uint64_t size)
 {
@@ -1715,9 +1703,6 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
 {
     if (!d || !out) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     *out = nullptr;
-    if (d->lenum < 0 || d->nharbored <= 0 || d->ldnnum < 0 || (d->lenum && !d->lnid) || !d->eTable ||
-        !d->nTable)
-        return hq_fail(HQ_ERR_ARG, "inconsistent mesh description%s", "");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return hq_fail(HQ_ERR_NODEVICE, "no HIP device: this engine has no CPU path%s", "");
@@ -1727,66 +1712,8 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return hq_fail(HQ_ERR_NODEVICE, "device is %s, kernels are built for gfx950 only", prop.gcnArchName);
     HQ_HIP(hipSetDevice(device));
-
-    hq_ctx* c = new (std::nothrow) hq_ctx();
-    if (!c) return hq_fail(HQ_ERR_NOMEM, "out of host memory%s", "");
-    c->device = device;
-    c->opts = opts;
-    c->E = d->lenum; c->N = d->nharbored; c->ldnnum = d->ldnnum;
-    c->dt = d->deltaT; c->dt2 = d->deltaT * d->deltaT;
-    c->rank = d->rank; c->nranks = d->nranks > 0 ? d->nranks : 1;
-    int rc = HQ_OK;
-    auto bail = [&](int r) { hq_destroy(c); return r; };
-
-    for (int64_t i = 0; i < (int64_t)c->E * 8; i++)
-        if (d->lnid[i] < 0 || d->lnid[i] >= c->N) return bail(hq_fail(HQ_ERR_ARG, "lnid out of range%s", ""));
-
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(hq_fail(HQ_ERR_DEVICE, "hipStreamCreate failed%s", ""));
-
-    int variant = d->variant;
-    if (variant == HQ_VARIANT_AUTO) variant = HQ_VARIANT_PATCH;
-    if (c->ldnnum && (!d->dn_ldnid || !d->dn_ptr || !d->dn_lanid))
-        return bail(hq_fail(HQ_ERR_ARG, "dangling-node tables missing%s", ""));
-    for (int32_t k = 0; k < c->ldnnum; k++) {
-        if (d->dn_ldnid[k] < 0 || d->dn_ldnid[k] >= c->N || d->dn_ptr[k + 1] <= d->dn_ptr[k])
-            return bail(hq_fail(HQ_ERR_ARG, "bad dangling-node table%s", ""));
-        for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++)
-            if (d->dn_lanid[a] < 0 || d->dn_lanid[a] >= c->N) return bail(hq_fail(HQ_ERR_ARG, "bad anchor id%s", ""));
-    }
-    if (c->ldnnum) {
-        /* an anchor must itself be anchored (octor's 2:1 balance guarantees it): the distribution kernels read the
-         * hanging nodes' rows while they add to the anchors' */
-        std::vector<char> is_dn((size_t)c->N, 0);
-        for (int32_t k = 0; k < c->ldnnum; k++) is_dn[d->dn_ldnid[k]] = 1;
-        for (int32_t a = 0; a < d->dn_ptr[c->ldnnum]; a++)
-            if (is_dn[d->dn_lanid[a]]) return bail(hq_fail(HQ_ERR_ARG, "an anchor is itself a hanging node%s", ""));
-    }
-    if (hipEventCreateWithFlags(&c->ev_sent, hipEventDisableTiming) != hipSuccess)
-        return bail(hq_fail(HQ_ERR_DEVICE, "hipEventCreate failed%s", ""));
-    if (variant != HQ_VARIANT_SCATTER && variant != HQ_VARIANT_PATCH)
-        return bail(hq_fail(HQ_ERR_ARG, "unknown variant%s", ""));
-    c->variant = variant;
-
-    /* element coefficients: (c1, c2, beta = c3/c1).  The fused product needs c3/c1 == c4/c2 (Rayleigh:
-     * both are b/dt, psolve.c:3386-3409); a table that applies different ratios to K1 and K2 is refused */
-    std::vector<double> c1(c->E), c2(c->E), beta(c->E);
-    for (int64_t e = 0; e < c->E; e++) {
-        const double* ep = d->eTable + 4 * e;
-        c1[e] = ep[0]; c2[e] = ep[1];
-        beta[e] = (ep[0] != 0.0) ? ep[2] / ep[0] : ((ep[1] != 0.0) ? ep[3] / ep[1] : 0.0);
-        const double lhs = ep[2] * ep[1], rhs = ep[3] * ep[0];
-        if (fabs(lhs - rhs) > 1e-12 * std::max(fabs(lhs), fabs(rhs)))
-            return bail(hq_fail(HQ_ERR_ARG, "eTable is not Rayleigh-proportional (c3/c1 != c4/c2): not the table solver_init builds%s", ""));
-    }
-
-
-    /*
-     * Bricks (hq_brick.h): where the mesh has simple nodes in bulk -- uniformly refined, homogeneous, no dashpot, not
-     * hanging, not on the partition interface -- they are stepped by the z-marching kernel on a tile-major layout.
-     * That needs the nodes renumbered: from here on `d` is the description in DEVICE numbering (c->perm maps the
-     * caller's ids); hq_set_source / hq_gather / hq_download / hq_upload translate.  Needs node_xyz.
-     */
+    const int variant = d->variant == HQ_VARIANT_AUTO ? HQ_VARIANT_PATCH : d->variant;
+    if (variant != HQ_VARIANT_SCATTER && variant != HQ_VARIANT_PATCH) return hq_fail(HQ_ERR_ARG, "unknown variant%s", "");
     if (variant == HQ_VARIANT_PATCH && !d->node_xyz) {
         static bool warned = false;
         if (!warned && !hq_set(opts.quiet)) {
@@ -1795,85 +1722,43 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
                             "order, element-form kernels only): expect about a third of the throughput; pass node_t.x/y/z\n");
         }
     }
+
+    /* everything that needs no device (hq_prepare.h): from here on `d` is the description in DEVICE numbering (c->perm
+     * maps the caller's ids); the start fields alone are still the caller's */
+    const hq_real *h_tm1 = d->tm1, *h_tm2 = d->tm2;
+    hq_prep prep;
+    HQ_TRY(hq_prepare(d, opts, HQ_PREP_COEF | HQ_PREP_NT | (variant == HQ_VARIANT_PATCH ? HQ_PREP_BRICKS : 0), &prep));
+    d = &prep.desc;
+    std::vector<char>().swap(prep.excl);
+    const hq_brick_host& BH = prep.bricks;
+    const double* ntab = prep.ntab;
+
+    hq_ctx* c = new (std::nothrow) hq_ctx();
+    if (!c) return hq_fail(HQ_ERR_NOMEM, "out of host memory%s", "");
+    c->device = device;
+    c->opts = opts;
+    c->E = d->lenum; c->N = d->nharbored; c->ldnnum = d->ldnnum;
+    c->dt = d->deltaT; c->dt2 = d->deltaT * d->deltaT;
+    c->rank = d->rank; c->nranks = d->nranks > 0 ? d->nranks : 1;
+    c->variant = variant;
+    c->perm = std::move(prep.perm);
+    int rc = HQ_OK;
+    auto bail = [&](int r) { hq_destroy(c); return r; };
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
+        return bail(hq_fail(HQ_ERR_DEVICE, "hipStreamCreate failed%s", ""));
+    if (hipEventCreateWithFlags(&c->ev_sent, hipEventDisableTiming) != hipSuccess)
+        return bail(hq_fail(HQ_ERR_DEVICE, "hipEventCreate failed%s", ""));
+
     /* HQ_PATCH_VERBOSE: where hq_create's time goes */
     const bool verbose = hq_set(opts.verbose);
     auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!verbose) return;
+    auto lap = [&](const char* what, double s = -1.0) {
         const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "hq_create: %-34s %7.2f s\n", what, std::chrono::duration<double>(now - t_last).count());
+        if (verbose) fprintf(stderr, "hq_create: %-34s %7.2f s\n", what, s >= 0.0 ? s : std::chrono::duration<double>(now - t_last).count());
         t_last = now;
     };
-    hq_desc dd = *d;
-    std::vector<int32_t> p_lnid, p_xyz, p_dn_id, p_dn_anchor;
-    std::vector<double> p_nt, nt64;
-    const double* ntab = hq_ntable64(d, nt64);       /* [N][7] doubles, in the numbering `d` has at the moment */
-    std::vector<int64_t> p_gnid;
-    std::vector<std::vector<int32_t>> p_maps;
-    std::vector<hq_messenger> p_msg[4];
-    hq_brick_host BH;
-    const hq_real *h_tm1 = d->tm1, *h_tm2 = d->tm2;
-    if (variant == HQ_VARIANT_PATCH && d->node_xyz && !hq_set(opts.no_bricks)) {
-        std::vector<char> excl;
-        if ((rc = hq_brick_excluded(d, excl)) != HQ_OK) return bail(rc);
-        hq_mat_src ms;
-        ms.edata = d->edata; ms.dt = d->deltaT; ms.bbase = d->mat_bbase; ms.thr_damp = d->mat_threshold_damping; ms.thr_vpvs = d->mat_threshold_vpvs;
-        if (hq_brick_plan_host(opts, c->E, c->N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab, excl.data(), &BH, &ms) != 0)
-            return bail(hq_fail(HQ_ERR_ARG, "brick plan: %s", hq_patch_error()));
-        lap("brick plan");
-    }
-    if (BH.nb > 0) {
-        const std::vector<int32_t>& pm = BH.perm;
-        const int64_t N = c->N;
-        p_lnid.resize((size_t)c->E * 8);
-#pragma omp parallel for schedule(static)
-        for (int64_t i = 0; i < (int64_t)c->E * 8; i++) p_lnid[(size_t)i] = pm[(size_t)d->lnid[i]];
-        p_xyz.resize((size_t)N * 3);
-        p_nt.resize((size_t)N * 7);
-#pragma omp parallel for schedule(static)
-        for (int64_t n = 0; n < N; n++) {
-            const int64_t q = pm[(size_t)n];
-            for (int k = 0; k < 3; k++) p_xyz[(size_t)(3 * q + k)] = d->node_xyz[3 * n + k];
-            for (int k = 0; k < 7; k++) p_nt[(size_t)(7 * q + k)] = ntab[7 * n + k];
-        }
-        dd.lnid = p_lnid.data(); dd.node_xyz = p_xyz.data(); dd.nTable = nullptr; ntab = p_nt.data();
-        std::vector<double>().swap(nt64);
-        if (d->node_gnid) {
-            p_gnid.resize((size_t)N);
-            for (int64_t n = 0; n < N; n++) p_gnid[(size_t)pm[(size_t)n]] = d->node_gnid[n];
-            dd.node_gnid = p_gnid.data();
-        }
-        if (c->ldnnum) {
-            const int32_t na = d->dn_ptr[c->ldnnum];
-            p_dn_id.resize((size_t)c->ldnnum); p_dn_anchor.resize((size_t)na);
-            for (int32_t k = 0; k < c->ldnnum; k++) p_dn_id[(size_t)k] = pm[(size_t)d->dn_ldnid[k]];
-            for (int32_t a = 0; a < na; a++) p_dn_anchor[(size_t)a] = pm[(size_t)d->dn_lanid[a]];
-            dd.dn_ldnid = p_dn_id.data(); dd.dn_lanid = p_dn_anchor.data();
-        }
-        {
-            const hq_schedule* in[2] = { &d->an_sched, &d->dn_sched };
-            hq_schedule* out[2] = { &dd.an_sched, &dd.dn_sched };
-            size_t nm = 0;
-            for (int s2 = 0; s2 < 2; s2++) nm += (size_t)in[s2]->c_count + (size_t)in[s2]->s_count;
-            p_maps.reserve(nm);
-            for (int s2 = 0; s2 < 2; s2++)
-                for (int side = 0; side < 2; side++) {
-                    const int32_t cnt = side ? in[s2]->s_count : in[s2]->c_count;
-                    const hq_messenger* list = side ? in[s2]->first_s : in[s2]->first_c;
-                    std::vector<hq_messenger>& v = p_msg[2 * s2 + side];
-                    for (int32_t i = 0; i < cnt; i++) {
-                        p_maps.emplace_back((size_t)list[i].nodecount);
-                        for (int32_t k = 0; k < list[i].nodecount; k++) p_maps.back()[(size_t)k] = pm[(size_t)list[i].mapping[k]];
-                        v.push_back({ list[i].procid, list[i].nodecount, p_maps.back().data() });
-                    }
-                    if (side) out[s2]->first_s = v.data(); else out[s2]->first_c = v.data();
-                }
-        }
-        dd.tm1 = dd.tm2 = nullptr;              /* uploaded through the permutation below */
-        c->perm = BH.perm;
-        d = &dd;
-        lap("renumbering");
-    }
+    if (prep.brick_plan_s > 0.0) lap("brick plan", prep.brick_plan_s);
+    if (BH.nb > 0) lap("renumbering", prep.renumber_s);
 
     /* node state */
     size_t n3 = (size_t)c->N * 3;
@@ -1945,9 +1830,9 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
         if ((rc = hq_dev_alloc(c, &c->d_c2, (size_t)c->E)) != HQ_OK) return bail(rc);
         if ((rc = hq_dev_alloc(c, &c->d_beta, (size_t)c->E)) != HQ_OK) return bail(rc);
         if (hipMemcpy(c->d_lnid, soa.data(), sizeof(int32_t) * soa.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_c1, c1.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_c2, c2.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_beta, beta.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess)
+            hipMemcpy(c->d_c1, prep.c1.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(c->d_c2, prep.c2.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(c->d_beta, prep.beta.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess)
             return bail(hq_fail(HQ_ERR_DEVICE, "element table upload failed%s", ""));
         if ((rc = hq_build_schedule(c, &d->an_sched, &c->an)) != HQ_OK) return bail(rc);
         if ((rc = hq_build_schedule(c, &d->dn_sched, &c->dn)) != HQ_OK) return bail(rc);
@@ -1961,46 +1846,9 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
         }
     } else {
         int64_t pb = 0;
-        /* hanging nodes the patches may distribute themselves: owned and not shared with any rank
-         * (the shared ones wait for the contribution exchange, hq_setup_interface) */
-        std::vector<char> shared_dn((size_t)c->N, 0);
-        for (int32_t i = 0; i < d->dn_sched.s_count; i++)
-            for (int32_t k = 0; k < d->dn_sched.first_s[i].nodecount; k++) {
-                int32_t n = d->dn_sched.first_s[i].mapping[k];
-                if (n < 0 || n >= c->N) return bail(hq_fail(HQ_ERR_ARG, "messenger node id out of range%s", ""));
-                shared_dn[n] = 1;
-            }
-        std::vector<int32_t> l_id, l_ptr(1, 0), l_anc;
-        for (int32_t k = 0; k < c->ldnnum; k++) {
-            if (shared_dn[d->dn_ldnid[k]]) continue;
-            l_id.push_back(d->dn_ldnid[k]);
-            for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++) l_anc.push_back(d->dn_lanid[a]);
-            l_ptr.push_back((int32_t)l_anc.size());
-        }
-        hq_dangling dn;
-        dn.n = (int32_t)l_id.size(); dn.id = l_id.data(); dn.ptr = l_ptr.data(); dn.anchor = l_anc.data();
-        /* nodes whose update is finished elsewhere: hanging nodes (compute_adjust) and the partition interface
-         * (every node a schedule names, and the anchors of owned hanging nodes that other ranks share) */
-        std::vector<char> seed0((size_t)c->N, 0);
-        for (int32_t k = 0; k < c->ldnnum; k++) {
-            seed0[d->dn_ldnid[k]] = 1;
-            if (shared_dn[d->dn_ldnid[k]])
-                for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++) seed0[d->dn_lanid[a]] = 1;
-        }
-        for (const hq_schedule* sc : { &d->an_sched, &d->dn_sched })
-            for (int side = 0; side < 2; side++) {
-                const int32_t cnt = side ? sc->s_count : sc->c_count;
-                const hq_messenger* list = side ? sc->first_s : sc->first_c;
-                for (int32_t i = 0; i < cnt; i++)
-                    for (int32_t k = 0; k < list[i].nodecount; k++) {
-                        const int32_t n = list[i].mapping ? list[i].mapping[k] : -1;
-                        if (n < 0 || n >= c->N) return bail(hq_fail(HQ_ERR_ARG, "messenger node id out of range%s", ""));
-                        seed0[n] = 1;
-                    }
-            }
         c->plan.ragged_default = true;
-        rc = hq_patch_build(opts, &c->plan, c->E, c->N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab,
-                            dn, seed0.data(), &pb, BH.nb);
+        rc = hq_patch_build(opts, &c->plan, c->E, c->N, d->lnid, d->node_xyz, prep.c1.data(), prep.c2.data(), prep.beta.data(), ntab,
+                            prep.dn, prep.seed0.data(), &pb, BH.nb);
         lap("patch plan");
         if (rc == 0 && BH.nb > 0) rc = hq_brick_upload(&c->bricks, BH, &pb);
         c->bricks.mat = { 0.0, 0.0, d->deltaT, d->mat_bbase, d->mat_threshold_damping, d->mat_threshold_vpvs };
@@ -2022,555 +1870,7 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
     return HQ_OK;
 }
 
-/*
- * Host-only self-check of the patch planner (no device needed; the -m "not gpu" tests call it):
- * plans the mesh exactly as hq_create does and verifies that every element row names the LDS rows
- * of its element's eight nodes, that the accumulate flags are exactly the owned nodes and the
- * hanging nodes on owned anchors, and counts the LDS passes of the gathers under the bank rule of
- * MI355X_MICROARCH.md (32-lane groups, rows distinct modulo 32).
- * report: {patches, lattice patches, (patch, element) pairs, distinct element-row blocks,
- *          gather passes, gather instructions (per 32-lane group), gather passes of the lattice patches
- *          (= 23 groups x 8 corners each when conflict-free), faults}
- */
-extern "C" int hq_plan_check(const hq_desc* d, int64_t report[8])
-{
-    hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
-    hq_options_resolve(&opts, nullptr);
-    if (!d || !report || d->lenum < 0 || d->nharbored <= 0 || (d->lenum && !d->lnid))
-        return hq_fail(HQ_ERR_ARG, "inconsistent mesh description%s", "");
-    const int64_t E = d->lenum, N = d->nharbored;
-    for (int64_t i = 0; i < E * 8; i++)
-        if (d->lnid[i] < 0 || d->lnid[i] >= N) return hq_fail(HQ_ERR_ARG, "lnid out of range%s", "");
-    std::vector<char> shared_dn((size_t)N, 0);
-    for (int32_t i = 0; i < d->dn_sched.s_count; i++)
-        for (int32_t k = 0; k < d->dn_sched.first_s[i].nodecount; k++) shared_dn[d->dn_sched.first_s[i].mapping[k]] = 1;
-    std::vector<int32_t> l_id, l_ptr(1, 0), l_anc;
-    for (int32_t k = 0; k < d->ldnnum; k++) {
-        if (shared_dn[d->dn_ldnid[k]]) continue;
-        l_id.push_back(d->dn_ldnid[k]);
-        for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++) l_anc.push_back(d->dn_lanid[a]);
-        l_ptr.push_back((int32_t)l_anc.size());
-    }
-    hq_dangling dn;
-    dn.n = (int32_t)l_id.size(); dn.id = l_id.data(); dn.ptr = l_ptr.data(); dn.anchor = l_anc.data();
-    bool want_lattice = false;
-    const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, d->node_xyz != nullptr, &want_lattice);
-    hq_patch_host H;
-    if (hq_patch_plan_host(opts, cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
-        return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
-    const hq_lattice_tab& T = hq_lattice();
-    int64_t nlat = 0, passes = 0, lpasses = 0, instr = 0, bad = 0;
-    std::vector<int32_t> covered((size_t)N, 0);
-#pragma omp parallel for schedule(dynamic, 64) reduction(+ : nlat, passes, lpasses, instr, bad)
-    for (int64_t p = 0; p < (int64_t)H.desc.size(); p++) {
-        const hq_patch_desc& D = H.desc[(size_t)p];
-        const bool lat = H.lattice[(size_t)p] != 0;
-        nlat += lat;
-        std::vector<int32_t> node_of_row(lat ? HQ_LAT_ROWS : (size_t)(D.nown + D.nhalo), -1);
-        for (int32_t t = 0; t < D.nown + D.nhalo; t++) {
-            const int32_t g = t < D.nown ? D.base + t : H.halo[(size_t)D.halo_off + (t - D.nown)];
-            const int32_t r = lat ? (int32_t)T.row_of_local[t] : t;
-            if (r < 0 || r >= (int32_t)node_of_row.size() || node_of_row[r] >= 0) { bad++; continue; }
-            node_of_row[r] = g;
-        }
-        for (int32_t t = 0; t < D.nown; t++) {
-#pragma omp atomic
-            covered[(size_t)D.base + t]++;
-        }
-        const uint16_t* rows = H.pidx.data() + 8 * (size_t)D.pidx_off;
-        for (int32_t q = 0; q < D.npairs; q++) {
-            const int32_t* id = d->lnid + 8 * (int64_t)H.pelem[(size_t)D.pair_off + q];
-            for (int c = 0; c < 8; c++) {
-                const int32_t r = rows[8 * (size_t)q + c] & HQ_PIDX_ROW;
-                const bool acc = (rows[8 * (size_t)q + c] & HQ_PIDX_ACC) != 0;
-                if (r >= (int32_t)node_of_row.size() || node_of_row[r] != id[c]) { bad++; continue; }
-                const bool owned = id[c] >= D.base && id[c] < D.base + D.nown;
-                /* an accumulator: owned nodes, and (id-ordered patches) the first nacc - nown halo rows */
-                const bool want = owned || (!lat && r < D.nacc);
-                if (acc != want) bad++;
-                if (lat && acc && r >= HQ_LAT_ACC) bad++;
-            }
-        }
-        for (int32_t w = 0; w < D.npairs; w += 32)
-            for (int c = 0; c < 8; c++) {
-                int cls[32] = { 0 }, mx = 0;
-                for (int32_t q = w; q < std::min(w + 32, D.npairs); q++) {
-                    /* identical rows broadcast; distinct rows of one class take a pass each */
-                    const int32_t r = rows[8 * (size_t)q + c] & HQ_PIDX_ROW;
-                    bool dup = false;
-                    for (int32_t q2 = w; q2 < q; q2++) dup |= ((rows[8 * (size_t)q2 + c] & HQ_PIDX_ROW) == r);
-                    if (!dup) mx = std::max(mx, ++cls[r & 31]);
-                }
-                passes += mx;
-                if (lat) lpasses += mx;
-                instr++;
-            }
-    }
-    for (int64_t n = 0; n < N; n++) if (covered[(size_t)n] != 1) bad++;
-    if (hq_set(opts.verbose)) {                                 /* owned-node histogram of the patches */
-        int64_t hist[8] = { 0 }, hp[8] = { 0 };
-        for (auto& D : H.desc) {
-            int b = D.nown <= 8 ? 0 : D.nown <= 64 ? 1 : D.nown <= 128 ? 2 : D.nown <= 256 ? 3 : D.nown < 512 ? 4 : D.nown == 512 ? 5 : D.nown <= 640 ? 6 : 7;
-            hist[b]++; hp[b] += D.npairs;
-        }
-        const char* nm[8] = { "<=8", "<=64", "<=128", "<=256", "<512", "=512", "<=640", ">640" };
-        for (int b = 0; b < 8; b++) fprintf(stderr, "hq plan: %8lld patches with %6s owned nodes, %10lld pairs\n", (long long)hist[b], nm[b], (long long)hp[b]);
-    }
-    report[0] = (int64_t)H.desc.size(); report[1] = nlat; report[2] = (int64_t)H.pelem.size();
-    report[3] = H.ndistinct; report[4] = passes; report[5] = instr;
-    report[6] = lpasses; report[7] = bad;
-    if (bad) return hq_fail(HQ_ERR_STATE, "patch plan self-check failed%s", "");
-    return HQ_OK;
-}
-
-/*
- * The sixteen numbers of the assembled 27-point stencil (hq_stencil in hq_patch.h), as hq_k_patch_stencil
- * uses them: out = {p1[6], p2[6], q1[2], q2[2]} for S = c1 S1 + c2 S2.  Host only; HQ_ERR_STATE if the
- * cube symmetry the kernel relies on does not hold for the element arithmetic (then no patch is marked).
- */
-extern "C" int hq_stencil_coefficients(double out[16])
-{
-    if (!out) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const hq_stencil_tab& t = hq_stencil();
-    for (int i = 0; i < 6; i++) { out[i] = t.c.p1[i]; out[6 + i] = t.c.p2[i]; }
-    for (int i = 0; i < 2; i++) { out[12 + i] = t.c.q1[i]; out[14 + i] = t.c.q2[i]; }
-    return t.ok ? HQ_OK : hq_fail(HQ_ERR_STATE, "the assembled stencil lacks the cube symmetry%s", "");
-}
-
-/*
- * Host-only self-check of what hq_k_patch_stencil reads (needs no device).  Plans `desc` as hq_create would; for every
- * patch whose geometry hq_ragged_match accepts (whatever its coefficients) it checks the shape table against the
- * mesh: rows distinct and inside the image; the eight nodes of every element of the patch at row(corner 0) + the
- * lattice offsets of their corner; the element mask of every owned node = the corners it really is in the patch's
- * elements; the boundary list = the owned nodes with an incomplete mask, in order, with their index.  And once: the
- * element-matrix blocks E1, E2 of the boundary phase reproduce hq_element_force (the kernels' own arithmetic) for
- * random displacements and every subset of present octants.
- * report = {patches, patches with a table, full lattices among them, boundary nodes, element corners checked, faults}
- */
-extern "C" int hq_stencil_plan_check(const hq_desc* d, int64_t report[6])
-{
-    hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
-    hq_options_resolve(&opts, nullptr);
-    if (!d || !report || d->lenum < 0 || d->nharbored <= 0 || (d->lenum && !d->lnid) || !d->node_xyz)
-        return hq_fail(HQ_ERR_ARG, "inconsistent mesh description (node_xyz is needed)%s", "");
-    const int64_t E = d->lenum, N = d->nharbored;
-    for (int64_t i = 0; i < E * 8; i++)
-        if (d->lnid[i] < 0 || d->lnid[i] >= N) return hq_fail(HQ_ERR_ARG, "lnid out of range%s", "");
-    std::vector<char> shared_dn((size_t)N, 0);
-    for (int32_t i = 0; i < d->dn_sched.s_count; i++)
-        for (int32_t k = 0; k < d->dn_sched.first_s[i].nodecount; k++) shared_dn[d->dn_sched.first_s[i].mapping[k]] = 1;
-    std::vector<int32_t> l_id, l_ptr(1, 0), l_anc;
-    for (int32_t k = 0; k < d->ldnnum; k++) {
-        if (shared_dn[d->dn_ldnid[k]]) continue;
-        l_id.push_back(d->dn_ldnid[k]);
-        for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++) l_anc.push_back(d->dn_lanid[a]);
-        l_ptr.push_back((int32_t)l_anc.size());
-    }
-    hq_dangling dn;
-    dn.n = (int32_t)l_id.size(); dn.id = l_id.data(); dn.ptr = l_ptr.data(); dn.anchor = l_anc.data();
-    bool want_lattice = false;
-    const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, true, &want_lattice);
-    hq_patch_host H;
-    if (hq_patch_plan_host(opts, cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
-        return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
-    int64_t ntab = 0, nfull = 0, nbnd_tot = 0, ncorner = 0, bad = 0;
-#pragma omp parallel for schedule(dynamic, 64) reduction(+ : ntab, nfull, nbnd_tot, ncorner, bad)
-    for (int64_t p = 0; p < (int64_t)H.desc.size(); p++) {
-        const hq_patch_desc& D = H.desc[(size_t)p];
-        if (D.nacc != D.nown) continue;
-        if (!H.ds_ptr.empty() && H.ds_ptr[(size_t)p + 1] > H.ds_ptr[(size_t)p]) continue;
-        std::vector<int32_t> h(H.halo.begin() + D.halo_off, H.halo.begin() + D.halo_off + D.nhalo);
-        std::vector<uint32_t> tab;
-        int32_t nbnd = 0;
-        if (!hq_ragged_match(D.base, D.nown, d->lnid, d->node_xyz, &H.pelem[(size_t)D.pair_off], D.npairs, h, tab, &nbnd)) continue;
-        ntab++;
-        nbnd_tot += nbnd;
-        if (nbnd == 0 && D.nown == HQ_LAT_NOWN && D.nhalo == HQ_LAT_NHALO && D.npairs == HQ_LAT_NELEM) nfull++;
-        const int32_t nloc = D.nown + D.nhalo;
-        if ((int32_t)tab.size() < nloc + nbnd) { bad++; continue; }
-        std::unordered_map<int32_t, int32_t> local_of;
-        std::vector<char> used(HQ_ST_ROWS, 0);
-        for (int32_t t = 0; t < nloc; t++) {
-            local_of[t < D.nown ? D.base + t : h[(size_t)(t - D.nown)]] = t;
-            const int r = HQ_RG_ROW(tab[(size_t)t]);
-            if (r >= HQ_ST_ROWS || used[(size_t)r]) bad++; else used[(size_t)r] = 1;
-        }
-        std::vector<unsigned> want((size_t)D.nown, 0u);
-        for (int32_t q = 0; q < D.npairs; q++) {
-            const int32_t* id = d->lnid + 8 * (int64_t)H.pelem[(size_t)D.pair_off + q];
-            auto it0 = local_of.find(id[0]);
-            if (it0 == local_of.end()) { bad++; continue; }
-            const int r0 = HQ_RG_ROW(tab[(size_t)it0->second]);
-            for (int c = 0; c < 8; c++) {
-                auto it = local_of.find(id[c]);
-                if (it == local_of.end()) { bad++; continue; }
-                const int r = HQ_RG_ROW(tab[(size_t)it->second]);
-                if (r != r0 + HQ_ST_PX * (c & 1) + HQ_ST_PY * ((c >> 1) & 1) + HQ_ST_PZ * ((c >> 2) & 1)) bad++;
-                if (it->second < D.nown) want[(size_t)it->second] |= 1u << c;
-                ncorner++;
-            }
-        }
-        int32_t nb = 0;
-        for (int32_t t = 0; t < D.nown; t++) {
-            const uint32_t w = tab[(size_t)t];
-            if (HQ_RG_MASK(w) != want[(size_t)t]) bad++;
-            if (want[(size_t)t] != 0xffu) {
-                if (nb >= nbnd || HQ_RG_BIDX(w) != nb) bad++;
-                else {
-                    const uint32_t b = tab[(size_t)(nloc + nb)];
-                    if (HQ_RG_ROW(b) != HQ_RG_ROW(w) || HQ_RG_MASK(b) != want[(size_t)t]) bad++;
-                }
-                nb++;
-            }
-        }
-        if (nb != nbnd) bad++;
-    }
-    /* E1, E2 against the element arithmetic: a node that is corner o of its present elements */
-    {
-        const hq_stencil_tab& T = hq_stencil();
-        if (!T.ok) bad++;
-        uint64_t seed = 88172645463325252ull;
-        auto rnd = [&]() { seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17; return (double)(seed >> 11) / 9007199254740992.0 - 0.5; };
-        for (int trial = 0; trial < 64; trial++) {
-            const double c1 = 1.0 + rnd(), c2 = 2.0 + rnd();
-            const unsigned mask = (unsigned)(trial * 37 + 1) & 0xffu;
-            double w[27][3];                             /* the 3x3x3 nodes around the node, index (dx+1) + 3 (dy+1) + 9 (dz+1) */
-            for (auto& r : w) for (double& v : r) v = rnd();
-            double ref[3] = { 0, 0, 0 }, got[3] = { 0, 0, 0 };
-            for (int o = 0; o < 8; o++) {
-                if (!((mask >> o) & 1)) continue;
-                double X[8], Y[8], Z[8];
-                for (int m = 0; m < 8; m++) {
-                    const int dx = (m & 1) - (o & 1), dy = ((m >> 1) & 1) - ((o >> 1) & 1), dz = ((m >> 2) & 1) - ((o >> 2) & 1);
-                    const double* q = w[(dx + 1) + 3 * (dy + 1) + 9 * (dz + 1)];
-                    X[m] = q[0]; Y[m] = q[1]; Z[m] = q[2];
-                    for (int a = 0; a < 3; a++)
-                        for (int b = 0; b < 3; b++) {
-                            const int k = ((o * 8 + m) * 3 + a) * 3 + b;
-                            got[a] += (c1 * T.E1[k] + c2 * T.E2[k]) * q[b];
-                        }
-                }
-                hq_element_force(X, Y, Z, c1, c2);
-                ref[0] += X[o]; ref[1] += Y[o]; ref[2] += Z[o];
-            }
-            for (int a = 0; a < 3; a++)
-                if (fabs(got[a] - ref[a]) > 1e-12 * (fabs(ref[a]) + 1.0)) bad++;
-        }
-    }
-    report[0] = (int64_t)H.desc.size(); report[1] = ntab; report[2] = nfull; report[3] = nbnd_tot; report[4] = ncorner;
-    report[5] = bad;
-    if (bad) return hq_fail(HQ_ERR_STATE, "stencil table self-check failed%s", "");
-    return HQ_OK;
-}
-
-/* nodes that must stay with the patches: hanging nodes, their anchors, every node a schedule names */
-static int hq_brick_excluded(const hq_desc* d, std::vector<char>& excl)
-{
-    excl.assign((size_t)d->nharbored, 0);
-    for (int32_t k = 0; k < d->ldnnum; k++) {
-        excl[d->dn_ldnid[k]] = 1;
-        for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++) excl[d->dn_lanid[a]] = 1;
-    }
-    for (const hq_schedule* sc : { &d->an_sched, &d->dn_sched })
-        for (int side = 0; side < 2; side++) {
-            const int32_t cnt = side ? sc->s_count : sc->c_count;
-            const hq_messenger* list = side ? sc->first_s : sc->first_c;
-            for (int32_t i = 0; i < cnt; i++)
-                for (int32_t k = 0; k < list[i].nodecount; k++) {
-                    const int32_t n = list[i].mapping ? list[i].mapping[k] : -1;
-                    if (n < 0 || n >= d->nharbored) return hq_fail(HQ_ERR_ARG, "messenger node id out of range%s", "");
-                    excl[n] = 1;
-                }
-        }
-    return HQ_OK;
-}
-
-/*
- * Host-only self-check of the brick planner (needs no device; desc->node_xyz required).  Plans the bricks as
- * hq_create would and verifies, against the mesh's connectivity alone (node -> elements, no coordinates): the
- * numbering is a permutation; every brick node lies in exactly one unit, is the corner of exactly eight elements
- * (one per corner) with the unit's (c1, c2, beta), has an n_t row without dashpot terms (the unit's row where the
- * unit says they are all the same), is neither hanging, an anchor, nor named in a schedule; and each of its 26
- * neighbours -- found through those eight elements -- is the node the kernel will read at that offset: a node of
- * the unit, an entry of the unit's ring table or of its first / last plane's id list.
- * report = {brick nodes, tile columns, units, units with one n_t row, levels, neighbours checked, patch nodes, faults}
- */
-static thread_local int64_t g_brick_check_extra[4];    /* the last check's ragged units and the nodes they own (hq_brick_plan_check_n) */
-
-extern "C" int hq_brick_plan_check(const hq_desc* d, int64_t report[8])
-{
-    hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
-    hq_options_resolve(&opts, nullptr);
-    if (!d || !report || d->lenum < 0 || d->nharbored <= 0 || (d->lenum && !d->lnid) || !d->node_xyz || !d->eTable || !d->nTable)
-        return hq_fail(HQ_ERR_ARG, "inconsistent mesh description (node_xyz is needed)%s", "");
-    const int64_t E = d->lenum, N = d->nharbored;
-    for (int64_t i = 0; i < E * 8; i++)
-        if (d->lnid[i] < 0 || d->lnid[i] >= N) return hq_fail(HQ_ERR_ARG, "lnid out of range%s", "");
-    std::vector<double> c1((size_t)E), c2((size_t)E), beta((size_t)E);
-    for (int64_t e = 0; e < E; e++) {
-        const double* ep = d->eTable + 4 * e;
-        c1[(size_t)e] = ep[0]; c2[(size_t)e] = ep[1];
-        beta[(size_t)e] = (ep[0] != 0.0) ? ep[2] / ep[0] : ((ep[1] != 0.0) ? ep[3] / ep[1] : 0.0);
-    }
-    std::vector<char> excl;
-    HQ_TRY(hq_brick_excluded(d, excl));
-    hq_brick_host B;
-    hq_mat_src ms;
-    ms.edata = d->edata; ms.dt = d->deltaT; ms.bbase = d->mat_bbase; ms.thr_damp = d->mat_threshold_damping; ms.thr_vpvs = d->mat_threshold_vpvs;
-    std::vector<double> nt64;
-    const double* ntab = hq_ntable64(d, nt64);
-    if (hq_brick_plan_host(opts, E, N, d->lnid, d->node_xyz, c1.data(), c2.data(), beta.data(), ntab, excl.data(), &B, &ms) != 0)
-        return hq_fail(HQ_ERR_ARG, "brick plan: %s", hq_patch_error());
-    int64_t bad = 0, nchecked = 0;
-    for (int k = 0; k < 8; k++) report[k] = 0;
-    report[6] = N;
-    if (B.nb == 0) return HQ_OK;
-    /* permutation and its inverse */
-    std::vector<int32_t> inv((size_t)N, -1);
-    for (int64_t n = 0; n < N; n++) {
-        const int32_t q = B.perm[(size_t)n];
-        if (q < 0 || q >= N || inv[(size_t)q] != -1) { bad++; continue; }
-        inv[(size_t)q] = (int32_t)n;
-    }
-    /* node -> (element, corner) */
-    std::vector<int64_t> aptr((size_t)N + 1, 0);
-    for (int64_t i = 0; i < E * 8; i++) aptr[(size_t)d->lnid[i] + 1]++;
-    for (int64_t n = 0; n < N; n++) aptr[(size_t)n + 1] += aptr[(size_t)n];
-    std::vector<int64_t> adj((size_t)(E * 8));
-    {
-        std::vector<int64_t> fill(aptr.begin(), aptr.end() - 1);
-        for (int64_t i = 0; i < E * 8; i++) adj[(size_t)fill[(size_t)d->lnid[i]]++] = i;
-    }
-    std::vector<int32_t> covered((size_t)B.nb, 0);
-    int64_t nsame = 0;
-#pragma omp parallel for schedule(dynamic, 4) reduction(+ : bad, nchecked, nsame)
-    for (int64_t u = 0; u < (int64_t)B.units.size(); u++) {
-        const hq_brick_unit& U = B.units[(size_t)u];
-        const int nx = U.nx, ny = U.ny, np = U.np, nr = 2 * (nx + 2) + 2 * ny;
-        const bool het = (U.flags & HQ_BK_HET) != 0, rag = (U.flags & HQ_BK_RAGGED) != 0;
-        if (nx < 1 || nx > (het ? HQ_BH_TX : HQ_BK_TX) || ny < 1 || ny > (het ? HQ_BH_TY : HQ_BK_TY) || np < 1 || U.base < 0 ||
-            (!rag && U.base + (int64_t)nx * ny * np > B.nb)) { bad++; continue; }
-        nsame += (U.flags & HQ_BK_NTSAME) != 0;
-        if (((U.flags & HQ_BK_NTSAME) != 0) != (u < B.nsame)) bad++;
-        /* the launch order: one n_t row | ragged (one row) | per-node rows | HET | HET packed | ragged HET | ragged HET packed */
-        const int64_t nu = (int64_t)B.units.size();
-        if ((rag && !het) != (u >= B.nsame - B.nrag && u < B.nsame) || (rag && (U.flags & (HQ_BK_TOPFACE | HQ_BK_BOTFACE)))) { bad++; continue; }
-        if ((rag && het) != (u >= nu - B.nrhet)) { bad++; continue; }
-        if (het != (u >= nu - B.nhet - B.nrhet)) bad++;
-        if (het && ((U.flags & HQ_BK_PACKED) != 0) != (rag ? u >= nu - B.nrpacked : (u >= nu - B.nrhet - B.npacked && u < nu - B.nrhet))) bad++;
-        if (het && (U.coef < 0 || U.coef + (int64_t)(np + 1) * HQ_BH_THREADS * 3 > (int64_t)B.coef.size())) { bad++; continue; }
-        const int32_t* ring = B.tab.data() + U.tab;
-        const int32_t* cap = ring + (int64_t)(np + 2) * nr;
-        /* the device id the kernel reads at (x, y) of plane k, k = -1 .. np */
-        auto at = [&](int x, int y, int k) -> int64_t {
-            const bool in = x >= 0 && x < nx && y >= 0 && y < ny;
-            if (in && rag) {                 /* the plane table: owned ids as they are, the others as -id - 2 */
-                const int32_t v = cap[(int64_t)(k + 1) * nx * ny + y * nx + x];
-                return v >= 0 ? v : (v == -1 ? -1 : -(int64_t)v - 2);
-            }
-            if (in) {
-                if (k >= 0 && k < np) return U.base + ((int64_t)k * ny + y) * nx + x;
-                return cap[(k < 0 ? 0 : nx * ny) + y * nx + x];
-            }
-            const int32_t* r = ring + (int64_t)(k + 1) * nr;
-            if (y == -1) return r[x + 1];
-            if (y == ny) return r[nx + 2 + x + 1];
-            if (x == -1) return r[2 * (nx + 2) + y];
-            return r[2 * (nx + 2) + ny + y];
-        };
-        int64_t next = U.base;               /* a ragged unit numbers what it owns plane by plane without gaps */
-        for (int k = 0; k < np; k++)
-            for (int y = 0; y < ny; y++)
-                for (int x = 0; x < nx; x++) {
-                    int64_t q = U.base + ((int64_t)k * ny + y) * nx + x;
-                    if (rag) {
-                        const int32_t v = cap[(int64_t)(k + 1) * nx * ny + y * nx + x];
-                        if (v < 0) continue;
-                        if (v != next++ || v >= B.nb) { bad++; continue; }
-                        q = v;
-                    }
-#pragma omp atomic
-                    covered[(size_t)q]++;
-                    const int32_t n = inv[(size_t)q];
-                    if (n < 0) { bad++; continue; }
-                    if (excl[(size_t)n]) bad++;
-                    const double* t7 = ntab + 7 * (int64_t)n;
-                    if (!((t7[1] == t7[2]) && (t7[1] == t7[3]) && (t7[4] == t7[5]) && (t7[4] == t7[6]))) bad++;
-                    if ((U.flags & HQ_BK_NTSAME) && (t7[0] != U.m0 || t7[1] != U.m2 || t7[4] != U.m1)) bad++;
-                    int64_t el[8];
-                    for (int o = 0; o < 8; o++) el[o] = -1;
-                    if (aptr[(size_t)n + 1] - aptr[(size_t)n] != 8) { bad++; continue; }
-                    bool ok = true;
-                    for (int64_t a = aptr[(size_t)n]; a < aptr[(size_t)n + 1]; a++) {
-                        const int64_t e = adj[(size_t)a] >> 3;
-                        const int o = (int)(adj[(size_t)a] & 7);
-                        if (el[o] != -1) ok = false;
-                        el[o] = e;
-                        if (het) {
-                            /* the element whose corner o the node is: column (x - ox + 1, y - oy + 1) of layer k - oz + 1 */
-                            const int i = x - (o & 1) + 1, j = y - ((o >> 1) & 1) + 1, l = k - ((o >> 2) & 1) + 1;
-                            const double* q = B.coef.data() + U.coef + (int64_t)l * (3 * HQ_BH_THREADS) + (j * 64 + i);
-                            if (c1[(size_t)e] != q[0] || c2[(size_t)e] != q[HQ_BH_CS] || beta[(size_t)e] != q[2 * HQ_BH_CS]) ok = false;
-                        } else if (c1[(size_t)e] != U.c1 || c2[(size_t)e] != U.c2 || beta[(size_t)e] != U.beta) ok = false;
-                    }
-                    if (!ok) { bad++; continue; }
-                    for (int dz = -1; dz <= 1; dz++)
-                        for (int dy = -1; dy <= 1; dy++)
-                            for (int dx = -1; dx <= 1; dx++) {
-                                if (!dx && !dy && !dz) continue;
-                                /* the neighbour is corner m of the element whose corner o the node is, m - o = d */
-                                const int o = (dx < 0 ? 1 : 0) | (dy < 0 ? 2 : 0) | (dz < 0 ? 4 : 0);
-                                const int m = (dx > 0 ? 1 : 0) | (dy > 0 ? 2 : 0) | (dz > 0 ? 4 : 0);
-                                const int32_t nb_abi = d->lnid[8 * el[o] + m];
-                                if (at(x + dx, y + dy, k + dz) != (int64_t)B.perm[(size_t)nb_abi]) bad++;
-                                nchecked++;
-                            }
-                }
-    }
-    /* face planes (HQ_BK_TOPFACE / BOTFACE): every node of the plane is the corner of exactly FOUR elements, all on the
-     * unit's side, with the unit's coefficients; its n_t row is the one in the unit's record; the kernel finds it in the
-     * cap table and its 17 neighbours where it reads them */
-#pragma omp parallel for schedule(dynamic, 4) reduction(+ : bad, nchecked)
-    for (int64_t u = 0; u < (int64_t)B.units.size(); u++) {
-        const hq_brick_unit& U = B.units[(size_t)u];
-        const int nx = U.nx, ny = U.ny, np = U.np, nr = 2 * (nx + 2) + 2 * ny;
-        if (!(U.flags & (HQ_BK_TOPFACE | HQ_BK_BOTFACE))) continue;
-        if ((U.flags & HQ_BK_HET) || !(U.flags & HQ_BK_NTSAME)) { bad++; continue; }
-        const int32_t* ring = B.tab.data() + U.tab;
-        const int32_t* cap = ring + (int64_t)(np + 2) * nr;
-        auto at = [&](int x, int y, int k) -> int64_t {
-            const bool in = x >= 0 && x < nx && y >= 0 && y < ny;
-            if (in) {
-                if (k >= 0 && k < np) return U.base + ((int64_t)k * ny + y) * nx + x;
-                return cap[(k < 0 ? 0 : nx * ny) + y * nx + x];
-            }
-            const int32_t* r = ring + (int64_t)(k + 1) * nr;
-            if (y == -1) return r[x + 1];
-            if (y == ny) return r[nx + 2 + x + 1];
-            if (x == -1) return r[2 * (nx + 2) + y];
-            return r[2 * (nx + 2) + ny + y];
-        };
-        for (int side = 0; side < 2; side++) {
-            if (!(U.flags & (side ? HQ_BK_BOTFACE : HQ_BK_TOPFACE))) continue;
-            const double* row = side ? U.fb : U.ft;
-            const int kf = side ? np : -1;
-            for (int y = 0; y < ny; y++)
-                for (int x = 0; x < nx; x++) {
-                    const int64_t q = U.base + ((int64_t)(side ? np : -1) * ny + y) * nx + x;
-                    if (q < 0 || q >= B.nb) { bad++; continue; }
-#pragma omp atomic
-                    covered[(size_t)q]++;
-                    if (at(x, y, kf) != q) bad++;
-                    const int32_t n = inv[(size_t)q];
-                    if (n < 0) { bad++; continue; }
-                    if (excl[(size_t)n]) bad++;
-                    if (memcmp(ntab + 7 * (int64_t)n, row, 7 * sizeof(double)) != 0) bad++;
-                    int64_t el[8];
-                    for (int o = 0; o < 8; o++) el[o] = -1;
-                    if (aptr[(size_t)n + 1] - aptr[(size_t)n] != 4) { bad++; continue; }
-                    bool ok = true;
-                    for (int64_t a = aptr[(size_t)n]; a < aptr[(size_t)n + 1]; a++) {
-                        const int64_t e = adj[(size_t)a] >> 3;
-                        const int o = (int)(adj[(size_t)a] & 7);
-                        if (((o >> 2) & 1) != side || el[o] != -1) ok = false;     /* top: the node is the elements' low-z corner */
-                        el[o] = e;
-                        if (c1[(size_t)e] != U.c1 || c2[(size_t)e] != U.c2 || beta[(size_t)e] != U.beta) ok = false;
-                    }
-                    if (!ok) { bad++; continue; }
-                    for (int dz = (side ? -1 : 0); dz <= (side ? 0 : 1); dz++)
-                        for (int dy = -1; dy <= 1; dy++)
-                            for (int dx = -1; dx <= 1; dx++) {
-                                if (!dx && !dy && !dz) continue;
-                                const int o = (dx < 0 ? 1 : 0) | (dy < 0 ? 2 : 0) | (side ? 4 : 0);
-                                const int m = (dx > 0 ? 1 : 0) | (dy > 0 ? 2 : 0) | ((side ? dz == 0 : dz > 0) ? 4 : 0);
-                                const int32_t nb_abi = d->lnid[8 * el[o] + m];
-                                if (at(x + dx, y + dy, kf + dz) != (int64_t)B.perm[(size_t)nb_abi]) bad++;
-                                nchecked++;
-                            }
-                }
-        }
-    }
-    for (int64_t q = 0; q < B.nb; q++) if (covered[(size_t)q] != 1) bad++;
-    /* the patches behind the bricks: planned on the renumbered mesh as hq_create does it -- walking only the elements
-     * of the shell (hq_patch_candidates) -- and once more walking every element: the two plans must be the same, and
-     * every element around a patch node must be in its patch */
-    {
-        std::vector<int32_t> p_lnid((size_t)E * 8), p_xyz((size_t)N * 3);
-        for (int64_t i = 0; i < E * 8; i++) p_lnid[(size_t)i] = B.perm[(size_t)d->lnid[i]];
-        for (int64_t n = 0; n < N; n++)
-            for (int k = 0; k < 3; k++) p_xyz[(size_t)(3 * (int64_t)B.perm[(size_t)n] + k)] = d->node_xyz[3 * n + k];
-        std::vector<char> shared_dn((size_t)N, 0);
-        for (int32_t i = 0; i < d->dn_sched.s_count; i++)
-            for (int32_t k = 0; k < d->dn_sched.first_s[i].nodecount; k++) shared_dn[(size_t)d->dn_sched.first_s[i].mapping[k]] = 1;
-        std::vector<int32_t> l_id, l_ptr(1, 0), l_anc;
-        for (int32_t k = 0; k < d->ldnnum; k++) {
-            if (shared_dn[(size_t)d->dn_ldnid[k]]) continue;
-            l_id.push_back(B.perm[(size_t)d->dn_ldnid[k]]);
-            for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++) l_anc.push_back(B.perm[(size_t)d->dn_lanid[a]]);
-            l_ptr.push_back((int32_t)l_anc.size());
-        }
-        hq_dangling dn;
-        dn.n = (int32_t)l_id.size(); dn.id = l_id.data(); dn.ptr = l_ptr.data(); dn.anchor = l_anc.data();
-        bool want_lattice = false;                   /* (not asked for: behind bricks the shell is planned without) */
-        const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, true, &want_lattice);
-        hq_patch_host Ha, Hb;
-        std::vector<int32_t> all((size_t)E);
-        for (int64_t e = 0; e < E; e++) all[(size_t)e] = (int32_t)e;
-        if (hq_patch_plan_host(opts, cfg, E, N, p_lnid.data(), p_xyz.data(), dn, false, &Ha, B.nb) != 0 ||
-            hq_patch_plan_host(opts, cfg, E, N, p_lnid.data(), p_xyz.data(), dn, false, &Hb, B.nb, &all) != 0)
-            return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
-        if (Ha.pelem != Hb.pelem || Ha.halo != Hb.halo || Ha.pidx != Hb.pidx || Ha.desc.size() != Hb.desc.size() || Ha.ds_ent != Hb.ds_ent) bad++;
-        for (size_t q = 0; q < Ha.desc.size() && q < Hb.desc.size(); q++)
-            if (Ha.desc[q].base != Hb.desc[q].base || Ha.desc[q].nown != Hb.desc[q].nown || Ha.desc[q].npairs != Hb.desc[q].npairs ||
-                Ha.desc[q].nhalo != Hb.desc[q].nhalo || Ha.desc[q].pair_off != Hb.desc[q].pair_off) bad++;
-        /* every (element, patch node) incidence is in the owner's list */
-        std::vector<int32_t> patch_of((size_t)N, -1);
-        for (size_t q = 0; q < Ha.desc.size(); q++)
-            for (int32_t n = Ha.desc[q].base; n < Ha.desc[q].base + Ha.desc[q].nown; n++) patch_of[(size_t)n] = (int32_t)q;
-        for (int64_t n = B.nb; n < N; n++) if (patch_of[(size_t)n] < 0) bad++;
-        int64_t need = 0, have = 0;
-        for (int64_t e = 0; e < E; e++) {
-            int32_t seen[8]; int ns = 0;
-            for (int c8 = 0; c8 < 8; c8++) {
-                const int32_t q = patch_of[(size_t)p_lnid[(size_t)(8 * e + c8)]];
-                bool dup = q < 0;
-                for (int t = 0; t < ns; t++) dup |= seen[t] == q;
-                if (!dup) seen[ns++] = q;
-            }
-            for (int t = 0; t < ns; t++) {
-                need++;
-                const hq_patch_desc& D = Ha.desc[(size_t)seen[t]];
-                have += std::binary_search(Ha.pelem.begin() + D.pair_off, Ha.pelem.begin() + D.pair_off + D.npairs, (int32_t)e);
-            }
-        }
-        if (have != need) bad++;
-    }
-    report[0] = B.nb; report[1] = B.ncolumns; report[2] = (int64_t)B.units.size(); report[3] = nsame;
-    report[4] = B.nhet + B.nrhet; report[5] = nchecked; report[6] = N - B.nb; report[7] = bad;
-    g_brick_check_extra[0] = B.nrag;
-    g_brick_check_extra[1] = 0;
-    g_brick_check_extra[2] = B.nrhet;
-    g_brick_check_extra[3] = 0;
-    for (const hq_brick_unit& U : B.units) {
-        if (!(U.flags & HQ_BK_RAGGED)) continue;
-        const int32_t* pl = B.tab.data() + U.tab + (int64_t)(U.np + 2) * (2 * (U.nx + 2) + 2 * U.ny);
-        for (int64_t i = (int64_t)U.nx * U.ny; i < (int64_t)U.nx * U.ny * (U.np + 1); i++) g_brick_check_extra[(U.flags & HQ_BK_HET) ? 3 : 1] += pl[i] >= 0;
-    }
-    if (bad) return hq_fail(HQ_ERR_STATE, "brick plan self-check failed%s", "");
-    return HQ_OK;
-}
-
-/* the same with a longer report: [8] = ragged units (HQ_BK_RAGGED), [9] = the nodes they own; n = entries the caller has */
-extern "C" int hq_brick_plan_check_n(const hq_desc* d, int64_t* report, int32_t n)
-{
-    int64_t r8[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    if (!report || n < 8) return hq_fail(HQ_ERR_ARG, "hq_brick_plan_check_n: a report of at least 8 entries%s", "");
-    for (int k = 0; k < 4; k++) g_brick_check_extra[k] = 0;
-    const int rc = hq_brick_plan_check(d, r8);
-    for (int k = 0; k < 8; k++) report[k] = r8[k];
-    for (int k = 8; k < n; k++) report[k] = k < 12 ? g_brick_check_extra[k - 8] : 0;
-    return rc;
-}
+#include "hq_plan_check.h"
 
 extern "C" int hq_destroy(hq_ctx* c)
 {

@@ -681,9 +681,10 @@ static hq_patch_cfg hq_patch_cfg_of(const hq_options& o, bool hanging, bool have
     if (c.nlmax < c.pmax + 8) c.nlmax = c.pmax + 8;
     if (c.nlmax > 0x7fff) c.nlmax = 0x7fff;          /* HQ_PIDX_ROW: 15-bit rows in the element row */
     c.vmax = hq_value_or(o.patch_vmax, c.vmax);
-    /* LDS: (6 nlmax + 3 (pmax + vmax)) doubles must fit 160 KiB */
-    while ((6 * (size_t)c.nlmax + 3 * (size_t)(c.pmax + c.vmax)) * 8 > 160 * 1024) c.nlmax -= 8;
     if (hanging && c.vmax == 0) c.vmax = 384;
+    /* LDS: (6 nlmax + 3 (pmax + vmax)) doubles must fit 160 KiB (the hanging nodes' accumulators, where the mesh has
+     * any, count against it too) */
+    while ((6 * (size_t)c.nlmax + 3 * (size_t)(c.pmax + c.vmax)) * 8 > 160 * 1024) c.nlmax -= 8;
     *want_lattice = !hq_set(o.patch_no_lattice) && have_xyz && c.pmax >= HQ_LAT_ACC;
     return c;
 }
@@ -2188,8 +2189,6 @@ static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int6
     P->n0 = n0;
     bool want_lattice = false;
     P->cfg = hq_patch_cfg_of(o, dn.n > 0, xyz != nullptr, &want_lattice);
-    /* (the hanging nodes' accumulators, where the mesh has any, count against the LDS too) */
-    while ((6 * (size_t)P->cfg.nlmax + 3 * (size_t)(P->cfg.pmax + P->cfg.vmax)) * 8 > 160 * 1024) P->cfg.nlmax -= 8;
     /* 6 (default) = hq_k_patch_seed where the plan fits it (else hq_k_patch_pers, else hq_k_patch_step), 4 = hq_k_patch_pers
      * where it fits, 0 = hq_k_patch_step always */
     P->pipe = hq_value_or(o.patch_pipe, 6);

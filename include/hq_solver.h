@@ -474,8 +474,10 @@ HQ_API int hq_download_force(hq_ctx* ctx, double* force);
 HQ_API int hq_run_timed(hq_ctx* ctx, int32_t nsteps, double* total_ms, double* kernel_ms_avg);
 
 /*
- * Host-only self-check of the patch planner (needs no device): plans `desc` as hq_create would and
- * verifies the element rows, accumulate flags and node coverage of every patch.
+ * Host-only self-check of the patch planner (needs no device; eTable / nTable are not read): refuses a description
+ * hq_create refuses, plans `desc` WITHOUT bricks -- every node a patch node, hq_create's plan under
+ * hq_options.no_bricks or without node_xyz -- and verifies the element rows, accumulate flags and node coverage of
+ * every patch.
  * report = {patches, lattice patches, (patch, element) pairs, distinct element-row blocks,
  *           LDS passes of the gathers, gather instructions (per 32-lane group), gather passes of the
  *           lattice patches (23 groups x 8 corners each when free of bank conflicts), faults}.
@@ -483,7 +485,8 @@ HQ_API int hq_run_timed(hq_ctx* ctx, int32_t nsteps, double* total_ms, double* k
 HQ_API int hq_plan_check(const hq_desc* desc, int64_t report[8]);
 
 /*
- * Host-only self-check of what hq_k_patch_stencil reads (needs no device; desc->node_xyz required): every patch-shape
+ * Host-only self-check of what hq_k_patch_stencil reads (needs no device; desc->node_xyz required, eTable / nTable are
+ * not read), on the plan WITHOUT bricks that hq_plan_check checks: every patch-shape
  * table (lattice rows, element masks, boundary lists) against the mesh's connectivity, and the element-matrix blocks
  * of the boundary phase against the kernels' own element arithmetic.
  * report = {patches, patches with a table, full lattices among them, boundary nodes, element corners checked, faults}.
@@ -493,7 +496,8 @@ HQ_API int hq_stencil_plan_check(const hq_desc* desc, int64_t report[6]);
 /*
  * Host-only self-check of the brick planner (needs no device; desc->node_xyz required): plans the bricks -- the bulk
  * of uniformly refined, homogeneous regions, stepped by hq_k_brick on a tile-major node numbering of the device's own
- * -- as hq_create would and verifies them against the mesh's connectivity alone: permutation, coverage, the eight
+ * -- with hq_create's own host half (it refuses what hq_create refuses) and verifies them, and the patches planned
+ * behind them on the renumbered description, against the mesh's connectivity alone: permutation, coverage, the eight
  * equal elements and the dashpot-free n_t row of every brick node, and every neighbour the kernel will read.
  * report = {brick nodes, tile columns, units, units with one n_t row, units with per-element coefficients
  *           (hq_k_brick_het), neighbours checked, patch nodes, faults}.

@@ -258,3 +258,33 @@ def test_two_materials_in_one_tile_footprint_against_the_oracle():
         s.close()
         assert H.rel_linf(tm1, o2) < 1e-9 and H.rel_linf(tm2, o1) < 1e-9
     box.close()
+
+
+def _three_descriptions():
+    import bench
+    from hercules_amd import host
+    yield "uniform", host.Box(32, 32, 32, 12.5, 2e-4, 50.0)
+    yield "lateral", host.Box(32, 32, 32, 12.5, 2e-4, 50.0, lateral_classes=61, lateral_amp=0.1)
+    yield "o4s", bench.make_octbox("o4s", 0, 1)[0]
+
+
+def test_the_brick_plan_check_reports_the_plan_a_context_runs():
+    """hq_brick_plan_check and hq_create begin with the same host half (hq_prepare): what the check reports of the bricks
+    is what hq_get_info says of a context created from the same description -- a uniform box, per-element material (HET
+    units), the laterally refined basin (ragged units).  (The patch-side counters are left out: hq_patch_build may plan
+    again without lattices, for reasons of the device's kernels.)"""
+    pairs = (("brick_nodes", "brick_nodes"), ("units", "brick_units"), ("het_units", "brick_units_het"),
+             ("ragged_units", "brick_units_ragged"), ("ragged_het_units", "brick_units_ragged_het"))
+    seen = {k: 0 for k, _ in pairs}
+    for name, box in _three_descriptions():
+        rep = box.brick_plan_check()
+        s = box.create_solver(variant=ha.HQ_VARIANT_PATCH)
+        info = s.info()
+        s.close()
+        box.close()
+        assert rep["faults"] == 0
+        for r, i in pairs:
+            assert rep[r] == info[i], (name, r, rep[r], i, info[i])
+            seen[r] += rep[r]
+    # the comparison is not of zeros: the three carry full, HET and ragged units (none of them ragged HET ones)
+    assert all(seen[k] > 0 for k in ("brick_nodes", "units", "het_units", "ragged_units")), seen

@@ -1,9 +1,10 @@
-"""The patch planner of libhq_solver.so is host code: hq_plan_check plans a mesh exactly as hq_create
-would and checks the plan against the mesh WITHOUT a device (no compute, nothing stepped):
+"""The patch planner of libhq_solver.so is host code: hq_plan_check plans a mesh as hq_create does where
+it has no bricks and checks the plan against the mesh WITHOUT a device (no compute, nothing stepped):
 every element row names the LDS rows of its element's eight nodes, accumulate flags = owned nodes +
 hanging nodes on owned anchors, every node owned by exactly one patch.  It also counts the LDS passes
 of the element gathers under the bank rule of MI355X_MICROARCH.md (32-lane groups, 24-byte rows
 conflict iff equal modulo 32): lattice patches must be free of conflicts."""
+import ctypes
 import os
 
 import numpy as np
@@ -270,3 +271,109 @@ def test_ragged_per_element_columns_of_the_small_gradient_basin():
     box.close()
     assert rep["faults"] == 0 and rep["units_one_nt_row"] == 0
     assert rep["ragged_het_units"] > 100 and rep["ragged_het_nodes"] > 350000 and rep["patch_nodes"] < 0.2 * N
+
+
+# ---- the checks begin with hq_create's own host half (hq_prepare): they refuse what it refuses, on every description ----
+
+HQ_ERR_ARG = -1
+_CHECKS = ("plan_check", "stencil_plan_check", "brick_plan_check")
+
+
+def _desc_of(box):
+    from hercules_amd import capi
+    d = capi._Desc()
+    fill = getattr(box._lib, "hqh_octbox_desc" if isinstance(box, host.OctBox) else "hqh_box_desc")
+    assert fill(box._h, ctypes.byref(d)) == 0
+    return d
+
+
+def _refused(check, d, message):
+    """`check` raises what capi._check raises for HQ_ERR_ARG, with hq_create's message."""
+    from hercules_amd import capi
+    with pytest.raises(capi.HqError) as e:
+        getattr(capi, check)(d)
+    assert str(e.value).startswith("hq error %d: " % HQ_ERR_ARG) and message in str(e.value), str(e.value)
+
+
+@pytest.mark.parametrize("rank, side", [(1, "s"), (0, "c")])
+def test_the_checks_refuse_a_messenger_id_out_of_range(rank, side):
+    """Box(16, 16, 16) cut in two: the smallest box with bricks and a partition interface.  The interface plane belongs to
+    rank 1, so an_sched's s-list (first_s[0]) is rank 1's and rank 0 has the c-list: both are tried.  One mapping entry
+    = nharbored: every check refuses it as hq_create does (the patch checks used to index a vector with it)."""
+    from hercules_amd import capi
+    b = host.Box(16, 16, 16, 10.0, 2e-4, 50.0, rank=rank, nranks=2)
+    d = _desc_of(b)
+    assert capi.brick_plan_check(d)["brick_nodes"] > 0
+    count, first = (d.an_sched.s_count, d.an_sched.first_s) if side == "s" else (d.an_sched.c_count, d.an_sched.first_c)
+    assert count == 1 and first[0].nodecount > 0
+    mapping = np.ctypeslib.as_array(ctypes.cast(first[0].mapping, ctypes.POINTER(ctypes.c_int32)), (first[0].nodecount,)).copy()
+    msg = (capi._Messenger * 1)()
+    msg[0].procid, msg[0].nodecount, msg[0].mapping = first[0].procid, first[0].nodecount, mapping.ctypes.data
+    setattr(d.an_sched, "first_" + side, msg)
+    good = {k: getattr(capi, k)(d) for k in _CHECKS}              # the copy as it came: nothing refused
+    mapping[len(mapping) // 2] = d.nharbored
+    for k in _CHECKS:
+        _refused(k, d, "messenger node id out of range")
+    mapping[len(mapping) // 2] = -1
+    for k in _CHECKS:
+        _refused(k, d, "messenger node id out of range")
+    d = _desc_of(b)                                             # the mapping restored: the reports of the copy
+    assert {k: getattr(capi, k)(d) for k in _CHECKS} == good
+    # an eTable that is not Rayleigh-proportional (c4 doubled on one element): the check that plans with it refuses it
+    et = b.etable.copy()
+    et[len(et) // 3, 3] *= 2.0
+    assert et[len(et) // 3, 3] != 0.0
+    d.eTable = capi._ptr(et)
+    _refused("brick_plan_check", d, "eTable is not Rayleigh-proportional (c3/c1 != c4/c2): not the table solver_init builds")
+    b.close()
+
+
+def test_the_checks_refuse_an_anchor_that_is_itself_a_hanging_node():
+    import bench
+    box = bench.make_octbox("o3s", 0, 1)[0]
+    d = _desc_of(box)
+    ids, ptr, anchors = box.dangling
+    anc = anchors.copy()
+    anc[len(anc) // 2] = ids[0]
+    d.dn_lanid = anc.ctypes.data
+    for k in _CHECKS:
+        _refused(k, d, "an anchor is itself a hanging node")
+    box.close()
+
+
+def test_the_two_brick_reports_agree():
+    """hq_brick_plan_check's eight entries are the first eight of hq_brick_plan_check_n's twelve (one implementation, no
+    state between calls): on o4s (ragged units), then the longer report of a uniform box names no ragged unit."""
+    import bench
+    from hercules_amd import capi
+    lib = capi.load_library()
+    box = bench.make_octbox("o4s", 0, 1)[0]
+    d = _desc_of(box)
+    r8, r12 = (ctypes.c_int64 * 8)(), (ctypes.c_int64 * 12)()
+    capi._check(lib.hq_brick_plan_check(ctypes.byref(d), r8))
+    capi._check(lib.hq_brick_plan_check_n(ctypes.byref(d), r12, ctypes.c_int32(12)))
+    box.close()
+    assert list(r8) == list(r12)[:8] and r12[8] > 0 and r12[9] > 0
+    b = host.Box(16, 16, 16, 10.0, 2e-4, 50.0)
+    d = _desc_of(b)
+    r16 = (ctypes.c_int64 * 16)(*([-7] * 16))
+    capi._check(lib.hq_brick_plan_check_n(ctypes.byref(d), r16, ctypes.c_int32(16)))
+    b.close()
+    rep = dict(zip(capi.BRICK_PLAN_REPORT, list(r16)))
+    assert rep["brick_nodes"] > 0 and rep["faults"] == 0
+    assert rep["ragged_units"] == rep["ragged_nodes"] == rep["ragged_het_units"] == rep["ragged_het_nodes"] == 0
+    assert list(r16)[12:] == [0, 0, 0, 0]
+
+
+def test_plan_check_needs_no_element_or_node_tables():
+    """hq_plan_check reads the connectivity and the coordinates alone: a description without eTable / nTable is planned
+    like the one with them."""
+    from hercules_amd import capi
+    b = host.Box(16, 16, 16, 10.0, 2e-4, 50.0, rank=0, nranks=2)
+    d = _desc_of(b)
+    full = capi.plan_check(d)
+    d.eTable = d.nTable = None
+    assert d.node_xyz
+    bare = capi.plan_check(d)
+    b.close()
+    assert bare == full and full["faults"] == 0 and full["patches"] > 0
