@@ -21,7 +21,9 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_run_timed", "hq_dominant_kernel", "hq_plan_check", "hq_stencil_plan_check", "hq_check_finite",
            "hq_stencil_coefficients", "hq_brick_plan_check", "hq_brick_plan_check_n", "hq_comm_init_host",
            "hq_comm_ipc_export", "hq_comm_init_ipc", "hq_comm_init_loopback",
-           "hq_record_add", "hq_record_pending", "hq_record_fetch", "hq_record_clear"]
+           "hq_record_add", "hq_record_pending", "hq_record_fetch", "hq_record_clear",
+           "hq_snapshot_add", "hq_snapshot_pending", "hq_snapshot_fetch", "hq_snapshot_clear"]
+HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
 
 
 class HqError(RuntimeError):
@@ -61,6 +63,11 @@ class _Desc(ctypes.Structure):
 class _RecorderDesc(ctypes.Structure):
     _fields_ = [("npoints", ctypes.c_int32), ("ids", ctypes.c_void_p), ("phi", ctypes.c_void_p),
                 ("rate", ctypes.c_int32), ("derivs", ctypes.c_int32), ("capacity", ctypes.c_int32)]
+
+
+class _SnapshotDesc(ctypes.Structure):
+    _fields_ = [("first", ctypes.c_int32), ("count", ctypes.c_int32), ("rate", ctypes.c_int32),
+                ("first_step", ctypes.c_int32), ("fields", ctypes.c_int32), ("slots", ctypes.c_int32)]
 
 
 class _Info(ctypes.Structure):
@@ -391,6 +398,48 @@ class Solver:
         """hq_record_clear: drop every recorder of the context and its device memory."""
         _check(self._lib.hq_record_clear(self._h), self._lib)
         self._recorders = {}
+
+    def snapshot_add(self, first=0, count=None, rate=1, first_step=0, fields=HQ_SNAP_TM1, slots=1):
+        """hq_snapshot_add: a field snapshot of the nodes [first, first + count) (None: up to the last node) at the head
+        of every step s >= first_step with s % rate == 0; `fields` a mask of HQ_SNAP_TM1 | TM2 | VEL, `slots` snapshots
+        may be pending at once.  Returns its handle."""
+        count = self.N - int(first) if count is None else int(count)
+        d = _SnapshotDesc(int(first), count, int(rate), int(first_step), int(fields), int(slots))
+        h = ctypes.c_int32(-1)
+        _check(self._lib.hq_snapshot_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
+        if not hasattr(self, "_snapshots"):
+            self._snapshots = {}
+        self._snapshots[h.value] = (count, int(fields))
+        return h.value
+
+    def snapshot_pending(self, handle):
+        """hq_snapshot_pending: (snapshots taken or enqueued and not yet fetched, those of them that have arrived in host
+        memory, step of the oldest or -1).  Waits for nothing."""
+        n, ready, first = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _check(self._lib.hq_snapshot_pending(self._h, ctypes.c_int32(handle), ctypes.byref(n), ctypes.byref(ready),
+                                             ctypes.byref(first)), self._lib)
+        return n.value, ready.value, first.value
+
+    def snapshot_fetch(self, handle):
+        """hq_snapshot_fetch: (step, tm1, tm2, vel) of the OLDEST pending snapshot -- tm1, tm2 [count, 3] in the solver's
+        precision, vel [count, 3] float64, None for a field the snapshot lacks; (-1, None, None, None) if nothing is
+        pending.  Waits for that snapshot's copy only, not for the steps enqueued behind it."""
+        self.snapshot_pending(handle)                           # (raises on an unknown handle)
+        count, fields = self._snapshots[handle]
+        tm1 = np.empty((count, 3), self.real) if fields & HQ_SNAP_TM1 else None
+        tm2 = np.empty((count, 3), self.real) if fields & HQ_SNAP_TM2 else None
+        vel = np.empty((count, 3), np.float64) if fields & HQ_SNAP_VEL else None
+        step = ctypes.c_int32(-1)
+        _check(self._lib.hq_snapshot_fetch(self._h, ctypes.c_int32(handle), _ptr(tm1), _ptr(tm2), _ptr(vel),
+                                           ctypes.byref(step)), self._lib)
+        if step.value < 0:
+            return -1, None, None, None
+        return step.value, tm1, tm2, vel
+
+    def snapshot_clear(self):
+        """hq_snapshot_clear: wait, then drop every snapshot of the context and its memory."""
+        _check(self._lib.hq_snapshot_clear(self._h), self._lib)
+        self._snapshots = {}
 
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)

@@ -271,6 +271,27 @@ struct hq_ctx {
     std::vector<hq_recorder> recs;
     int32_t rec_next_id = 0;
     hipEvent_t ev_recorded = nullptr;
+    /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
+     * pinned host memory, accounted on the host as the recorders' rings are.  A slot holds the fields one behind the other,
+     * each at a 256-byte boundary (off[]; the same layout on both sides, so one copy carries a slot).  sstream, the copy
+     * stream, and ev_snapped exist from the first hq_snapshot_add on: behind each hq_k_snapshot launch the event is
+     * recorded on the compute stream and waited for by sstream, which copies the slot and records the slot's done event */
+    struct hq_snapshot {
+        int32_t id = 0, first = 0, count = 0, rate = 1, first_step = 0, fields = 0, slots = 0;
+        int32_t* d_map = nullptr;     /* [count] device id of node first + i; NULL on contexts without a renumbering */
+        char* d_stage = nullptr;      /* [slots][slot_bytes] */
+        char* h_stage = nullptr;      /* the same, pinned host memory */
+        size_t off[3] = { 0, 0, 0 };  /* tm1, tm2, vel inside a slot */
+        size_t slot_bytes = 0;
+        int32_t head = 0, npending = 0;
+        std::vector<int32_t> steps;   /* [slots] step number of the snapshot in each slot */
+        std::vector<hipEvent_t> done; /* [slots] the slot's copy has arrived */
+        int64_t bytes = 0;            /* device memory of this snapshot (part of `bytes`) */
+    };
+    std::vector<hq_snapshot> snaps;
+    int32_t snap_next_id = 0;
+    hipStream_t sstream = nullptr;
+    hipEvent_t ev_snapped = nullptr;
     /* timing */
     std::vector<hipEvent_t> ev;     /* per-launch marks */
     hipEvent_t ev_span[2] = { nullptr, nullptr };
@@ -675,6 +696,95 @@ hq_k_record(int32_t np, const int32_t* __restrict__ ids, const double* __restric
                 d[a] = d[a] + w[c] * (double)u3[row[c] + a];
             }
         for (int a = 0; a < 3; a++) o[6 + a] = d[a] / dt2;
+    }
+}
+
+/*
+ * One field snapshot (hq_snapshot_add): the rows [first, first + count) of u1 = u(t), u2 = u(t - dt) out of the device's
+ * numbering into a staging slot in the caller's (octor) order -- hq_field_to_host's un-permutation, done at HBM speed
+ * ahead of the copy instead of on the host behind it.  A streaming permutation: per node 4 bytes of map, 24-48 bytes of
+ * state read, 24-72 written; no arithmetic but the velocity's, (double)u1 - (double)u2 over dt, contraction off
+ * (hqh_wavefield_write's write_velocity, bit for bit).
+ * The OUTPUT is what the lanes are laid over: the slot's fields are flat arrays of 3 count scalars, and a lane owns V =
+ * 16 / sizeof(T) consecutive ones (2 doubles, 4 floats -- they may straddle two rows), so every store is a 16-byte store
+ * and a wave's stores cover 1 KiB of consecutive output rows.  The reads are gathers of single scalars, lane by lane: the
+ * three lanes (or one and a half) of a row read its 24 (12) bytes side by side, and wherever the map runs on -- inside a
+ * brick's tile the x-neighbours of the octor order are neighbours on the device too, 64 at a time, and on contexts without
+ * a renumbering everywhere -- consecutive lanes read consecutive addresses and the wave's loads merge into whole lines
+ * like those of a plain copy.  Where the map jumps, the other rows of the lines it touches are read by the same workgroup
+ * (a tile of 256 V consecutive octor rows is a compact cube of the mesh) and come out of L2.
+ * A workgroup takes tiles of 256 V rows = 768 lane groups, three per thread (independent: their loads are in flight
+ * together); 256 V rows are a multiple of 16 bytes in every field, so each group's stores are aligned.  map == NULL: the
+ * device numbers the nodes as the caller does.  o1 / o2 / ov == NULL: that field is not wanted.
+ */
+template <typename T>
+__global__ void __launch_bounds__(256)
+hq_k_snapshot(int32_t first, int32_t count, const int32_t* __restrict__ map, const T* __restrict__ u1,
+              const T* __restrict__ u2, double dt, T* __restrict__ o1, T* __restrict__ o2, double* __restrict__ ov)
+{
+#pragma clang fp contract(off)
+    constexpr int V = 16 / (int)sizeof(T);
+    constexpr int32_t TR = 256 * V;                              /* rows per tile */
+    typedef T vecT __attribute__((ext_vector_type(V)));         /* 16 bytes: one global_store_dwordx4 */
+    typedef double vecD __attribute__((ext_vector_type(2)));
+    const int32_t ntiles = (count + TR - 1) / TR;
+    const bool want1 = o1 != nullptr || ov != nullptr, want2 = o2 != nullptr || ov != nullptr;
+    for (int32_t tile = (int32_t)blockIdx.x; tile < ntiles; tile += (int32_t)gridDim.x) {
+        const int32_t row0 = tile * TR;
+        const int32_t nscal = 3 * min(TR, count - row0);         /* scalars of this tile */
+        const int64_t base = 3 * (int64_t)row0;
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            const int32_t j0 = ((int32_t)threadIdx.x + 256 * m) * V;
+            if (j0 >= nscal) continue;
+            T a[V], b[V];
+#pragma unroll
+            for (int k = 0; k < V; k++) {
+                const int32_t j = min(j0 + k, nscal - 1);        /* (a lane group past the end re-reads the last scalar) */
+                const int32_t n = j / 3;
+                const int64_t row = map ? (int64_t)map[row0 + n] : (int64_t)first + row0 + n;
+                const int64_t src = 3 * row + (j - 3 * n);
+                a[k] = want1 ? u1[src] : (T)0;
+                b[k] = want2 ? u2[src] : (T)0;
+            }
+            const bool whole = j0 + V <= nscal;
+            if (o1) {
+                if (whole) {
+                    vecT w;
+#pragma unroll
+                    for (int k = 0; k < V; k++) w[k] = a[k];
+                    *(vecT*)(o1 + base + j0) = w;
+                }
+                else {
+#pragma unroll
+                    for (int k = 0; k < V; k++) if (j0 + k < nscal) o1[base + j0 + k] = a[k];
+                }
+            }
+            if (o2) {
+                if (whole) {
+                    vecT w;
+#pragma unroll
+                    for (int k = 0; k < V; k++) w[k] = b[k];
+                    *(vecT*)(o2 + base + j0) = w;
+                }
+                else {
+#pragma unroll
+                    for (int k = 0; k < V; k++) if (j0 + k < nscal) o2[base + j0 + k] = b[k];
+                }
+            }
+            if (ov) {
+                double v[V];
+#pragma unroll
+                for (int k = 0; k < V; k++) v[k] = ((double)a[k] - (double)b[k]) / dt;
+                if (whole) {
+#pragma unroll
+                    for (int k = 0; k < V; k += 2) { vecD w = { v[k], v[k + 1] }; *(vecD*)(ov + base + j0 + k) = w; }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < V; k++) if (j0 + k < nscal) ov[base + j0 + k] = v[k];
+                }
+            }
+        }
     }
 }
 
@@ -1264,6 +1374,81 @@ static int hq_record_enqueue(hq_ctx* c, bool brick_stream)
     return HQ_OK;
 }
 
+/* ---- field snapshots ---- */
+
+static inline bool hq_snapshot_due(const hq_ctx::hq_snapshot& sn, int64_t step) { return step >= sn.first_step && step % sn.rate == 0; }
+
+/* would the due steps of [c->step, c->step + nsteps) need more slots than are free?  Decided before anything is enqueued */
+static int hq_snapshot_check_room(const hq_ctx* c, int32_t nsteps)
+{
+    for (const auto& sn : c->snaps) {
+        int64_t due = 0;
+        for (int32_t s = 0; s < nsteps; s++) due += hq_snapshot_due(sn, (int64_t)c->step + s);
+        if (sn.npending + due > sn.slots)
+            return hq_fail(HQ_ERR_STATE, "a snapshot's slots would run out: fetch the pending ones first (hq_snapshot_fetch)%s", "");
+    }
+    return HQ_OK;
+}
+
+/* the recorders' rings and the snapshots' slots: what hq_run, hq_group_run and hq_run_timed ask before they enqueue */
+static int hq_output_check_room(const hq_ctx* c, int32_t nsteps)
+{
+    HQ_TRY(hq_record_check_room(c, nsteps));
+    return hq_snapshot_check_room(c, nsteps);
+}
+
+/* free every snapshot (the caller has waited for the streams, the copy stream included) */
+static void hq_snapshot_drop_all(hq_ctx* c)
+{
+    for (auto& sn : c->snaps) {
+        if (sn.d_map) hipFree(sn.d_map);
+        if (sn.d_stage) hipFree(sn.d_stage);
+        if (sn.h_stage) hipHostFree(sn.h_stage);
+        for (hipEvent_t e : sn.done) if (e) hipEventDestroy(e);
+        c->bytes -= sn.bytes;
+    }
+    c->snaps.clear();
+    if (c->ev_snapped) { hipEventDestroy(c->ev_snapped); c->ev_snapped = nullptr; }
+    if (c->sstream) { hipStreamDestroy(c->sstream); c->sstream = nullptr; }
+}
+
+/* head of a step, where hq_record_enqueue sits and behind the same waits: one hq_k_snapshot launch per due snapshot on the
+ * compute stream into the next free slot; the copy stream waits for it, carries the slot to its pinned mirror and records
+ * the slot's done event.  The launch reads d_u[now] and d_u[prev], which this step only reads; the next step overwrites
+ * d_u[prev], and its kernels follow this launch on the compute stream or wait for events recorded behind it.  The bricks'
+ * and the exchange chain's streams are held back behind the launch all the same, as they are behind hq_k_record: the
+ * launch then has the memory system to itself and its time is the whole of what a snapshot adds to its step. */
+static int hq_snapshot_enqueue(hq_ctx* c, bool brick_stream)
+{
+    bool any = false;
+    for (auto& sn : c->snaps) {
+        if (!hq_snapshot_due(sn, c->step)) continue;
+        if (sn.npending >= sn.slots) return hq_fail(HQ_ERR_STATE, "a snapshot's slots are all pending%s", "");   /* (hq_snapshot_check_room saw to it) */
+        const int32_t slot = (sn.head + sn.npending) % sn.slots;
+        sn.steps[(size_t)slot] = c->step;
+        sn.npending++;
+        char* d = sn.d_stage + (size_t)slot * sn.slot_bytes;
+        constexpr int32_t tile_rows = 256 * (16 / (int32_t)sizeof(hq_real));
+        const int64_t ntiles = ((int64_t)sn.count + tile_rows - 1) / tile_rows;
+        hq_k_snapshot<hq_real><<<(unsigned)std::min<int64_t>(ntiles, 8192), 256, 0, c->stream>>>(
+            sn.first, sn.count, sn.d_map, c->d_u[c->now], c->d_u[c->prev], c->dt,
+            (sn.fields & HQ_SNAP_TM1) ? (hq_real*)(d + sn.off[0]) : nullptr,
+            (sn.fields & HQ_SNAP_TM2) ? (hq_real*)(d + sn.off[1]) : nullptr,
+            (sn.fields & HQ_SNAP_VEL) ? (double*)(d + sn.off[2]) : nullptr);
+        HQ_HIP(hipEventRecord(c->ev_snapped, c->stream));
+        HQ_HIP(hipStreamWaitEvent(c->sstream, c->ev_snapped, 0));
+        HQ_HIP(hipMemcpyAsync(sn.h_stage + (size_t)slot * sn.slot_bytes, d, sn.slot_bytes, hipMemcpyDeviceToHost, c->sstream));
+        HQ_HIP(hipEventRecord(sn.done[(size_t)slot], c->sstream));
+        c->d2h_bytes += (int64_t)sn.slot_bytes;
+        any = true;
+    }
+    if (any && c->variant == HQ_VARIANT_PATCH) {                 /* (ev_snapped names the last launch's record) */
+        if (brick_stream && c->bstream) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_snapped, 0));
+        if (c->overlap && c->cstream) HQ_HIP(hipStreamWaitEvent(c->cstream, c->ev_snapped, 0));
+    }
+    return HQ_OK;
+}
+
 static int hq_phase(hq_ctx* c, int ph)
 {
     const bool patch = (c->variant == HQ_VARIANT_PATCH);
@@ -1292,6 +1477,7 @@ static int hq_phase(hq_ctx* c, int ph)
                 if (c->ev_shared) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_shared, 0));
                 HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_patches, 0));
             }
+            if (!c->snaps.empty()) HQ_TRY(hq_snapshot_enqueue(c, bs));     /* solver_write_checkpoint / _output_wavefield, :4277-4278 */
             if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, bs));        /* solver_output_planes / _stations, :4279-4280 */
             auto launch_bricks = [&]() {
                 if (c->bricks.nunits > 0)
@@ -1355,6 +1541,7 @@ static int hq_phase(hq_ctx* c, int ph)
              *  kernel time from the phase clock's events instead, and a timed batch enqueues exactly what hq_run does) */
             hq_mark(c);
         } else {
+            if (!c->snaps.empty()) HQ_TRY(hq_snapshot_enqueue(c, false));
             if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, false));
             HQ_TRY(hq_launch_source(c));                                   /* :4288 */
             HQ_TRY(hq_launch_element_scatter(c));                          /* :4290-4291 */
@@ -1877,6 +2064,7 @@ extern "C" int hq_destroy(hq_ctx* c)
     if (!c) return HQ_OK;
     hipSetDevice(c->device);
     if (c->stream) hq_quiesce(c);
+    if (c->sstream) hipStreamSynchronize(c->sstream);
     if (c->comm && g_rccl.handle) g_rccl.CommDestroy(c->comm);
     if (c->ipc) {
         hq_ipc_state* I = c->ipc;
@@ -1902,6 +2090,7 @@ extern "C" int hq_destroy(hq_ctx* c)
                      c->dn.d_c_out_id, c->dn.d_c_in_id, c->dn.d_s_out_id, c->dn.d_s_in_id };
     for (void* p : ptrs) if (p) hipFree(p);
     hq_record_drop_all(c);
+    hq_snapshot_drop_all(c);
     if (c->an.d_cmap_f && c->an.d_cmap_f != c->an.d_cmap) hipFree(c->an.d_cmap_f);
     if (c->an.d_smap_f && c->an.d_smap_f != c->an.d_smap) hipFree(c->an.d_smap_f);
     if (c->dn.d_cmap_f && c->dn.d_cmap_f != c->dn.d_cmap) hipFree(c->dn.d_cmap_f);
@@ -2441,7 +2630,7 @@ extern "C" int hq_group_run(hq_ctx** ctxs, int32_t n, int32_t nsteps)
      * buffers, so a group steps complete or not at all */
     for (hq_ctx* m : *ctxs[0]->group)
         if (!m) return hq_fail(HQ_ERR_STATE, "a member of the group has been destroyed: the others cannot step any more%s", "");
-    for (int32_t i = 0; i < n; i++) HQ_TRY(hq_record_check_room(ctxs[i], nsteps));
+    for (int32_t i = 0; i < n; i++) HQ_TRY(hq_output_check_room(ctxs[i], nsteps));
     for (int32_t s = 0; s < nsteps; s++)
         for (int ph = 0; ph < HQ_NPHASE; ph++)
             for (int32_t i = 0; i < n; i++) {
@@ -2506,7 +2695,7 @@ extern "C" int hq_run(hq_ctx* c, int32_t nsteps)
     if (!c || nsteps < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
     if (c->group && c->group->size() > 1)
         return hq_fail(HQ_ERR_STATE, "linked contexts are stepped with hq_group_run%s", "");
-    HQ_TRY(hq_record_check_room(c, nsteps));
+    HQ_TRY(hq_output_check_room(c, nsteps));
     HQ_HIP(hipSetDevice(c->device));
     for (int32_t s = 0; s < nsteps; s++) HQ_TRY(hq_step(c));
     HQ_HIP(hipGetLastError());
@@ -2518,6 +2707,7 @@ extern "C" int hq_sync(hq_ctx* c)
     if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
+    if (c->sstream) HQ_HIP(hipStreamSynchronize(c->sstream));     /* the snapshots' copies */
     hq_clock_harvest_all(c, true);
     if (c->ipc) {
         int32_t late = 0;
@@ -2569,7 +2759,7 @@ extern "C" int hq_check_finite(hq_ctx* c, int64_t* nonfinite)
 extern "C" int hq_run_timed(hq_ctx* c, int32_t nsteps, double* total_ms, double* kernel_ms_avg)
 {
     if (!c || nsteps <= 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
-    HQ_TRY(hq_record_check_room(c, nsteps));
+    HQ_TRY(hq_output_check_room(c, nsteps));
     HQ_HIP(hipSetDevice(c->device));
     size_t need = 2 * (size_t)nsteps;
     while (c->ev.size() < need) {
@@ -2788,6 +2978,133 @@ extern "C" int hq_record_clear(hq_ctx* c)
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
     hq_record_drop_all(c);
+    return HQ_OK;
+}
+
+/* ---- field snapshots: entry points (include/hq_solver.h) ---- */
+
+static hq_ctx::hq_snapshot* hq_snapshot_find(hq_ctx* c, int32_t handle)
+{
+    for (auto& sn : c->snaps)
+        if (sn.id == handle) return &sn;
+    return nullptr;
+}
+
+extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const int32_t all = HQ_SNAP_TM1 | HQ_SNAP_TM2 | HQ_SNAP_VEL;
+    if (d->count < 1 || d->first < 0 || (int64_t)d->first + d->count > c->N || d->rate < 1 || d->slots < 1 ||
+        d->fields == 0 || (d->fields & ~all) != 0)
+        return hq_fail(HQ_ERR_ARG, "bad snapshot description%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    hq_ctx::hq_snapshot sn;
+    sn.first = d->first; sn.count = d->count; sn.rate = d->rate; sn.first_step = d->first_step; sn.fields = d->fields;
+    sn.slots = d->slots;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t n3 = 3 * (size_t)d->count;
+    size_t at = 0;
+    sn.off[0] = at; if (d->fields & HQ_SNAP_TM1) at += pad(sizeof(hq_real) * n3);
+    sn.off[1] = at; if (d->fields & HQ_SNAP_TM2) at += pad(sizeof(hq_real) * n3);
+    sn.off[2] = at; if (d->fields & HQ_SNAP_VEL) at += pad(sizeof(double) * n3);
+    sn.slot_bytes = at;
+    const int64_t bytes0 = c->bytes;
+    const bool had_stream = c->sstream != nullptr, had_event = c->ev_snapped != nullptr;
+    int rc = hq_dev_alloc(c, &sn.d_stage, sn.slot_bytes * (size_t)d->slots);
+    if (rc == HQ_OK && !c->perm.empty()) rc = hq_dev_alloc(c, &sn.d_map, (size_t)d->count);
+    if (rc == HQ_OK && hipHostMalloc((void**)&sn.h_stage, sn.slot_bytes * (size_t)d->slots, hipHostMallocDefault) != hipSuccess) {
+        sn.h_stage = nullptr;
+        rc = hq_fail(HQ_ERR_NOMEM, "hipHostMalloc failed for the snapshot's pinned buffers%s", "");
+    }
+    hipError_t e = hipSuccess;
+    if (rc == HQ_OK && !c->sstream) e = hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking);
+    if (rc == HQ_OK && e == hipSuccess && !c->ev_snapped) e = hipEventCreateWithFlags(&c->ev_snapped, hipEventDisableTiming);
+    sn.done.assign((size_t)d->slots, nullptr);
+    for (int32_t k = 0; k < d->slots && rc == HQ_OK && e == hipSuccess; k++)
+        e = hipEventCreateWithFlags(&sn.done[(size_t)k], hipEventDisableTiming);
+    if (rc == HQ_OK && e == hipSuccess && sn.d_map) {            /* perm[first .. first + count): the caller's id -> the device's */
+        e = hipMemcpy(sn.d_map, c->perm.data() + d->first, sizeof(int32_t) * (size_t)d->count, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  /* the steps read the map on other streams */
+    }
+    if (rc != HQ_OK || e != hipSuccess) {
+        if (sn.d_stage) hipFree(sn.d_stage);
+        if (sn.d_map) hipFree(sn.d_map);
+        if (sn.h_stage) hipHostFree(sn.h_stage);
+        for (hipEvent_t ev : sn.done) if (ev) hipEventDestroy(ev);
+        if (!had_stream && c->sstream) { hipStreamDestroy(c->sstream); c->sstream = nullptr; }
+        if (!had_event && c->ev_snapped) { hipEventDestroy(c->ev_snapped); c->ev_snapped = nullptr; }
+        c->bytes = bytes0;
+        (void)hipGetLastError();
+        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_snapshot_add failed: %s", hipGetErrorString(e));
+    }
+    sn.bytes = c->bytes - bytes0;
+    if (sn.d_map) c->h2d_bytes += 4 * (int64_t)d->count;
+    sn.steps.assign((size_t)d->slots, 0);
+    sn.id = c->snap_next_id++;
+    *handle = sn.id;
+    c->snaps.push_back(std::move(sn));
+    return HQ_OK;
+}
+
+extern "C" int hq_snapshot_pending(hq_ctx* c, int32_t handle, int32_t* npending, int32_t* nready, int32_t* first_step)
+{
+    if (!c || !npending) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const hq_ctx::hq_snapshot* sn = hq_snapshot_find(c, handle);
+    if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
+    *npending = sn->npending;
+    if (nready) {
+        int32_t n = 0;
+        for (int32_t k = 0; k < sn->npending; k++)
+            n += hipEventQuery(sn->done[(size_t)((sn->head + k) % sn->slots)]) == hipSuccess;
+        (void)hipGetLastError();                                 /* (hipErrorNotReady is an answer, not an error) */
+        *nready = n;
+    }
+    if (first_step) *first_step = sn->npending > 0 ? sn->steps[(size_t)sn->head] : -1;
+    return HQ_OK;
+}
+
+/* `bytes` from the pinned mirror into the caller's array; the large ones on all host threads (one thread moves ~10 GB/s) */
+static void hq_host_copy(void* dst, const void* src, size_t bytes)
+{
+    const size_t chunk = (size_t)4 << 20;
+    const int64_t nchunks = (int64_t)((bytes + chunk - 1) / chunk);
+#pragma omp parallel for schedule(static) if (nchunks > 4)
+    for (int64_t k = 0; k < nchunks; k++) {
+        const size_t at = (size_t)k * chunk;
+        memcpy((char*)dst + at, (const char*)src + at, std::min(chunk, bytes - at));
+    }
+}
+
+extern "C" int hq_snapshot_fetch(hq_ctx* c, int32_t handle, hq_real* tm1, hq_real* tm2, double* vel, int32_t* step)
+{
+    if (!c || !step) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_snapshot* sn = hq_snapshot_find(c, handle);
+    if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
+    if ((tm1 && !(sn->fields & HQ_SNAP_TM1)) || (tm2 && !(sn->fields & HQ_SNAP_TM2)) || (vel && !(sn->fields & HQ_SNAP_VEL)))
+        return hq_fail(HQ_ERR_ARG, "the snapshot does not hold a field that an output pointer was given for%s", "");
+    *step = -1;
+    if (sn->npending == 0) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hipEventSynchronize(sn->done[(size_t)sn->head]));     /* this slot's copy -- not the steps enqueued behind it */
+    const char* h = sn->h_stage + (size_t)sn->head * sn->slot_bytes;
+    const size_t n3 = 3 * (size_t)sn->count;
+    if (tm1) hq_host_copy(tm1, h + sn->off[0], sizeof(hq_real) * n3);
+    if (tm2) hq_host_copy(tm2, h + sn->off[1], sizeof(hq_real) * n3);
+    if (vel) hq_host_copy(vel, h + sn->off[2], sizeof(double) * n3);
+    *step = sn->steps[(size_t)sn->head];
+    sn->head = (sn->head + 1) % sn->slots;
+    sn->npending--;
+    return HQ_OK;
+}
+
+extern "C" int hq_snapshot_clear(hq_ctx* c)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (c->snaps.empty()) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    if (c->sstream) HQ_HIP(hipStreamSynchronize(c->sstream));
+    hq_snapshot_drop_all(c);
     return HQ_OK;
 }
 

@@ -1231,17 +1231,13 @@ int hqh_forcefile_write(const char* path, int32_t nloaded, const int32_t* lnid, 
     return bad ? HQ_ERR_ARG : HQ_OK;
 }
 
-int hqh_checkpoint_write(hq_ctx* ctx, const char* path, int32_t step, int32_t rank, int32_t nranks,
-                         int32_t nharbored, int32_t nharboredmax)
+int hqh_checkpoint_write_fields(const char* path, int32_t step, int32_t rank, int32_t nranks, int32_t nharbored,
+                                int32_t nharboredmax, const double* tm1, const double* tm2)
 {
-    if (!ctx || !path || rank < 0 || rank >= nranks || nharbored < 0 || nharbored > nharboredmax) return HQ_ERR_ARG;
-    size_t n3 = (size_t)nharbored * 3;
-    double* tm1 = (double*)malloc(sizeof(double) * (n3 ? n3 : 1));
-    double* tm2 = (double*)malloc(sizeof(double) * (n3 ? n3 : 1));
-    if (!tm1 || !tm2) { free(tm1); free(tm2); return HQ_ERR_NOMEM; }
-    int rc = hq_download(ctx, tm1, tm2);
+    if (!path || rank < 0 || rank >= nranks || nharbored < 0 || nharbored > nharboredmax || !tm1 || !tm2) return HQ_ERR_ARG;
+    int rc = HQ_OK;
     FILE* fp = NULL;
-    if (rc == HQ_OK && rank == 0) {                       /* io_checkpoint.c:63-74 */
+    if (rank == 0) {                                      /* io_checkpoint.c:63-74 */
         fp = fopen(path, "wb");
         int hdr[3] = { nranks, step, nharboredmax };
         if (!fp || fwrite(hdr, sizeof(int), 3, fp) != 3) rc = HQ_ERR_ARG;
@@ -1259,6 +1255,19 @@ int hqh_checkpoint_write(hq_ctx* ctx, const char* path, int32_t step, int32_t ra
             rc = HQ_ERR_ARG;
         if (fclose(fp) != 0) rc = HQ_ERR_ARG;
     }
+    return rc;
+}
+
+int hqh_checkpoint_write(hq_ctx* ctx, const char* path, int32_t step, int32_t rank, int32_t nranks,
+                         int32_t nharbored, int32_t nharboredmax)
+{
+    if (!ctx || !path || rank < 0 || rank >= nranks || nharbored < 0 || nharbored > nharboredmax) return HQ_ERR_ARG;
+    size_t n3 = (size_t)nharbored * 3;
+    double* tm1 = (double*)malloc(sizeof(double) * (n3 ? n3 : 1));
+    double* tm2 = (double*)malloc(sizeof(double) * (n3 ? n3 : 1));
+    if (!tm1 || !tm2) { free(tm1); free(tm2); return HQ_ERR_NOMEM; }
+    int rc = hq_download(ctx, tm1, tm2);
+    if (rc == HQ_OK) rc = hqh_checkpoint_write_fields(path, step, rank, nranks, nharbored, nharboredmax, tm1, tm2);
     free(tm1); free(tm2);
     return rc;
 }
@@ -1364,6 +1373,19 @@ int hqh_wavefield_write(const char* path, int64_t total_nodes, int32_t quantity,
     return ok ? HQ_OK : HQ_ERR_ARG;
 }
 
+int hqh_wavefield_write_block(const char* path, int64_t total_nodes, int32_t out_step, int64_t base_gnid, int32_t count,
+                              const double* block)
+{
+    if (!path || !block || out_step < 0 || count < 0 || base_gnid < 0 || base_gnid + count > total_nodes) return HQ_ERR_ARG;
+    FILE* fp = fopen(path, "r+");
+    if (!fp) return HQ_ERR_ARG;
+    const off_t off = (off_t)HQH_OUT_HDR_BYTES + (off_t)24 * total_nodes * out_step + (off_t)24 * base_gnid;
+    int ok = fseeko(fp, off, SEEK_SET) == 0;
+    if (ok) ok = fwrite(block, 24, (size_t)count, fp) == (size_t)count;
+    ok = (fclose(fp) == 0) && ok;
+    return ok ? HQ_OK : HQ_ERR_ARG;
+}
+
 int hqh_station_header(char* buf, int32_t cap, int32_t derivs)
 {
     if (!buf || cap < 160 || derivs < 0 || derivs > 2) return HQ_ERR_ARG;
@@ -1460,9 +1482,25 @@ int hqh_solver_run(hq_ctx* ctx, const hqh_box* b, const hqh_run_params* rp, int3
     return hqh_solver_run_on(ctx, b->p.deltaT, b->nharbored, rp, step0, nsteps);
 }
 
-int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0, int32_t nsteps)
+/* hqh_solver_run_async: one field snapshot of the run (hq_snapshot_add); handle -1: none */
+typedef struct { int32_t handle, rate, first_step, slots; } hqh_snapshot;
+
+/* the step a batch that starts at `step` with every slot of this snapshot free must end at, at the latest */
+static int32_t hqh_snapshot_limit(const hqh_snapshot* sn, int32_t step, int32_t next)
 {
-    if (!ctx || !rp || nsteps < 0 || deltaT <= 0 || nharb < 0) return HQ_ERR_ARG;
+    if (sn->handle < 0) return next;
+    const int64_t from = step > sn->first_step ? step : sn->first_step;
+    const int64_t first = (from + sn->rate - 1) / sn->rate * sn->rate;
+    const int64_t full = first + (int64_t)sn->slots * sn->rate;                 /* the (slots + 1)-th due step */
+    return full < next ? (int32_t)full : next;
+}
+
+/* slots = 0: hqh_solver_run_on; slots > 0: hqh_solver_run_async */
+static int hqh_run_impl(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0, int32_t nsteps,
+                        int32_t slots)
+{
+    if (!ctx || !rp || nsteps < 0 || deltaT <= 0 || nharb < 0 || slots < 0) return HQ_ERR_ARG;
+    const int async = slots > 0;
     int32_t win = rp->source_window > 0 ? rp->source_window : 256;
     double* F = NULL;
     double *u = NULL, *disp = NULL;
@@ -1544,15 +1582,46 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
     }
     int ckpt_number = 0;                                         /* CheckpointNumber, io_checkpoint.c:38,126 */
     const int do_ckpt = rp->checkpoint_rate > 0 && rp->checkpoint_dir != NULL;
+    /* hqh_solver_run_async: the 4D output and the checkpoints as field snapshots, fetched and written beside the steps */
+    const int32_t wcnt = rp->wavefield_count > 0 ? rp->wavefield_count : nharb;
+    const int32_t wfirst = rp->wavefield_count > 0 ? rp->wavefield_first_owned : 0;
+    const int64_t wgbase = rp->wavefield_count > 0 ? rp->wavefield_base_gnid : 0;
+    const int64_t wtotal = rp->wavefield_total_nodes > 0 ? rp->wavefield_total_nodes : nharb;
+    hqh_snapshot swv = { -1, 1, 0, slots }, sck = { -1, 1, 0, slots };
+    double *k1 = NULL, *k2 = NULL;
+    if (async && rc == HQ_OK && (do_wave || do_ckpt)) {
+        hq_info inf;
+        if (step0 < 0 || hq_get_info(ctx, &inf) != HQ_OK) rc = HQ_ERR_ARG;
+        else if (inf.step != step0) rc = HQ_ERR_STATE;           /* the due steps follow the context's own counter */
+        hq_snapshot_desc d;
+        if (rc == HQ_OK && do_ckpt) {                            /* first: at a step due for both it is launched, and fetched, first */
+            k1 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
+            k2 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
+            if (!k1 || !k2) rc = HQ_ERR_NOMEM;
+            memset(&d, 0, sizeof d);
+            d.first = 0; d.count = nharb; d.rate = rp->checkpoint_rate; d.first_step = step0 + 1;   /* "not at step0" */
+            d.fields = HQ_SNAP_TM1 | HQ_SNAP_TM2; d.slots = slots;
+            sck.rate = d.rate; sck.first_step = d.first_step;
+            if (rc == HQ_OK) rc = hq_snapshot_add(ctx, &d, &sck.handle);
+        }
+        if (rc == HQ_OK && do_wave) {
+            memset(&d, 0, sizeof d);
+            d.first = wfirst; d.count = wcnt; d.rate = rp->wavefield_rate; d.first_step = 0;
+            d.fields = (rp->wavefield_disp_file ? HQ_SNAP_TM1 : 0) | (rp->wavefield_vel_file ? HQ_SNAP_VEL : 0);
+            d.slots = slots;
+            swv.rate = d.rate; swv.first_step = 0;
+            rc = hq_snapshot_add(ctx, &d, &swv.handle);
+        }
+    }
     while (step < end && rc == HQ_OK) {
-        if (do_ckpt && step != step0 && step % rp->checkpoint_rate == 0) {   /* solver_write_checkpoint, :4277 */
+        if (do_ckpt && !async && step != step0 && step % rp->checkpoint_rate == 0) {   /* solver_write_checkpoint, :4277 */
             char path[1200];
             snprintf(path, sizeof path, "%s/checkpoint.out%d", rp->checkpoint_dir, ckpt_number);
             rc = hqh_checkpoint_write(ctx, path, step, 0, 1, nharb, nharb);
             if (rc != HQ_OK) break;
             ckpt_number = (ckpt_number + 1) % 2;
         }
-        if (do_wave && step % rp->wavefield_rate == 0) {         /* solver_output_wavefield, :4278 */
+        if (do_wave && !async && step % rp->wavefield_rate == 0) {   /* solver_output_wavefield, :4278 */
             rc = hq_download(ctx, w1, rp->wavefield_vel_file ? w2 : NULL);
             const int32_t cnt = rp->wavefield_count > 0 ? rp->wavefield_count : nharb;
             const int32_t first = rp->wavefield_count > 0 ? rp->wavefield_first_owned : 0;
@@ -1618,13 +1687,17 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
             int32_t ns = (step / rp->plane_rate + 1) * rp->plane_rate;
             if (ns < next) next = ns;
         }
-        if (do_ckpt) {
+        if (do_ckpt && !async) {
             int32_t ns = (step / rp->checkpoint_rate + 1) * rp->checkpoint_rate;
             if (ns < next) next = ns;
         }
-        if (do_wave) {
+        if (do_wave && !async) {
             int32_t ns = (step / rp->wavefield_rate + 1) * rp->wavefield_rate;
             if (ns < next) next = ns;
+        }
+        if (async) {                                             /* ... and where the snapshots' slots would run out */
+            next = hqh_snapshot_limit(&sck, step, next);
+            next = hqh_snapshot_limit(&swv, step, next);
         }
         if (dev_rec) {                                           /* ... and where a ring would fill */
             next = hqh_recorder_limit(&rst, step, next);
@@ -1632,6 +1705,28 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
         }
         rc = hq_run(ctx, next - step);
         step = next;
+        /* the batch's snapshots, in step order, while the device works through the batch: each fetch waits for its own
+         * slot's copy only.  At a step due for both, the checkpoint first (:4277-4278) */
+        while (async && rc == HQ_OK) {
+            int32_t nck = 0, nwv = 0, sck_step = -1, swv_step = -1, got = -1;
+            if (sck.handle >= 0) rc = hq_snapshot_pending(ctx, sck.handle, &nck, NULL, &sck_step);
+            if (rc == HQ_OK && swv.handle >= 0) rc = hq_snapshot_pending(ctx, swv.handle, &nwv, NULL, &swv_step);
+            if (rc != HQ_OK || (nck == 0 && nwv == 0)) break;
+            if (nck > 0 && (nwv == 0 || sck_step <= swv_step)) {
+                char path[1200];
+                snprintf(path, sizeof path, "%s/checkpoint.out%d", rp->checkpoint_dir, ckpt_number);
+                rc = hq_snapshot_fetch(ctx, sck.handle, k1, k2, NULL, &got);
+                if (rc == HQ_OK) rc = hqh_checkpoint_write_fields(path, got, 0, 1, nharb, nharb, k1, k2);
+                ckpt_number = (ckpt_number + 1) % 2;
+            } else {
+                rc = hq_snapshot_fetch(ctx, swv.handle, rp->wavefield_disp_file ? w1 : NULL, NULL,
+                                       rp->wavefield_vel_file ? w2 : NULL, &got);
+                if (rc == HQ_OK && rp->wavefield_disp_file)
+                    rc = hqh_wavefield_write_block(rp->wavefield_disp_file, wtotal, got / rp->wavefield_rate, wgbase, wcnt, w1);
+                if (rc == HQ_OK && rp->wavefield_vel_file)
+                    rc = hqh_wavefield_write_block(rp->wavefield_vel_file, wtotal, got / rp->wavefield_rate, wgbase, wcnt, w2);
+            }
+        }
         if (dev_rec && rc == HQ_OK) {
             /* the batch's samples, in step order; at a step both print at, the planes first (:4279-4280) */
             int32_t nst = 0, npl = 0, i = 0, j = 0;
@@ -1662,10 +1757,27 @@ int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_p
         int rc2 = hq_record_clear(ctx);
         if (rc == HQ_OK) rc = rc2;
     }
+    if (async) {
+        int rc2 = hq_snapshot_clear(ctx);
+        if (rc == HQ_OK) rc = rc2;
+    }
     if (pfp) for (int32_t i = 0; i < rp->nplanes; i++) if (pfp[i]) fclose(pfp[i]);
     free(F); free(u); free(disp); free(pu); free(pbuf); free(pfp); free(w1); free(w2);
     free(rst.vals); free(rst.steps); free(rpl.vals); free(rpl.steps); free(pl_ids); free(pl_phi); free(pl_point);
+    free(k1); free(k2);
     return rc;
+}
+
+int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0, int32_t nsteps)
+{
+    return hqh_run_impl(ctx, deltaT, nharb, rp, step0, nsteps, 0);
+}
+
+int hqh_solver_run_async(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0, int32_t nsteps,
+                         int32_t slots)
+{
+    if (slots < 1) return HQ_ERR_ARG;
+    return hqh_run_impl(ctx, deltaT, nharb, rp, step0, nsteps, slots);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -16,6 +16,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_box_node_ijk", "hqh_box_etable", "hqh_box_ntable", "hqh_box_owner", "hqh_box_material", "hqh_ntable_to_float",
            "hqh_point_source", "hqh_stations", "hqh_solver_run", "hqh_source_table",
            "hqh_forcefile_info", "hqh_forcefile_read", "hqh_forcefile_write",
+           "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
            "hqh_station_kinematics", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
@@ -338,6 +339,11 @@ class Box:
         capi._check(self._lib.hqh_solver_run(solver._h, self._h, ctypes.byref(rp), ctypes.c_int32(step0),
                                              ctypes.c_int32(nsteps)))
 
+    def solver_run_async(self, solver, rp, step0, nsteps, slots=2):
+        """hqh_solver_run_async: solver_run with the 4D output and the checkpoints taken as field snapshots and written
+        beside the steps; `slots` snapshots of each kind may be pending at once."""
+        _solver_run_async(self._lib, solver, self.dt, rp, step0, nsteps, slots)
+
 
 class _OctParams(ctypes.Structure):
     _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz_fine", ctypes.c_int32),
@@ -493,6 +499,10 @@ class OctBox:
     def solver_run(self, solver, rp, step0, nsteps):
         capi._check(self._lib.hqh_octbox_solver_run(solver._h, self._h, ctypes.byref(rp), ctypes.c_int32(step0),
                                                     ctypes.c_int32(nsteps)))
+
+    def solver_run_async(self, solver, rp, step0, nsteps, slots=2):
+        """hqh_solver_run_async (see Box.solver_run_async)."""
+        _solver_run_async(self._lib, solver, self.dt, rp, step0, nsteps, slots)
 
     def schedules(self):
         """{"an": {"c": [(procid, mapping)], "s": [...]}, "dn": {...}} (copies)."""
@@ -733,6 +743,27 @@ def checkpoint_write(solver, path, step, rank=0, nranks=1, nharboredmax=None):
                                              ctypes.c_int32(nh if nharboredmax is None else nharboredmax))
     if rc != 0:
         raise capi.HqError("hqh_checkpoint_write failed: %d" % rc)
+
+
+def checkpoint_write_fields(path, step, tm1, tm2, rank=0, nranks=1, nharboredmax=None):
+    """hqh_checkpoint_write_fields: the file half of checkpoint_write, on arrays -- tm1 = u(step dt), tm2 = u((step-1) dt),
+    [nharbored, 3] -- such as a fetched snapshot's (Solver.snapshot_fetch)."""
+    a = np.ascontiguousarray(tm1, np.float64)
+    b = np.ascontiguousarray(tm2, np.float64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape:
+        raise capi.HqError("checkpoint_write_fields: tm1 and tm2 must both be [nharbored, 3]")
+    nh = a.shape[0]
+    rc = load_library().hqh_checkpoint_write_fields(os.fsencode(path), ctypes.c_int32(step), ctypes.c_int32(rank),
+                                                    ctypes.c_int32(nranks), ctypes.c_int32(nh),
+                                                    ctypes.c_int32(nh if nharboredmax is None else nharboredmax),
+                                                    a.ctypes.data_as(ctypes.c_void_p), b.ctypes.data_as(ctypes.c_void_p))
+    if rc != 0:
+        raise capi.HqError("hqh_checkpoint_write_fields failed: %d" % rc)
+
+
+def _solver_run_async(lib, solver, dt, rp, step0, nsteps, slots):
+    capi._check(lib.hqh_solver_run_async(solver._h, ctypes.c_double(dt), ctypes.c_int32(solver.N), ctypes.byref(rp),
+                                         ctypes.c_int32(step0), ctypes.c_int32(nsteps), ctypes.c_int32(slots)))
 
 
 def checkpoint_read(solver, path, rank=0, nranks=1):

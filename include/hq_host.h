@@ -203,6 +203,10 @@ HQ_API int hqh_wavefield_create(const char* path, const hqh_wavefield_info* info
 HQ_API int hqh_wavefield_write(const char* path, int64_t total_nodes, int32_t quantity, int32_t out_step,
                                int64_t base_gnid, int32_t first_owned, int32_t count, const double* tm1,
                                const double* tm2, double delta_t);
+/* The same for a ready-made block: `count` rows of 3 doubles -- displacements, or velocities that were formed elsewhere
+ * (hq_snapshot_fetch's vel) -- go to output step `out_step` at global id base_gnid, whichever quantity the file holds. */
+HQ_API int hqh_wavefield_write_block(const char* path, int64_t total_nodes, int32_t out_step, int64_t base_gnid,
+                                     int32_t count, const double* block);
 
 /* solver_run: steps [step0, step0 + nsteps) on `ctx` (a context made from `box`; or, _on, from
  * any mesh of `nharbored` nodes and time step deltaT). */
@@ -210,6 +214,19 @@ HQ_API int hqh_solver_run(hq_ctx* ctx, const hqh_box* box, const hqh_run_params*
                           int32_t step0, int32_t nsteps);
 HQ_API int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharbored, const hqh_run_params* rp,
                              int32_t step0, int32_t nsteps);
+/*
+ * hqh_solver_run_on with the 4D output and the checkpoints taken as field snapshots (hq_snapshot_add, hq_solver.h) instead
+ * of whole-field downloads that stop the queue: the same callbacks, files and file order (checkpoint.out0 / .out1 in
+ * turn).  The wavefield becomes one snapshot -- wavefield_first_owned / wavefield_count or the whole mesh, TM1 if a
+ * displacement file is asked for, VEL if a velocity file is, rate wavefield_rate -- and the checkpoints another: every
+ * node, TM1 | TM2, rate checkpoint_rate, first_step = step0 + 1 (the reference's "not at step0").  Batches are not cut at
+ * those steps any more, only where the `slots` (>= 1) slots of a snapshot would run out; after each hq_run the runner
+ * fetches every pending snapshot in step order -- at a step due for both, the checkpoint first -- and writes it while the
+ * device works through the batch.  step0 must be the context's own step counter, and the runner drops EVERY snapshot of
+ * the context (hq_snapshot_clear) before it returns.  Checkpoints on a multi-rank context: HQ_ERR_STATE, as above.
+ */
+HQ_API int hqh_solver_run_async(hq_ctx* ctx, double deltaT, int32_t nharbored, const hqh_run_params* rp,
+                                int32_t step0, int32_t nsteps, int32_t slots);
 
 /*
  * Files in the reference's formats, so runs can be exchanged with psolve.
@@ -230,11 +247,16 @@ HQ_API int hqh_forcefile_write(const char* path, int32_t nloaded, const int32_t*
  * u((step-1) dt) then u(step dt), nharbored fvector_t each.
  *   hqh_checkpoint_write: rank 0 must have been called (creates the file) before the
  *                         others write their stripes (the reference barriers there);
+ *   hqh_checkpoint_write_fields: the file half of it, on the caller's arrays (tm1 = u(step dt), tm2 = u((step-1) dt),
+ *                         nharbored fvector_t each) -- hqh_checkpoint_write is hq_download plus this; for states that
+ *                         were fetched as snapshots (hq_snapshot_fetch), partitions included;
  *   hqh_checkpoint_read : verifies the rank count, loads this rank's stripe into the
  *                         context and sets its step; returns the step in *step.
  */
 HQ_API int hqh_checkpoint_write(hq_ctx* ctx, const char* path, int32_t step, int32_t rank, int32_t nranks,
                                 int32_t nharbored, int32_t nharboredmax);
+HQ_API int hqh_checkpoint_write_fields(const char* path, int32_t step, int32_t rank, int32_t nranks,
+                                       int32_t nharbored, int32_t nharboredmax, const double* tm1, const double* tm2);
 HQ_API int hqh_checkpoint_read(hq_ctx* ctx, const char* path, int32_t rank, int32_t nranks,
                                int32_t nharbored, int32_t* step);
 

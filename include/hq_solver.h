@@ -454,6 +454,44 @@ HQ_API int hq_record_fetch(hq_ctx* ctx, int32_t handle, int32_t max_samples, dou
 HQ_API int hq_record_clear(hq_ctx* ctx);
 
 /*
+ * Field snapshots (additive under ABI 6): what the 4D output (solver_output_wavefield psolve.c:3858-3864, output.c:1265)
+ * and checkpoint_write (io_checkpoint.c:98-112) read at the top of the loop body, taken WITHOUT stopping the queue.  A
+ * snapshot is a range of nodes [first, first + count) in the caller's (octor) numbering; at the head of every step
+ * s >= first_step with s % rate == 0 -- where hq_k_record sits, on exactly the state hq_download documents for that step --
+ * one launch of hq_k_snapshot copies the fields out of the device's own numbering into a staging slot in device memory,
+ * in octor order; a copy stream of the context then carries the slot to pinned host memory while the steps s, s + 1, ...
+ * run, and hq_snapshot_fetch hands it over.  tm1 and tm2 are bit copies in hq_real; vel[n][a] = ((double)tm1 - (double)tm2)
+ * / dt without contraction, write_velocity's arithmetic as hqh_wavefield_write states it (always double, in both
+ * libraries) -- a velocity-only output moves 24 bytes per node instead of 48.
+ * `slots` snapshots may be pending (taken or enqueued, not yet fetched) at once; the ring is accounted on the host as the
+ * recorders' is: hq_run, hq_group_run and hq_run_timed count the due steps of the call against the free slots BEFORE they
+ * enqueue anything and return HQ_ERR_STATE, with nothing enqueued and the step counter unchanged, if a slot would be
+ * missing.  hq_snapshot_fetch delivers the OLDEST pending snapshot and frees its slot; it waits only for that slot's copy
+ * -- never for the steps enqueued behind it; tm1 / tm2 / vel may be given only for fields the snapshot has (NULL skips
+ * one), *step is the snapshot's step, -1 (and nothing else written) if none is pending.  hq_snapshot_pending waits for
+ * nothing: *npending counts the snapshots taken or enqueued, *nready those of them whose copy has arrived, *first_step
+ * the oldest one's step or -1 (either of the last two may be NULL).  hq_sync and hq_destroy also wait for the copies.
+ * hq_upload keeps snapshots and pending slots; the due steps follow the new step number.  hq_snapshot_clear waits, then
+ * drops every snapshot of the context and its memory; handles are not reused.  Both variants.
+ * Errors: HQ_ERR_ARG for null pointers, a range outside [0, nharbored), count < 1, rate < 1, slots < 1, fields 0 or with
+ * unknown bits, an unknown handle, an output pointer for a field the snapshot lacks; HQ_ERR_NOMEM if the staging slots
+ * (device), the id map or the pinned host buffers cannot be allocated -- nothing is kept then.
+ * A context without snapshots enqueues exactly what it did before they existed.
+ */
+enum { HQ_SNAP_TM1 = 1, HQ_SNAP_TM2 = 2, HQ_SNAP_VEL = 4 };
+typedef struct {
+    int32_t first, count;     /* local node ids [first, first + count), octor numbering; count >= 1 */
+    int32_t rate;             /* a snapshot at the head of every step s >= first_step with s % rate == 0 */
+    int32_t first_step;
+    int32_t fields;           /* mask of HQ_SNAP_*; non-zero, no unknown bits */
+    int32_t slots;            /* snapshots that may be pending at once (>= 1) */
+} hq_snapshot_desc;
+HQ_API int hq_snapshot_add(hq_ctx* ctx, const hq_snapshot_desc* desc, int32_t* handle);
+HQ_API int hq_snapshot_pending(hq_ctx* ctx, int32_t handle, int32_t* npending, int32_t* nready, int32_t* first_step);
+HQ_API int hq_snapshot_fetch(hq_ctx* ctx, int32_t handle, hq_real* tm1, hq_real* tm2, double* vel, int32_t* step);
+HQ_API int hq_snapshot_clear(hq_ctx* ctx);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
