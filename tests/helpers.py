@@ -99,7 +99,7 @@ def two_level_mesh(nx, ny, nz_fine, nz_coarse, soft=(3000.0, 1732.0, 2200.0), ha
     etable, ntable = ho.solver_init(m["lnid"], edata, m["face"], N, dt, freq)
     ho.compute_adjust(ntable, 0, m["dangling"])
     return dict(lnid=m["lnid"], node_q=m["node_q"], etable=etable, ntable=ntable, dangling=m["dangling"],
-                N=N, E=E, dt=dt, emin=1, mesh=m)
+                N=N, E=E, dt=dt, emin=1, mesh=m, edata=edata, far=far, freq=freq)
 
 
 def c5_np8_problem(name="c5_two_level_np8", real=np.float64):
@@ -216,3 +216,110 @@ def two_material_leaves(nx=128, ny=32, nz=32, split=37, h=100.0):
     edata[:] = (h, 6000.0, 3464.0, 2700.0)
     edata[i < split] = (h, 3000.0, 1732.0, 2200.0)
     return ticks, np.full(len(i), e, np.uint32), edata, (nx * e, ny * e, nz * e)
+
+
+# ---------------------------------------------------------------------------------------------
+# source forces on every node, one step from rest (tests/test_sources_oracle_cpu.py)
+# ---------------------------------------------------------------------------------------------
+def rest_forces(nt0, dt, seed):
+    """A force of its own for every node and component: sign * uniform(0.5, 1) * 1e-3 * n_t[n][0] / dt^2 -- one step from
+    rest then leaves about 1e-3 at every plain node and nothing near zero.  nt0 = the n_t rows' first column. -> [N, 3]"""
+    rng = np.random.default_rng(seed)
+    n = len(nt0)
+    sign = rng.choice([-1.0, 1.0], (n, 3))
+    return sign * rng.uniform(0.5, 1.0, (n, 3)) * (1e-3 / dt ** 2) * np.asarray(nt0, np.float64)[:, None]
+
+
+def node_classes(n, dangling):
+    """-> (hanging, anchor): boolean masks over the n nodes of a mesh with the hanging-node table `dangling` (or None)."""
+    hanging, anchor = np.zeros(n, bool), np.zeros(n, bool)
+    if dangling is not None:
+        hanging[np.asarray(dangling[0])] = True
+        anchor[np.asarray(dangling[2])] = True
+    return hanging, anchor
+
+
+def oracle_step_from_rest(lnid, etable, ntable, dt, loaded, F, dangling=None):
+    """u(1) of the oracle's own single step from zero arrays with the nodes `loaded` forced by F [len(loaded), 3]; the
+    arrays have ntable's type (float32: the oracle's -DSINGLE_PRECISION_SOLVER build)."""
+    n = len(ntable)
+    o1, o2 = np.zeros((n, 3), ntable.dtype), np.zeros((n, 3), ntable.dtype)
+    ho.solver_run(lnid, np.ascontiguousarray(etable, np.float64), np.ascontiguousarray(ntable), o1, o2, 0, 1, dt,
+                  loaded_lnid=np.ascontiguousarray(loaded, np.int32), forces=np.ascontiguousarray(F, np.float64)[None],
+                  dangling=dangling)
+    return o2
+
+
+def uniform_box(nx, ny, nz, h=62.5, dt=1e-3, freq=5.0, vp=6000.0, vs=3464.0, rho=2700.0):
+    """A homogeneous box with the oracle's own tables (ho.uniform_mesh + ho.solver_init) -> dict like two_level_mesh()."""
+    elem_ijk, lnid, node_ijk = ho.uniform_mesh(nx, ny, nz)
+    edata = np.empty((len(lnid), 4), np.float32)
+    edata[:] = (h, vp, vs, rho)
+    et, nt = ho.solver_init(lnid, edata, ho.face_bits(elem_ijk, nx, ny, nz), len(node_ijk), dt, freq)
+    return dict(lnid=lnid, node_ijk=node_ijk, etable=et, ntable=nt, dt=dt, dangling=None, N=len(node_ijk), E=len(lnid),
+                shape=(nx, ny, nz), node_xyz=(np.asarray(node_ijk, np.int64) * (1 << 20)).astype(np.int32))
+
+
+RAGGED_PLAN = {"brick_ragged_minfill": 12, "brick_minnodes": 48, "brick_minz": 2}      # tests/test_gpu_parity.py test_ragged_*
+_SOURCE_MESHES = {}
+
+
+def source_mesh(name):
+    """The meshes of the every-node-loaded source tests (tests/test_gpu_sources.py on the device,
+    tests/test_sources_oracle_cpu.py for the oracle's side and the planner's counters), built once: the smallest ones
+    the suite reaches each kernel with.  -> dict(lnid, etable, ntable, dt, dangling, N, node_xyz[, box | edata, material])"""
+    if name in _SOURCE_MESHES:
+        return _SOURCE_MESHES[name]
+    from hercules_amd import host
+    if name == "box32x32x16":
+        p = uniform_box(32, 32, 16)
+    elif name == "box70x20x12":                 # x extent no multiple of 64, y no multiple of 8: partial tiles
+        p = uniform_box(70, 20, 12)
+    elif name == "box32":                       # 64 patches of 8^3 without bricks, 8 of them full lattices
+        p = uniform_box(32, 32, 32, h=10.0, dt=2e-4)
+    elif name in ("two_material", "lateral"):
+        if name == "two_material":              # (reduced from 128 x 32 x 32: 28 033 nodes, still 8 ragged units)
+            ticks, edge, edata, far = two_material_leaves(nx=96, ny=16, nz=16)
+            box = host.OctBox.from_leaves(ticks, edge, edata, far, 1e-3, 2.0)
+            xyz = box.node_xyz
+        else:
+            box = host.Box(32, 32, 32, 12.5, 2e-4, 50.0, lateral_classes=61, lateral_amp=0.1)
+            xyz = None
+        p = dict(lnid=box.lnid, etable=box.etable, ntable=box.ntable, dt=box.dt, dangling=None, N=len(box.ntable),
+                 node_xyz=xyz, box=box)
+    elif name in ("c5_basin", "c5_gradient"):
+        q = c5_problem(name)
+        p = dict(lnid=q["lnid"], etable=q["etable"], ntable=q["ntable"], dt=q["dt"], dangling=q["dangling"], N=q["N"],
+                 node_xyz=(q["node_q"].astype(np.int64) * q["emin"]).astype(np.int32), edata=q["edata"], material=c5_material(q))
+    elif name == "two_level":
+        q = two_level_mesh(16, 8, 6, 3)
+        p = dict(q, node_xyz=q["node_q"])
+    else:
+        raise KeyError(name)
+    _SOURCE_MESHES[name] = p
+    return p
+
+
+def solver_desc(p):
+    """hq_desc (capi._Desc) of a source_mesh() for the host-only plan checks (capi.brick_plan_check, plan_check,
+    stencil_plan_check); the arrays it points to are kept alive on the returned object."""
+    import ctypes
+    from hercules_amd import capi
+    d = capi._Desc()
+    if "box" in p:
+        fill = p["box"]._lib.hqh_octbox_desc if hasattr(p["box"], "gid") else p["box"]._lib.hqh_box_desc
+        assert fill(p["box"]._h, ctypes.byref(d)) == 0
+        d.variant = capi.HQ_VARIANT_PATCH
+        return d
+    keep = [np.ascontiguousarray(p["lnid"], np.int32), np.ascontiguousarray(p["etable"], np.float64),
+            np.ascontiguousarray(p["ntable"], np.float64), np.ascontiguousarray(p["node_xyz"], np.int32)]
+    d.lenum, d.nharbored = len(keep[0]), len(keep[2])
+    d.lnid, d.eTable, d.nTable, d.node_xyz = [capi._ptr(a) for a in keep]
+    if p["dangling"] is not None:
+        dn = [np.ascontiguousarray(a, np.int32) for a in p["dangling"]]
+        keep += dn
+        d.ldnnum = len(dn[0])
+        d.dn_ldnid, d.dn_ptr, d.dn_lanid = [capi._ptr(a) for a in dn]
+    d.deltaT, d.rank, d.nranks, d.variant = p["dt"], 0, 1, capi.HQ_VARIANT_PATCH
+    d._keep = keep
+    return d
