@@ -475,7 +475,7 @@ def stencil_plan_check(desc):
 
 
 BRICK_PLAN_REPORT = ("brick_nodes", "columns", "units", "units_one_nt_row", "het_units", "neighbours_checked",
-                     "patch_nodes", "faults", "ragged_units", "ragged_nodes", "ragged_het_units", "ragged_het_nodes")
+                     "patch_nodes", "faults", "ragged_units", "ragged_nodes", "ragged_het_units", "ragged_het_nodes", "packed_units")
 
 
 def brick_plan_check(desc):

@@ -231,13 +231,14 @@ extern "C" int hq_stencil_plan_check(const hq_desc* d, int64_t report[6])
  * neighbours -- found through those eight elements -- is the node the kernel will read at that offset: a node of
  * the unit, an entry of the unit's ring table or of its first / last plane's id list.
  * report = {brick nodes, tile columns, units, units with one n_t row, levels, neighbours checked, patch nodes, faults,
- *           ragged units (HQ_BK_RAGGED), the nodes they own, ragged HET units, the nodes they own}
+ *           ragged units (HQ_BK_RAGGED), the nodes they own, ragged HET units, the nodes they own,
+ *           HET units in the packed form (HQ_BK_PACKED), ragged ones included}
  */
-static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[12])
+static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[13])
 {
     hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
     hq_options_resolve(&opts, nullptr);
-    for (int k = 0; k < 12; k++) report[k] = 0;
+    for (int k = 0; k < 13; k++) report[k] = 0;
     if (!d || !d->node_xyz || !d->eTable || !d->nTable)
         return hq_fail(HQ_ERR_ARG, "inconsistent mesh description (node_xyz is needed)%s", "");
     hq_prep prep;
@@ -447,7 +448,7 @@ static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[12])
     }
     report[0] = B.nb; report[1] = B.ncolumns; report[2] = (int64_t)B.units.size(); report[3] = nsame;
     report[4] = B.nhet + B.nrhet; report[5] = nchecked; report[6] = N - B.nb; report[7] = bad;
-    report[8] = B.nrag; report[10] = B.nrhet;
+    report[8] = B.nrag; report[10] = B.nrhet; report[12] = B.npacked + B.nrpacked;
     for (const hq_brick_unit& U : B.units) {
         if (!(U.flags & HQ_BK_RAGGED)) continue;
         const int32_t* pl = B.tab.data() + U.tab + (int64_t)(U.np + 2) * (2 * (U.nx + 2) + 2 * U.ny);
@@ -459,13 +460,13 @@ static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[12])
 
 extern "C" int hq_brick_plan_check(const hq_desc* d, int64_t report[8]) { return hq_brick_plan_check_n(d, report, 8); }
 
-/* the same with a longer report (entries 8 .. 11 above); n = entries the caller has, those past 12 are zeroed */
+/* the same with a longer report (entries 8 .. 12 above); n = entries the caller has, those past 13 are zeroed */
 extern "C" int hq_brick_plan_check_n(const hq_desc* d, int64_t* report, int32_t n)
 {
-    int64_t r12[12];
+    int64_t r13[13];
     if (!report || n < 8) return hq_fail(HQ_ERR_ARG, "hq_brick_plan_check_n: a report of at least 8 entries%s", "");
-    const int rc = hq_brick_plan_check_impl(d, r12);
-    for (int k = 0; k < n; k++) report[k] = k < 12 ? r12[k] : 0;
+    const int rc = hq_brick_plan_check_impl(d, r13);
+    for (int k = 0; k < n; k++) report[k] = k < 13 ? r13[k] : 0;
     return rc;
 }
 

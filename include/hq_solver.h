@@ -542,7 +542,8 @@ HQ_API int hq_stencil_plan_check(const hq_desc* desc, int64_t report[6]);
  */
 HQ_API int hq_brick_plan_check(const hq_desc* desc, int64_t report[8]);
 /* ... with report[8] = units that own only part of their tile (ragged, one n_t row), report[9] = the nodes those own,
- * report[10] / [11] = the same for the ragged units of the per-element kernel; n >= 8 entries */
+ * report[10] / [11] = the same for the ragged units of the per-element kernel, report[12] = the per-element units kept in
+ * the packed form (desc->edata given and every coefficient reproduced bit for bit), ragged ones included; n >= 8 entries */
 HQ_API int hq_brick_plan_check_n(const hq_desc* desc, int64_t* report, int32_t n);
 
 /*

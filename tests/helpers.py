@@ -264,10 +264,17 @@ RAGGED_PLAN = {"brick_ragged_minfill": 12, "brick_minnodes": 48, "brick_minz": 2
 _SOURCE_MESHES = {}
 
 
-def source_mesh(name):
+def source_mesh(name, damping="rayleigh"):
     """The meshes of the every-node-loaded source tests (tests/test_gpu_sources.py on the device,
     tests/test_sources_oracle_cpu.py for the oracle's side and the planner's counters), built once: the smallest ones
-    the suite reaches each kernel with.  -> dict(lnid, etable, ntable, dt, dangling, N, node_xyz[, box | edata, material])"""
+    the suite reaches each kernel with.  -> dict(lnid, etable, ntable, dt, dangling, N, node_xyz[, box | edata, material])
+    het70x20x12 (box70x20x12's geometry) and c5_gradient_branch (c5_gradient's) carry branch_materials per element,
+    labels included, with the tables of the damping kind (rayleigh, mass, none) at step_mesh's time step."""
+    if name in ("het70x20x12", "c5_gradient_branch"):
+        if (name, damping) not in _SOURCE_MESHES:
+            _SOURCE_MESHES[(name, damping)] = _branch_mesh(name, damping)
+        return _SOURCE_MESHES[(name, damping)]
+    assert damping == "rayleigh"
     if name in _SOURCE_MESHES:
         return _SOURCE_MESHES[name]
     from hercules_amd import host
@@ -300,9 +307,10 @@ def source_mesh(name):
     return p
 
 
-def solver_desc(p):
+def solver_desc(p, pack=False):
     """hq_desc (capi._Desc) of a source_mesh() for the host-only plan checks (capi.brick_plan_check, plan_check,
-    stencil_plan_check); the arrays it points to are kept alive on the returned object."""
+    stencil_plan_check); the arrays it points to are kept alive on the returned object.  pack: with p's edata and
+    material (hq_desc.edata / mat_*), as a context that may pack its per-element units gets them."""
     import ctypes
     from hercules_amd import capi
     d = capi._Desc()
@@ -321,5 +329,165 @@ def solver_desc(p):
         d.ldnnum = len(dn[0])
         d.dn_ldnid, d.dn_ptr, d.dn_lanid = [capi._ptr(a) for a in dn]
     d.deltaT, d.rank, d.nranks, d.variant = p["dt"], 0, 1, capi.HQ_VARIANT_PATCH
+    if pack:
+        keep.append(np.ascontiguousarray(p["edata"], np.float32))
+        d.edata = capi._ptr(keep[-1])
+        d.mat_bbase, d.mat_threshold_damping, d.mat_threshold_vpvs = [float(v) for v in p["material"]]
     d._keep = keep
     return d
+
+
+# ---------------------------------------------------------------------------------------------
+# one step from two independent fields, term by term (tests/test_step_terms_cpu.py, tests/test_gpu_step_terms.py)
+# ---------------------------------------------------------------------------------------------
+def extended_step(lnid, etable, ntable, u1, u2, dangling=None):
+    """The oracle's step (oracle/herc_oracle.c: ho_solver_run with the conventional element matrices) restated in
+    np.longdouble, the inputs taken as given and widened: element forces -(c1 K1 + c2 K2) u1 - (c3 K1 + c4 K2)(u1 - u2)
+    with K1, K2 of ho.compute_K(), compute_adjust DISTRIBUTION of the forces, the per-axis update
+    (f + m2[d] u1 - m1[d] u2) / m0 with the 7-double n_t row, compute_adjust ASSIGNMENT.
+    -> (ref [N, 3] = the new displacement, T [N, 3] = the same expression with every product replaced by its absolute
+    value: the node's own scale of summed magnitudes), both np.longdouble."""
+    L = np.longdouble
+    assert np.finfo(L).eps < 1e-18, "np.longdouble is no wider than double here: the test modules skip before they get here"
+    lnid = np.asarray(lnid, np.int64)
+    E, N = len(lnid), len(ntable)
+    et, nt = np.asarray(etable).astype(L), np.asarray(ntable).astype(L)
+    u1, u2 = np.asarray(u1).astype(L), np.asarray(u2).astype(L)
+    # [8][8][3][3] blocks -> [24 = (i, k)][24 = (j, l)]
+    A1, A2 = [np.asarray(K).reshape(8, 8, 3, 3).transpose(0, 2, 1, 3).reshape(24, 24).astype(L) for K in ho.compute_K()]
+    U = u1[lnid].reshape(E, 24)
+    D = (u1 - u2)[lnid].reshape(E, 24)
+    c = [et[:, k:k + 1] for k in range(4)]
+    f = -(c[0] * (U @ A1.T) + c[1] * (U @ A2.T)) - (c[2] * (D @ A1.T) + c[3] * (D @ A2.T))
+    aU, aD, a1, a2 = np.abs(U), np.abs(D), np.abs(A1), np.abs(A2)
+    t = np.abs(c[0]) * (aU @ a1.T) + np.abs(c[1]) * (aU @ a2.T) + np.abs(c[2]) * (aD @ a1.T) + np.abs(c[3]) * (aD @ a2.T)
+    force, tf = np.zeros((N, 3), L), np.zeros((N, 3), L)
+    np.add.at(force, lnid.reshape(-1), f.reshape(-1, 3))
+    np.add.at(tf, lnid.reshape(-1), t.reshape(-1, 3))
+    if dangling is not None and len(dangling[0]):
+        ids, ptr, anc = [np.asarray(a, np.int64) for a in dangling]
+        deps = np.diff(ptr)
+        assert not np.isin(anc, ids).any()                       # no anchor is itself hanging: the order of the loop is free
+        for table in (force, tf):
+            np.add.at(table, anc, np.repeat(table[ids] / deps[:, None].astype(L), deps, axis=0))
+    ref = (force + nt[:, 1:4] * u1 - nt[:, 4:7] * u2) / nt[:, :1]
+    T = (tf + np.abs(nt[:, 1:4] * u1) + np.abs(nt[:, 4:7] * u2)) / np.abs(nt[:, :1])
+    if dangling is not None and len(dangling[0]):
+        for table in (ref, T):
+            mean = np.zeros((len(ids), 3), L)
+            np.add.at(mean, np.repeat(np.arange(len(ids)), deps), table[anc] / np.repeat(deps, deps)[:, None].astype(L))
+            table[ids] = mean
+    return ref, T
+
+
+def step_fields(n, seed, dangling=None, real=np.float64):
+    """(u1, u2), drawn independently as sign * uniform(0.5, 1) * 1e-3 per node and component (the shape of rest_forces:
+    nothing near zero, u1 - u2 as large as the fields); hanging nodes take the mean of their anchors in both."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(2):
+        u = np.ascontiguousarray(rng.choice([-1.0, 1.0], (n, 3)) * rng.uniform(0.5, 1.0, (n, 3)) * 1e-3, real)
+        if dangling is not None and len(dangling[0]):
+            ho.compute_adjust(u, 1, dangling)
+        out.append(u)
+    return out[0], out[1]
+
+
+BRANCHES = ("plain", "capped", "fixed", "zeta_capped")
+
+
+def branch_materials(E, seed, thr_damping=0.05, thr_vpvs=3.0):
+    """Per-element (Vp, Vs, rho) float32 through every branch of mu_and_lambda (psolve.c:3236-3272) and both sides of
+    the damping threshold (psolve.c:3397-3401), drawn as tests/test_kernel_math_cpu.py draws them but shuffled over the
+    elements: Vs in 80 - 4000 (log-uniform: a quarter below 200, where 10 / Vs passes the threshold), a quarter of the
+    elements with Vp / Vs in 3 - 12 (capped), an eighth with Vp^2 < 2 Vs^2 (negative lambda: solver_init rewrites Vp).
+    -> (vp, vs, rho, labels): labels = {name: bool [E]} for BRANCHES, from the edata before and after ho.solver_init
+    rewrote it; plain / capped / fixed exclude each other, zeta_capped is independent of them.  Each holds >= 10 %."""
+    rng = np.random.default_rng(seed)
+    vs = np.exp(rng.uniform(np.log(80.0), np.log(4000.0), E)).astype(np.float32)
+    ratio = np.where(rng.random(E) < 0.25, rng.uniform(3.0, 12.0, E), rng.uniform(1.5, 3.0, E))
+    neg = rng.permutation(E)[: E // 8]
+    ratio[neg] = rng.uniform(0.9, 1.4, len(neg))
+    vp = (vs * ratio).astype(np.float32)
+    rho = rng.uniform(1500.0, 3000.0, E).astype(np.float32)
+    before = np.stack([np.full(E, 10.0, np.float32), vp, vs, rho], 1).copy()
+    after = before.copy()
+    ho.solver_init(np.arange(8 * E, dtype=np.int32).reshape(E, 8), after, np.zeros(E, np.uint8), 8 * E, 1e-3, 5.0,
+                   thr_damping=thr_damping, thr_vpvs=thr_vpvs)      # disjoint elements: only the rewrite of Vp matters
+    fixed = after[:, 1] != before[:, 1]
+    capped = ~fixed & (before[:, 1].astype(np.float64) > before[:, 2].astype(np.float64) * thr_vpvs)
+    zeta = (np.float32(10.0) / vs).astype(np.float64) > thr_damping
+    labels = dict(plain=~fixed & ~capped, capped=capped, fixed=fixed, zeta_capped=zeta)
+    for k in BRANCHES:
+        assert labels[k].sum() * 10 >= E, (k, int(labels[k].sum()), E)
+    assert np.array_equal(fixed, np.isin(np.arange(E), neg))
+    return vp, vs, rho, labels
+
+
+def _quarter_cfl_dt(edata, thr_vpvs=3.0):
+    """dt at which the stiffest element has (Vp dt / h)^2 = 0.25, Vp as the solver uses it (capped at thr_vpvs Vs; the
+    edata as solver_init left it): one step needs no stability, only a force that is not lost beside 2 u1 - u2."""
+    ed = np.asarray(edata, np.float64)
+    return float(0.5 / (np.minimum(ed[:, 1], thr_vpvs * ed[:, 2]) / ed[:, 0]).max())
+
+
+def _branch_tables(lnid, h, face, N, seed, damping, freq, dangling=None):
+    """branch_materials on a mesh -> (edata as solver_init left it, etable, ntable, dt, labels, material)."""
+    kind = ho.DAMPING_BY_NAME[damping]
+    vp, vs, rho, labels = branch_materials(len(lnid), seed)
+    raw = np.ascontiguousarray(np.stack([np.asarray(h, np.float32) * np.ones(len(lnid), np.float32), vp, vs, rho], 1))
+    probe = raw.copy()
+    ho.solver_init(lnid, probe, face, N, 1e-3, freq, damping=kind)           # (the rewritten Vp does not depend on dt)
+    dt = _quarter_cfl_dt(probe)
+    edata = raw.copy()
+    etable, ntable = ho.solver_init(lnid, edata, face, N, dt, freq, damping=kind)
+    assert np.array_equal(edata, probe)
+    if dangling is not None:
+        ho.compute_adjust(ntable, 0, dangling)
+    return edata, etable, ntable, dt, labels, (ho.setab(freq, kind)[1], 0.05, 3.0)
+
+
+def _branch_mesh(name, damping):
+    if name == "het70x20x12":
+        nx, ny, nz, h, freq = 70, 20, 12, 62.5, 5.0
+        elem_ijk, lnid, node_ijk = ho.uniform_mesh(nx, ny, nz)
+        edata, et, nt, dt, labels, material = _branch_tables(lnid, h, ho.face_bits(elem_ijk, nx, ny, nz), len(node_ijk), 7012,
+                                                             damping, freq)
+        return dict(lnid=lnid, etable=et, ntable=nt, dt=dt, dangling=None, N=len(node_ijk), E=len(lnid), shape=(nx, ny, nz),
+                    node_xyz=(np.asarray(node_ijk, np.int64) * (1 << 20)).astype(np.int32), edata=edata, material=material,
+                    labels=labels, damping=damping)
+    g = load("c5_gradient")
+    m = ho.octree_mesh_from_elem_ticks(g["elem_ticks"], C1_FAR_TICKS)
+    h = (1000.0 / 2 ** 30 * m["emin"] * m["elem_size"].astype(np.float64)).astype(np.float32)
+    edata, et, nt, dt, labels, material = _branch_tables(m["lnid"], h, m["face"], len(m["node_q"]), 7013, damping, float(g["freq"]),
+                                                         m["dangling"])
+    return dict(lnid=m["lnid"], etable=et, ntable=nt, dt=dt, dangling=m["dangling"], N=len(m["node_q"]), E=len(m["lnid"]),
+                node_xyz=(m["node_q"].astype(np.int64) * m["emin"]).astype(np.int32), edata=edata, material=material,
+                labels=labels, damping=damping)
+
+
+_STEP_MESHES = {}
+
+
+def step_mesh(name, damping="rayleigh"):
+    """A mesh of the one-step term tests with the time step at a quarter of the stiffest element's CFL square and the
+    tables of the damping kind: source_mesh's new entries as they are, its homogeneous ones rebuilt at that dt."""
+    key = (name, damping)
+    if key in _STEP_MESHES:
+        return _STEP_MESHES[key]
+    kind = ho.DAMPING_BY_NAME[damping]
+    if name in ("het70x20x12", "c5_gradient_branch"):
+        p = source_mesh(name, damping)
+    elif name in ("box32x32x16", "box70x20x12", "box32"):
+        assert damping == "rayleigh"
+        shape, h = {"box32x32x16": ((32, 32, 16), 62.5), "box70x20x12": ((70, 20, 12), 62.5), "box32": ((32, 32, 32), 10.0)}[name]
+        p = uniform_box(*shape, h=h, dt=0.5 * h / 6000.0)
+    elif name == "two_level":
+        assert damping == "rayleigh"
+        q = two_level_mesh(16, 8, 6, 3, dt=0.5 * 31.25 / 3000.0)
+        p = dict(q, node_xyz=q["node_q"])
+    else:
+        raise KeyError(name)
+    p = dict(p, damping=damping, kind=kind)
+    _STEP_MESHES[key] = p
+    return p
