@@ -41,6 +41,7 @@
 #include "../../include/hq_solver.h"
 #include "hq_kernels.h"
 #include "hq_opts.h"
+#include "hq_cadence.h"
 #include "hq_patch.h"
 #include "hq_brick.h"
 
@@ -256,37 +257,46 @@ struct hq_ctx {
     size_t clock_at = 0;
     double clk_us[5] = { 0, 0, 0, 0, 0 };   /* step, shell, interior, chain, chain behind the interior's end */
     int64_t clk_steps = 0;
-    /* sample recorders (hq_record_add): rings in device memory, accounted on the host -- which steps are due follows
-     * from `step` alone.  ev_recorded exists from the first hq_record_add on: behind a due step's hq_k_record launches,
-     * waited for by the streams whose kernels of that step overwrite the buffer the launches read as u(t - 2 dt) */
-    struct hq_recorder {
-        int32_t id = 0, np = 0, rate = 1, derivs = 0, capacity = 0;
+    /* what a recorder and a snapshot share (hq_cadence.h): the steps it is due at and the ring of its pending slots,
+     * accounted on the host -- which steps are due follows from `step` alone */
+    struct hq_output {
+        int32_t id = 0;
+        hq_cadence due = { 1, 0 };
+        hq_step_ring ring = { nullptr, 0, 0, 0 };
+        std::vector<int32_t> steps;   /* [capacity] the ring's storage: a move keeps the buffer, and so ring.steps */
+        int64_t bytes = 0;            /* device memory of this output (part of `bytes`) */
+        void open(int32_t rate, int64_t first_step, int32_t capacity)
+        {
+            due = { rate, first_step };
+            steps.assign((size_t)capacity, 0);
+            ring = { steps.data(), capacity, 0, 0 };
+        }
+    };
+    /* sample recorders (hq_record_add): rings in device memory.  ev_recorded exists from the first hq_record_add on: behind
+     * a due step's hq_k_record launches, waited for by the streams whose kernels of that step overwrite the buffer the
+     * launches read as u(t - 2 dt) */
+    struct hq_recorder : hq_output {
+        int32_t np = 0, derivs = 0;
         int32_t* d_ids = nullptr;     /* [8][np] device numbering */
         double* d_phi = nullptr;      /* [8][np] */
         double* d_ring = nullptr;     /* [capacity][np][3 (1 + derivs)] */
-        int32_t head = 0, count = 0;  /* oldest pending slot, pending samples (taken or enqueued) */
-        std::vector<int32_t> steps;   /* [capacity] step number of the sample in each slot */
-        int64_t bytes = 0;            /* device memory of this recorder (part of `bytes`) */
     };
     std::vector<hq_recorder> recs;
     int32_t rec_next_id = 0;
     hipEvent_t ev_recorded = nullptr;
     /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
-     * pinned host memory, accounted on the host as the recorders' rings are.  A slot holds the fields one behind the other,
+     * pinned host memory.  A slot holds the fields one behind the other,
      * each at a 256-byte boundary (off[]; the same layout on both sides, so one copy carries a slot).  sstream, the copy
      * stream, and ev_snapped exist from the first hq_snapshot_add on: behind each hq_k_snapshot launch the event is
      * recorded on the compute stream and waited for by sstream, which copies the slot and records the slot's done event */
-    struct hq_snapshot {
-        int32_t id = 0, first = 0, count = 0, rate = 1, first_step = 0, fields = 0, slots = 0;
+    struct hq_snapshot : hq_output {
+        int32_t first = 0, count = 0, fields = 0;
         int32_t* d_map = nullptr;     /* [count] device id of node first + i; NULL on contexts without a renumbering */
         char* d_stage = nullptr;      /* [slots][slot_bytes] */
         char* h_stage = nullptr;      /* the same, pinned host memory */
         size_t off[3] = { 0, 0, 0 };  /* tm1, tm2, vel inside a slot */
         size_t slot_bytes = 0;
-        int32_t head = 0, npending = 0;
-        std::vector<int32_t> steps;   /* [slots] step number of the snapshot in each slot */
         std::vector<hipEvent_t> done; /* [slots] the slot's copy has arrived */
-        int64_t bytes = 0;            /* device memory of this snapshot (part of `bytes`) */
     };
     std::vector<hq_snapshot> snaps;
     int32_t snap_next_id = 0;
@@ -1319,19 +1329,44 @@ static bool hq_use_brick_stream(hq_ctx* c)
     return true;
 }
 
-/* ---- sample recorders ---- */
+/* ---- device outputs: what recorders and snapshots share (hq_cadence.h) ---- */
 
-/* would the due steps of [c->step, c->step + nsteps) overflow a ring?  Decided before anything is enqueued */
-static int hq_record_check_room(const hq_ctx* c, int32_t nsteps)
+/* do the due steps of [c->step, c->step + nsteps) fit into every ring's free slots? */
+template <typename T>
+static bool hq_outputs_have_room(const std::vector<T>& outs, int64_t step, int32_t nsteps)
 {
-    for (const auto& r : c->recs) {
-        int64_t due = 0;
-        for (int32_t s = 0; s < nsteps; s++) due += ((int64_t)c->step + s) % r.rate == 0;
-        if (r.count + due > r.capacity)
-            return hq_fail(HQ_ERR_STATE, "a recorder's ring would overflow: fetch its samples first (hq_record_fetch)%s", "");
-    }
+    for (const auto& o : outs)
+        if (hq_cadence_count(o.due, step, step + nsteps) > hq_step_ring_room(&o.ring)) return false;
+    return true;
+}
+
+/* the recorders' rings and the snapshots' slots: what hq_run, hq_group_run and hq_run_timed ask before they enqueue */
+static int hq_output_check_room(const hq_ctx* c, int32_t nsteps)
+{
+    if (!hq_outputs_have_room(c->recs, c->step, nsteps))
+        return hq_fail(HQ_ERR_STATE, "a recorder's ring would overflow: fetch its samples first (hq_record_fetch)%s", "");
+    if (!hq_outputs_have_room(c->snaps, c->step, nsteps))
+        return hq_fail(HQ_ERR_STATE, "a snapshot's slots would run out: fetch the pending ones first (hq_snapshot_fetch)%s", "");
     return HQ_OK;
 }
+
+template <typename T>
+static T* hq_output_find(std::vector<T>& outs, int32_t handle)
+{
+    for (auto& o : outs)
+        if (o.id == handle) return &o;
+    return nullptr;
+}
+
+/* hold the bricks' own stream and the exchange chain's behind `ev`, recorded on the compute stream */
+static int hq_hold_behind(hq_ctx* c, bool brick_stream, hipEvent_t ev)
+{
+    if (brick_stream && c->bstream) HQ_HIP(hipStreamWaitEvent(c->bstream, ev, 0));
+    if (c->overlap && c->cstream) HQ_HIP(hipStreamWaitEvent(c->cstream, ev, 0));
+    return HQ_OK;
+}
+
+/* ---- sample recorders ---- */
 
 /* free every recorder (the caller has waited for the streams) */
 static void hq_record_drop_all(hq_ctx* c)
@@ -1354,11 +1389,9 @@ static int hq_record_enqueue(hq_ctx* c, bool brick_stream)
 {
     bool any = false;
     for (auto& r : c->recs) {
-        if (c->step % r.rate != 0) continue;
-        if (r.count >= r.capacity) return hq_fail(HQ_ERR_STATE, "a recorder's ring is full%s", "");   /* (hq_record_check_room saw to it) */
-        const int32_t slot = (r.head + r.count) % r.capacity;
-        r.steps[(size_t)slot] = c->step;
-        r.count++;
+        if (!hq_cadence_due(r.due, c->step)) continue;
+        const int32_t slot = hq_step_ring_push(&r.ring, c->step);
+        if (slot < 0) return hq_fail(HQ_ERR_STATE, "a recorder's ring is full%s", "");   /* (hq_output_check_room saw to it) */
         if (r.np <= 0) continue;
         const int32_t ncomp = 3 * (1 + r.derivs);
         hq_k_record<<<hq_blocks(r.np, 256), 256, 0, c->stream>>>(
@@ -1368,34 +1401,12 @@ static int hq_record_enqueue(hq_ctx* c, bool brick_stream)
     }
     if (any && c->variant == HQ_VARIANT_PATCH && ((brick_stream && c->bstream) || (c->overlap && c->cstream))) {
         HQ_HIP(hipEventRecord(c->ev_recorded, c->stream));
-        if (brick_stream && c->bstream) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_recorded, 0));
-        if (c->overlap && c->cstream) HQ_HIP(hipStreamWaitEvent(c->cstream, c->ev_recorded, 0));
+        HQ_TRY(hq_hold_behind(c, brick_stream, c->ev_recorded));
     }
     return HQ_OK;
 }
 
 /* ---- field snapshots ---- */
-
-static inline bool hq_snapshot_due(const hq_ctx::hq_snapshot& sn, int64_t step) { return step >= sn.first_step && step % sn.rate == 0; }
-
-/* would the due steps of [c->step, c->step + nsteps) need more slots than are free?  Decided before anything is enqueued */
-static int hq_snapshot_check_room(const hq_ctx* c, int32_t nsteps)
-{
-    for (const auto& sn : c->snaps) {
-        int64_t due = 0;
-        for (int32_t s = 0; s < nsteps; s++) due += hq_snapshot_due(sn, (int64_t)c->step + s);
-        if (sn.npending + due > sn.slots)
-            return hq_fail(HQ_ERR_STATE, "a snapshot's slots would run out: fetch the pending ones first (hq_snapshot_fetch)%s", "");
-    }
-    return HQ_OK;
-}
-
-/* the recorders' rings and the snapshots' slots: what hq_run, hq_group_run and hq_run_timed ask before they enqueue */
-static int hq_output_check_room(const hq_ctx* c, int32_t nsteps)
-{
-    HQ_TRY(hq_record_check_room(c, nsteps));
-    return hq_snapshot_check_room(c, nsteps);
-}
 
 /* free every snapshot (the caller has waited for the streams, the copy stream included) */
 static void hq_snapshot_drop_all(hq_ctx* c)
@@ -1422,11 +1433,9 @@ static int hq_snapshot_enqueue(hq_ctx* c, bool brick_stream)
 {
     bool any = false;
     for (auto& sn : c->snaps) {
-        if (!hq_snapshot_due(sn, c->step)) continue;
-        if (sn.npending >= sn.slots) return hq_fail(HQ_ERR_STATE, "a snapshot's slots are all pending%s", "");   /* (hq_snapshot_check_room saw to it) */
-        const int32_t slot = (sn.head + sn.npending) % sn.slots;
-        sn.steps[(size_t)slot] = c->step;
-        sn.npending++;
+        if (!hq_cadence_due(sn.due, c->step)) continue;
+        const int32_t slot = hq_step_ring_push(&sn.ring, c->step);
+        if (slot < 0) return hq_fail(HQ_ERR_STATE, "a snapshot's slots are all pending%s", "");   /* (hq_output_check_room saw to it) */
         char* d = sn.d_stage + (size_t)slot * sn.slot_bytes;
         constexpr int32_t tile_rows = 256 * (16 / (int32_t)sizeof(hq_real));
         const int64_t ntiles = ((int64_t)sn.count + tile_rows - 1) / tile_rows;
@@ -1442,10 +1451,7 @@ static int hq_snapshot_enqueue(hq_ctx* c, bool brick_stream)
         c->d2h_bytes += (int64_t)sn.slot_bytes;
         any = true;
     }
-    if (any && c->variant == HQ_VARIANT_PATCH) {                 /* (ev_snapped names the last launch's record) */
-        if (brick_stream && c->bstream) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_snapped, 0));
-        if (c->overlap && c->cstream) HQ_HIP(hipStreamWaitEvent(c->cstream, c->ev_snapped, 0));
-    }
+    if (any && c->variant == HQ_VARIANT_PATCH) HQ_TRY(hq_hold_behind(c, brick_stream, c->ev_snapped));   /* (the last launch's record) */
     return HQ_OK;
 }
 
@@ -2877,13 +2883,6 @@ static int hq_gather_impl(hq_ctx* c, int32_t n, const int32_t* lnid, hq_real* o1
 
 /* ---- sample recorders: entry points (include/hq_solver.h) ---- */
 
-static hq_ctx::hq_recorder* hq_record_find(hq_ctx* c, int32_t handle)
-{
-    for (auto& r : c->recs)
-        if (r.id == handle) return &r;
-    return nullptr;
-}
-
 extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* handle)
 {
     if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
@@ -2906,7 +2905,7 @@ extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* hand
             phi[(size_t)k * np + p] = d->phi[8 * (size_t)p + k];
         }
     hq_ctx::hq_recorder r;
-    r.np = np; r.rate = d->rate; r.derivs = d->derivs; r.capacity = d->capacity;
+    r.np = np; r.derivs = d->derivs;
     const size_t ring = (size_t)d->capacity * (size_t)np * 3 * (size_t)(1 + d->derivs);
     const int64_t bytes0 = c->bytes;
     int rc = hq_dev_alloc(c, &r.d_ids, ids.size());
@@ -2928,7 +2927,7 @@ extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* hand
     }
     r.bytes = c->bytes - bytes0;
     c->h2d_bytes += 12 * (int64_t)ids.size();
-    r.steps.assign((size_t)d->capacity, 0);
+    r.open(d->rate, INT32_MIN, d->capacity);                     /* every multiple of the rate, wherever `step` is set to */
     r.id = c->rec_next_id++;
     *handle = r.id;
     c->recs.push_back(std::move(r));
@@ -2938,10 +2937,10 @@ extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* hand
 extern "C" int hq_record_pending(hq_ctx* c, int32_t handle, int32_t* nsamples, int32_t* first_step)
 {
     if (!c || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const hq_ctx::hq_recorder* r = hq_record_find(c, handle);
+    const hq_ctx::hq_recorder* r = hq_output_find(c->recs, handle);
     if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
-    *nsamples = r->count;
-    if (first_step) *first_step = r->count > 0 ? r->steps[(size_t)r->head] : -1;
+    *nsamples = r->ring.count;
+    if (first_step) *first_step = hq_step_ring_first_step(&r->ring);
     return HQ_OK;
 }
 
@@ -2949,24 +2948,23 @@ extern "C" int hq_record_fetch(hq_ctx* c, int32_t handle, int32_t max_samples, d
                                int32_t* nfetched)
 {
     if (!c || !out || !steps || !nfetched || max_samples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
-    hq_ctx::hq_recorder* r = hq_record_find(c, handle);
+    hq_ctx::hq_recorder* r = hq_output_find(c->recs, handle);
     if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
     *nfetched = 0;
-    const int32_t n = std::min(max_samples, r->count);
+    const int32_t n = std::min(max_samples, r->ring.count), head = r->ring.head;
     if (n == 0) return HQ_OK;
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
     const size_t row = (size_t)r->np * 3 * (size_t)(1 + r->derivs);          /* doubles per sample */
-    const int32_t first = std::min(n, r->capacity - r->head);                /* up to the ring's end, then from its start */
+    const int32_t first = std::min(n, r->ring.capacity - head);              /* up to the ring's end, then from its start */
     if (row > 0) {
-        HQ_HIP(hipMemcpy(out, r->d_ring + (size_t)r->head * row, sizeof(double) * row * (size_t)first, hipMemcpyDeviceToHost));
+        HQ_HIP(hipMemcpy(out, r->d_ring + (size_t)head * row, sizeof(double) * row * (size_t)first, hipMemcpyDeviceToHost));
         if (n > first)
             HQ_HIP(hipMemcpy(out + (size_t)first * row, r->d_ring, sizeof(double) * row * (size_t)(n - first), hipMemcpyDeviceToHost));
     }
-    for (int32_t k = 0; k < n; k++) steps[k] = r->steps[(size_t)((r->head + k) % r->capacity)];
+    for (int32_t k = 0; k < n; k++) steps[k] = r->steps[(size_t)hq_step_ring_slot_at(&r->ring, k)];
     c->d2h_bytes += 8 * (int64_t)row * n;
-    r->head = (r->head + n) % r->capacity;
-    r->count -= n;
+    hq_step_ring_pop(&r->ring, n);
     *nfetched = n;
     return HQ_OK;
 }
@@ -2983,13 +2981,6 @@ extern "C" int hq_record_clear(hq_ctx* c)
 
 /* ---- field snapshots: entry points (include/hq_solver.h) ---- */
 
-static hq_ctx::hq_snapshot* hq_snapshot_find(hq_ctx* c, int32_t handle)
-{
-    for (auto& sn : c->snaps)
-        if (sn.id == handle) return &sn;
-    return nullptr;
-}
-
 extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* handle)
 {
     if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
@@ -2999,8 +2990,7 @@ extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* ha
         return hq_fail(HQ_ERR_ARG, "bad snapshot description%s", "");
     HQ_HIP(hipSetDevice(c->device));
     hq_ctx::hq_snapshot sn;
-    sn.first = d->first; sn.count = d->count; sn.rate = d->rate; sn.first_step = d->first_step; sn.fields = d->fields;
-    sn.slots = d->slots;
+    sn.first = d->first; sn.count = d->count; sn.fields = d->fields;
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t n3 = 3 * (size_t)d->count;
     size_t at = 0;
@@ -3039,7 +3029,7 @@ extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* ha
     }
     sn.bytes = c->bytes - bytes0;
     if (sn.d_map) c->h2d_bytes += 4 * (int64_t)d->count;
-    sn.steps.assign((size_t)d->slots, 0);
+    sn.open(d->rate, d->first_step, d->slots);
     sn.id = c->snap_next_id++;
     *handle = sn.id;
     c->snaps.push_back(std::move(sn));
@@ -3049,17 +3039,17 @@ extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* ha
 extern "C" int hq_snapshot_pending(hq_ctx* c, int32_t handle, int32_t* npending, int32_t* nready, int32_t* first_step)
 {
     if (!c || !npending) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const hq_ctx::hq_snapshot* sn = hq_snapshot_find(c, handle);
+    const hq_ctx::hq_snapshot* sn = hq_output_find(c->snaps, handle);
     if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
-    *npending = sn->npending;
+    *npending = sn->ring.count;
     if (nready) {
         int32_t n = 0;
-        for (int32_t k = 0; k < sn->npending; k++)
-            n += hipEventQuery(sn->done[(size_t)((sn->head + k) % sn->slots)]) == hipSuccess;
+        for (int32_t k = 0; k < sn->ring.count; k++)
+            n += hipEventQuery(sn->done[(size_t)hq_step_ring_slot_at(&sn->ring, k)]) == hipSuccess;
         (void)hipGetLastError();                                 /* (hipErrorNotReady is an answer, not an error) */
         *nready = n;
     }
-    if (first_step) *first_step = sn->npending > 0 ? sn->steps[(size_t)sn->head] : -1;
+    if (first_step) *first_step = hq_step_ring_first_step(&sn->ring);
     return HQ_OK;
 }
 
@@ -3078,22 +3068,21 @@ static void hq_host_copy(void* dst, const void* src, size_t bytes)
 extern "C" int hq_snapshot_fetch(hq_ctx* c, int32_t handle, hq_real* tm1, hq_real* tm2, double* vel, int32_t* step)
 {
     if (!c || !step) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_snapshot* sn = hq_snapshot_find(c, handle);
+    hq_ctx::hq_snapshot* sn = hq_output_find(c->snaps, handle);
     if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
     if ((tm1 && !(sn->fields & HQ_SNAP_TM1)) || (tm2 && !(sn->fields & HQ_SNAP_TM2)) || (vel && !(sn->fields & HQ_SNAP_VEL)))
         return hq_fail(HQ_ERR_ARG, "the snapshot does not hold a field that an output pointer was given for%s", "");
     *step = -1;
-    if (sn->npending == 0) return HQ_OK;
+    if (sn->ring.count == 0) return HQ_OK;
     HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hipEventSynchronize(sn->done[(size_t)sn->head]));     /* this slot's copy -- not the steps enqueued behind it */
-    const char* h = sn->h_stage + (size_t)sn->head * sn->slot_bytes;
+    HQ_HIP(hipEventSynchronize(sn->done[(size_t)sn->ring.head]));   /* this slot's copy -- not the steps enqueued behind it */
+    const char* h = sn->h_stage + (size_t)sn->ring.head * sn->slot_bytes;
     const size_t n3 = 3 * (size_t)sn->count;
     if (tm1) hq_host_copy(tm1, h + sn->off[0], sizeof(hq_real) * n3);
     if (tm2) hq_host_copy(tm2, h + sn->off[1], sizeof(hq_real) * n3);
     if (vel) hq_host_copy(vel, h + sn->off[2], sizeof(double) * n3);
-    *step = sn->steps[(size_t)sn->head];
-    sn->head = (sn->head + 1) % sn->slots;
-    sn->npending--;
+    *step = hq_step_ring_first_step(&sn->ring);
+    hq_step_ring_pop(&sn->ring, 1);
     return HQ_OK;
 }
 

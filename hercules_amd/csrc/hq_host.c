@@ -33,6 +33,7 @@
 #endif
 
 #include "hq_host.h"
+#include "hq_cadence.h"
 
 #define HQH_PI 3.14159265358979323846
 
@@ -1431,45 +1432,6 @@ void hqh_source_table(const hqh_run_params* rp, double dt, int32_t step0, int32_
     }
 }
 
-/* hqh_run_params.device_recorders: one device recorder of the run (hq_record_add) and the host buffers one batch's
- * samples are fetched into.  The ring holds every due step of [step0, end) where that stays within 64 MB, fewer
- * otherwise (the batches are then cut where it would fill); no recorder at all (handle -1) if no step is due. */
-#define HQH_RING_BYTES ((int64_t)64 << 20)
-typedef struct {
-    int32_t  handle, cap, rate, ncomp, npoints;
-    double*  vals;                                               /* [cap][npoints][ncomp] */
-    int32_t* steps;                                              /* [cap] */
-} hqh_recorder;
-
-static int hqh_recorder_open(hq_ctx* ctx, hqh_recorder* r, int32_t npoints, const int32_t* ids, const double* phi,
-                             int32_t rate, int32_t derivs, int32_t step0, int32_t end)
-{
-    r->handle = -1; r->cap = 0; r->rate = rate; r->ncomp = 3 * (1 + derivs); r->npoints = npoints;
-    r->vals = NULL; r->steps = NULL;
-    const int64_t first = ((int64_t)step0 + rate - 1) / rate * rate;            /* first due step >= step0 */
-    if (first >= end) return HQ_OK;
-    int64_t cap = ((int64_t)end - 1 - first) / rate + 1;                        /* due steps of the run */
-    const int64_t row = 8 * (int64_t)npoints * r->ncomp;                        /* bytes per sample */
-    if (row > 0 && cap * row > HQH_RING_BYTES) cap = HQH_RING_BYTES / row > 0 ? HQH_RING_BYTES / row : 1;
-    r->cap = (int32_t)cap;
-    r->vals = (double*)malloc((size_t)(cap * row > 0 ? cap * row : 8));
-    r->steps = (int32_t*)malloc(sizeof(int32_t) * (size_t)cap);
-    if (!r->vals || !r->steps) return HQ_ERR_NOMEM;
-    hq_recorder_desc d;
-    memset(&d, 0, sizeof d);
-    d.npoints = npoints; d.ids = ids; d.phi = phi; d.rate = rate; d.derivs = derivs; d.capacity = r->cap;
-    return hq_record_add(ctx, &d, &r->handle);
-}
-
-/* the step a batch that starts at `step` with this recorder's ring empty must end at, at the latest */
-static int32_t hqh_recorder_limit(const hqh_recorder* r, int32_t step, int32_t next)
-{
-    if (r->handle < 0) return next;
-    const int64_t first = ((int64_t)step + r->rate - 1) / r->rate * r->rate;
-    const int64_t full = first + (int64_t)r->cap * r->rate;                     /* the (cap + 1)-th due step */
-    return full < next ? (int32_t)full : next;
-}
-
 /*
  * solver_run, psolve.c:4241-4324.  Per step the reference does: swap, outputs
  * (stations read tm1), read source forces, physics + communication.  Here the
@@ -1482,290 +1444,392 @@ int hqh_solver_run(hq_ctx* ctx, const hqh_box* b, const hqh_run_params* rp, int3
     return hqh_solver_run_on(ctx, b->p.deltaT, b->nharbored, rp, step0, nsteps);
 }
 
-/* hqh_solver_run_async: one field snapshot of the run (hq_snapshot_add); handle -1: none */
-typedef struct { int32_t handle, rate, first_step, slots; } hqh_snapshot;
+/* hqh_run_params.device_recorders: one device recorder of the run (hq_record_add) and the host buffers one batch's
+ * samples are fetched into.  The ring holds every due step of [step0, end) where that stays within 64 MB, fewer
+ * otherwise (the batches are then cut where it would fill); no recorder at all (handle -1) if no step is due. */
+#define HQH_RING_BYTES ((int64_t)64 << 20)
+typedef struct {
+    int32_t  handle, cap, ncomp, npoints;
+    double*  vals;                                               /* [cap][npoints][ncomp] */
+    int32_t* steps;                                              /* [cap] */
+    int32_t  n, at;                                              /* the batch's samples, and the next of them to hand on */
+} hqh_recorder;
 
-/* the step a batch that starts at `step` with every slot of this snapshot free must end at, at the latest */
-static int32_t hqh_snapshot_limit(const hqh_snapshot* sn, int32_t step, int32_t next)
+/* the run's outputs in the order the reference takes them at a step (psolve.c:4277-4280) */
+enum { HQH_CKPT = 0, HQH_WAVE, HQH_PLANES, HQH_STATIONS, HQH_NOUT };
+
+/* everything a run owns: hqh_run_open fills it, hqh_run_close frees it */
+typedef struct {
+    hq_ctx* ctx;
+    const hqh_run_params* rp;
+    double deltaT;
+    int32_t nharb, step0, end, win, slots;
+    hq_cadence due[HQH_NOUT];                                    /* from step0 on; checkpoints "not at step0" */
+    int on[HQH_NOUT], sync[HQH_NOUT];                            /* asked for; and taken by the host at its due steps */
+    int dev_rec, async;                                          /* close clears the context's recorders / snapshots */
+    int64_t sync_rates[HQH_NOUT];                                /* hq_batch_end's arguments: the same for every batch, */
+    hq_device_output dev[HQH_NOUT];                              /* as every ring and slot set is empty when one starts */
+    int nsync, ndev;
+    double* F;                                                   /* the source window */
+    double *u, *disp;                                            /* stations: tm1 | tm2 | tm3 rows; what the callback gets */
+    double *pu, *pbuf;                                           /* planes: gathered rows; one record of every plane */
+    FILE** pfp;
+    int64_t npp, *pl_point;                                      /* with recorders: the plane_mine points compacted */
+    int32_t* pl_ids;                                             /* (ids, phi), and where each belongs in pbuf */
+    double* pl_phi;
+    double *w1, *w2, *k1, *k2;                                   /* 4D output; checkpoints out of snapshots */
+    int32_t wcnt, wfirst;
+    int64_t wgbase, wtotal;
+    int ckpt_number;                                             /* CheckpointNumber, io_checkpoint.c:38,126 */
+    hqh_recorder rec[HQH_NOUT];                                  /* [HQH_PLANES], [HQH_STATIONS] */
+    int32_t snap[HQH_NOUT];                                      /* [HQH_CKPT], [HQH_WAVE]: snapshot handles, -1: none */
+} hqh_run_state;
+
+static int hqh_recorder_open(hqh_run_state* st, int which, int32_t npoints, const int32_t* ids, const double* phi, int32_t derivs)
 {
-    if (sn->handle < 0) return next;
-    const int64_t from = step > sn->first_step ? step : sn->first_step;
-    const int64_t first = (from + sn->rate - 1) / sn->rate * sn->rate;
-    const int64_t full = first + (int64_t)sn->slots * sn->rate;                 /* the (slots + 1)-th due step */
-    return full < next ? (int32_t)full : next;
+    hqh_recorder* r = &st->rec[which];
+    r->ncomp = 3 * (1 + derivs); r->npoints = npoints;
+    int64_t cap = hq_cadence_count(st->due[which], st->step0, st->end);         /* due steps of the run */
+    if (cap == 0) return HQ_OK;
+    const int64_t row = 8 * (int64_t)npoints * r->ncomp;                        /* bytes per sample */
+    if (row > 0 && cap * row > HQH_RING_BYTES) cap = HQH_RING_BYTES / row > 0 ? HQH_RING_BYTES / row : 1;
+    r->cap = (int32_t)cap;
+    r->vals = (double*)malloc((size_t)(cap * row > 0 ? cap * row : 8));
+    r->steps = (int32_t*)malloc(sizeof(int32_t) * (size_t)cap);
+    if (!r->vals || !r->steps) return HQ_ERR_NOMEM;
+    hq_recorder_desc d;
+    memset(&d, 0, sizeof d);
+    d.npoints = npoints; d.ids = ids; d.phi = phi; d.rate = (int32_t)st->due[which].rate; d.derivs = derivs; d.capacity = r->cap;
+    int rc = hq_record_add(st->ctx, &d, &r->handle);
+    if (rc == HQ_OK) { st->dev[st->ndev].due = st->due[which]; st->dev[st->ndev++].room = cap; }
+    return rc;
 }
 
-/* slots = 0: hqh_solver_run_on; slots > 0: hqh_solver_run_async */
-static int hqh_run_impl(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0, int32_t nsteps,
-                        int32_t slots)
+static int hqh_snapshot_open(hqh_run_state* st, int which, int32_t first, int32_t count, int32_t fields)
 {
-    if (!ctx || !rp || nsteps < 0 || deltaT <= 0 || nharb < 0 || slots < 0) return HQ_ERR_ARG;
-    const int async = slots > 0;
-    int32_t win = rp->source_window > 0 ? rp->source_window : 256;
-    double* F = NULL;
-    double *u = NULL, *disp = NULL;
-    if (rp->nloaded > 0) {
-        F = (double*)malloc(sizeof(double) * 3 * (size_t)rp->nloaded * (size_t)win);
-        if (!F) return HQ_ERR_NOMEM;
+    hq_snapshot_desc d;
+    memset(&d, 0, sizeof d);
+    d.first = first; d.count = count; d.rate = (int32_t)st->due[which].rate; d.first_step = (int32_t)st->due[which].first_step;
+    d.fields = fields; d.slots = st->slots;
+    int rc = hq_snapshot_add(st->ctx, &d, &st->snap[which]);
+    if (rc == HQ_OK) { st->dev[st->ndev].due = st->due[which]; st->dev[st->ndev++].room = st->slots; }
+    return rc;
+}
+
+/* the device routes' due steps follow the context's own counter: the run must start where it stands */
+static int hqh_starts_at_context_step(const hqh_run_state* st)
+{
+    hq_info inf;
+    if (st->step0 < 0 || hq_get_info(st->ctx, &inf) != HQ_OK) return HQ_ERR_ARG;
+    return inf.step != st->step0 ? HQ_ERR_STATE : HQ_OK;
+}
+
+static int hqh_planes_open(hqh_run_state* st)
+{
+    const hqh_run_params* rp = st->rp;
+    for (int32_t i = 0; i < rp->nplanes; i++) st->npp += rp->plane_npoints[i];
+    const size_t n = (size_t)(st->npp ? st->npp : 1);
+    st->pu = (double*)malloc(sizeof(double) * 24 * n);
+    st->pbuf = (double*)calloc(n * 3, sizeof(double));
+    st->pfp = (FILE**)calloc((size_t)rp->nplanes, sizeof(FILE*));
+    if (!st->pu || !st->pbuf || !st->pfp) return HQ_ERR_NOMEM;
+    for (int32_t i = 0; i < rp->nplanes; i++) {
+        char path[1200];
+        snprintf(path, sizeof path, "%s/planedisplacements.%d", rp->plane_dir, i);
+        st->pfp[i] = fopen(path, st->step0 > 0 ? "ab" : "wb");  /* a restart continues the file */
+        if (!st->pfp[i]) return HQ_ERR_ARG;
     }
-    if (rp->checkpoint_rate > 0 && rp->checkpoint_dir != NULL) {
+    return HQ_OK;
+}
+
+/* stations and planes sampled on the device (hqh_run_params.device_recorders): no batch is cut at a print step */
+static int hqh_recorders_open(hqh_run_state* st)
+{
+    const hqh_run_params* rp = st->rp;
+    int rc = hqh_starts_at_context_step(st);
+    if (rc == HQ_OK && st->u)
+        rc = hqh_recorder_open(st, HQH_STATIONS, rp->nstations, rp->station_ids, rp->station_phi, rp->station_derivs);
+    if (rc != HQ_OK || !st->pfp) return rc;
+    const size_t n = (size_t)(st->npp ? st->npp : 1);
+    int64_t nm = 0;
+    st->pl_ids = (int32_t*)malloc(sizeof(int32_t) * 8 * n);
+    st->pl_phi = (double*)malloc(sizeof(double) * 8 * n);
+    st->pl_point = (int64_t*)malloc(sizeof(int64_t) * n);
+    if (!st->pl_ids || !st->pl_phi || !st->pl_point) return HQ_ERR_NOMEM;
+    for (int64_t q = 0; q < st->npp; q++) {
+        if (rp->plane_mine && !rp->plane_mine[q]) continue;
+        memcpy(st->pl_ids + 8 * nm, rp->plane_ids + 8 * q, sizeof(int32_t) * 8);
+        memcpy(st->pl_phi + 8 * nm, rp->plane_phi + 8 * q, sizeof(double) * 8);
+        st->pl_point[nm++] = q;
+    }
+    return hqh_recorder_open(st, HQH_PLANES, (int32_t)nm, st->pl_ids, st->pl_phi, 0);
+}
+
+/* hqh_solver_run_async: the 4D output and the checkpoints as field snapshots, fetched and written beside the steps */
+static int hqh_snapshots_open(hqh_run_state* st)
+{
+    const hqh_run_params* rp = st->rp;
+    const size_t n = (size_t)(st->nharb ? st->nharb : 1);
+    int rc = hqh_starts_at_context_step(st);
+    if (rc == HQ_OK && st->on[HQH_CKPT]) {                       /* first: at a step due for both it is launched, and fetched, first */
+        st->k1 = (double*)malloc(sizeof(double) * 3 * n);
+        st->k2 = (double*)malloc(sizeof(double) * 3 * n);
+        rc = st->k1 && st->k2 ? hqh_snapshot_open(st, HQH_CKPT, 0, st->nharb, HQ_SNAP_TM1 | HQ_SNAP_TM2) : HQ_ERR_NOMEM;
+    }
+    if (rc == HQ_OK && st->on[HQH_WAVE])
+        rc = hqh_snapshot_open(st, HQH_WAVE, st->wfirst, st->wcnt,
+                               (rp->wavefield_disp_file ? HQ_SNAP_TM1 : 0) | (rp->wavefield_vel_file ? HQ_SNAP_VEL : 0));
+    return rc;
+}
+
+/* slots = 0: hqh_solver_run_on; slots > 0: hqh_solver_run_async.  May fail part-way: hqh_run_close takes what there is */
+static int hqh_run_open(hqh_run_state* st, hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0,
+                        int32_t nsteps, int32_t slots)
+{
+    memset(st, 0, sizeof *st);
+    if (!ctx || !rp || nsteps < 0 || deltaT <= 0 || nharb < 0 || slots < 0) return HQ_ERR_ARG;
+    st->ctx = ctx; st->rp = rp; st->deltaT = deltaT; st->nharb = nharb; st->step0 = step0; st->end = step0 + nsteps;
+    st->slots = slots;
+    st->win = rp->source_window > 0 ? rp->source_window : 256;
+    for (int i = 0; i < HQH_NOUT; i++) { st->rec[i].handle = st->snap[i] = -1; st->due[i].rate = 1; st->due[i].first_step = step0; }
+    if (rp->nloaded > 0) {
+        st->F = (double*)malloc(sizeof(double) * 3 * (size_t)rp->nloaded * (size_t)st->win);
+        if (!st->F) return HQ_ERR_NOMEM;
+    }
+    st->on[HQH_CKPT] = rp->checkpoint_rate > 0 && rp->checkpoint_dir != NULL;
+    if (st->on[HQH_CKPT]) {
         /* checkpoint.out<N> holds one stripe per rank behind a common header (io_checkpoint.c:29-127): a
          * partition cannot write it alone with a groupsize-1 header.  Partitioned callers call
          * hqh_checkpoint_write themselves (rank, nranks, nharboredmax, a barrier after rank 0 created the file). */
         hq_info inf;
-        if (hq_get_info(ctx, &inf) != HQ_OK) { free(F); return HQ_ERR_ARG; }
-        if (inf.nranks > 1) { free(F); return HQ_ERR_STATE; }
+        if (hq_get_info(ctx, &inf) != HQ_OK) return HQ_ERR_ARG;
+        if (inf.nranks > 1) return HQ_ERR_STATE;
+        st->due[HQH_CKPT].rate = rp->checkpoint_rate; st->due[HQH_CKPT].first_step = (int64_t)step0 + 1;
     }
-    if (rp->nstations > 0 && rp->station_rate > 0 && rp->station_fn) {
-        if (rp->station_derivs < 0 || rp->station_derivs > 2) { free(F); return HQ_ERR_ARG; }
-        u = (double*)malloc(sizeof(double) * 24 * 3 * (size_t)rp->nstations);          /* tm1 | tm2 | tm3 rows */
-        disp = (double*)malloc(sizeof(double) * 3 * (size_t)(1 + rp->station_derivs) * (size_t)rp->nstations);
-        if (!u || !disp) { free(F); free(u); free(disp); return HQ_ERR_NOMEM; }
+    st->on[HQH_STATIONS] = rp->nstations > 0 && rp->station_rate > 0 && rp->station_fn;
+    if (st->on[HQH_STATIONS]) {
+        if (rp->station_derivs < 0 || rp->station_derivs > 2) return HQ_ERR_ARG;
+        st->due[HQH_STATIONS].rate = rp->station_rate;
+        st->u = (double*)malloc(sizeof(double) * 24 * 3 * (size_t)rp->nstations);
+        st->disp = (double*)malloc(sizeof(double) * 3 * (size_t)(1 + rp->station_derivs) * (size_t)rp->nstations);
+        if (!st->u || !st->disp) return HQ_ERR_NOMEM;
     }
-    /* output planes */
-    double *pu = NULL, *pbuf = NULL;
-    FILE** pfp = NULL;
-    int64_t npp = 0;
+    st->async = slots > 0;                                       /* from here on a failed open clears them too, as the run's end does */
     int rc = HQ_OK;
-    if (rp->nplanes > 0 && rp->plane_rate > 0 && rp->plane_dir) {
-        for (int32_t i = 0; i < rp->nplanes; i++) npp += rp->plane_npoints[i];
-        pu = (double*)malloc(sizeof(double) * 24 * (size_t)(npp ? npp : 1));
-        pbuf = (double*)calloc((size_t)(npp ? npp : 1) * 3, sizeof(double));
-        pfp = (FILE**)calloc((size_t)rp->nplanes, sizeof(FILE*));
-        if (!pu || !pbuf || !pfp) rc = HQ_ERR_NOMEM;
-        for (int32_t i = 0; i < rp->nplanes && rc == HQ_OK; i++) {
-            char path[1200];
-            snprintf(path, sizeof path, "%s/planedisplacements.%d", rp->plane_dir, i);
-            pfp[i] = fopen(path, step0 > 0 ? "ab" : "wb");     /* a restart continues the file */
-            if (!pfp[i]) rc = HQ_ERR_ARG;
-        }
+    st->on[HQH_PLANES] = rp->nplanes > 0 && rp->plane_rate > 0 && rp->plane_dir;
+    if (st->on[HQH_PLANES]) { st->due[HQH_PLANES].rate = rp->plane_rate; rc = hqh_planes_open(st); }
+    /* 4D wavefield files: the caller's stripe of them, or all of the one partition's nodes */
+    st->on[HQH_WAVE] = rp->wavefield_rate > 0 && (rp->wavefield_disp_file || rp->wavefield_vel_file);
+    st->wcnt = rp->wavefield_count > 0 ? rp->wavefield_count : nharb;
+    st->wfirst = rp->wavefield_count > 0 ? rp->wavefield_first_owned : 0;
+    st->wgbase = rp->wavefield_count > 0 ? rp->wavefield_base_gnid : 0;
+    st->wtotal = rp->wavefield_total_nodes > 0 ? rp->wavefield_total_nodes : nharb;
+    if (st->on[HQH_WAVE]) st->due[HQH_WAVE].rate = rp->wavefield_rate;
+    if (st->on[HQH_WAVE] && rc == HQ_OK) {
+        st->w1 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
+        st->w2 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
+        if (!st->w1 || !st->w2) rc = HQ_ERR_NOMEM;
     }
-    /* 4D wavefield files: whole-field download at the (rare) output steps */
-    const int do_wave = rp->wavefield_rate > 0 && (rp->wavefield_disp_file || rp->wavefield_vel_file);
-    double *w1 = NULL, *w2 = NULL;
-    if (do_wave && rc == HQ_OK) {
-        w1 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
-        w2 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
-        if (!w1 || !w2) rc = HQ_ERR_NOMEM;
+    st->dev_rec = rp->device_recorders != 0 && (st->u || st->pfp);
+    if (st->dev_rec && rc == HQ_OK) rc = hqh_recorders_open(st);
+    if (st->async && rc == HQ_OK && (st->on[HQH_WAVE] || st->on[HQH_CKPT])) rc = hqh_snapshots_open(st);
+    for (int i = 0; i < HQH_NOUT; i++) {                         /* the rest is the host's, and cuts the batches at its steps */
+        st->sync[i] = st->on[i] && !(i <= HQH_WAVE ? st->async : st->dev_rec);
+        if (st->sync[i]) st->sync_rates[st->nsync++] = st->due[i].rate;
     }
-    int32_t step = step0, end = step0 + nsteps, win_end = step0;
-    /* stations and planes sampled on the device (hqh_run_params.device_recorders): no batch is cut at a print step */
-    const int dev_rec = rp->device_recorders != 0 && (u || pfp);
-    hqh_recorder rst, rpl;
-    memset(&rst, 0, sizeof rst); memset(&rpl, 0, sizeof rpl);
-    rst.handle = rpl.handle = -1;
-    int32_t* pl_ids = NULL;                                      /* the planes' points that are plane_mine, compacted */
-    double* pl_phi = NULL;
-    int64_t* pl_point = NULL;                                    /* ... and where each belongs in pbuf */
-    if (dev_rec && rc == HQ_OK) {
-        hq_info inf;
-        if (step0 < 0 || hq_get_info(ctx, &inf) != HQ_OK) rc = HQ_ERR_ARG;
-        else if (inf.step != step0) rc = HQ_ERR_STATE;           /* the due steps follow the context's own counter */
-        if (rc == HQ_OK && u)
-            rc = hqh_recorder_open(ctx, &rst, rp->nstations, rp->station_ids, rp->station_phi, rp->station_rate,
-                                   rp->station_derivs, step0, end);
-        if (rc == HQ_OK && pfp) {
-            int64_t nm = 0;
-            pl_ids = (int32_t*)malloc(sizeof(int32_t) * 8 * (size_t)(npp ? npp : 1));
-            pl_phi = (double*)malloc(sizeof(double) * 8 * (size_t)(npp ? npp : 1));
-            pl_point = (int64_t*)malloc(sizeof(int64_t) * (size_t)(npp ? npp : 1));
-            if (!pl_ids || !pl_phi || !pl_point) rc = HQ_ERR_NOMEM;
-            for (int64_t q = 0; q < npp && rc == HQ_OK; q++) {
-                if (rp->plane_mine && !rp->plane_mine[q]) continue;
-                memcpy(pl_ids + 8 * nm, rp->plane_ids + 8 * q, sizeof(int32_t) * 8);
-                memcpy(pl_phi + 8 * nm, rp->plane_phi + 8 * q, sizeof(double) * 8);
-                pl_point[nm++] = q;
+    return rc;
+}
+
+/* frees what hqh_run_open made, on every path; `rc` is the run's result so far, and the first error wins */
+static int hqh_run_close(hqh_run_state* st, int rc)
+{
+    if (st->dev_rec) {
+        int rc2 = hq_record_clear(st->ctx);
+        if (rc == HQ_OK) rc = rc2;
+    }
+    if (st->async) {
+        int rc2 = hq_snapshot_clear(st->ctx);
+        if (rc == HQ_OK) rc = rc2;
+    }
+    if (st->pfp) for (int32_t i = 0; i < st->rp->nplanes; i++) if (st->pfp[i]) fclose(st->pfp[i]);
+    void* const owned[] = { st->F, st->u, st->disp, st->pu, st->pbuf, st->pfp, st->pl_ids, st->pl_phi, st->pl_point, st->w1, st->w2,
+                            st->k1, st->k2, st->rec[HQH_PLANES].vals, st->rec[HQH_PLANES].steps, st->rec[HQH_STATIONS].vals,
+                            st->rec[HQH_STATIONS].steps };
+    for (size_t i = 0; i < sizeof owned / sizeof owned[0]; i++) free(owned[i]);
+    return rc;
+}
+
+/* solver_write_checkpoint, :4277 -- checkpoint.out0 and .out1 in turn; from_snapshot: the oldest pending one's fields */
+static int hqh_checkpoint_out(hqh_run_state* st, int32_t step, int from_snapshot)
+{
+    char path[1200];
+    snprintf(path, sizeof path, "%s/checkpoint.out%d", st->rp->checkpoint_dir, st->ckpt_number);
+    st->ckpt_number = (st->ckpt_number + 1) % 2;
+    if (!from_snapshot) return hqh_checkpoint_write(st->ctx, path, step, 0, 1, st->nharb, st->nharb);
+    int rc = hq_snapshot_fetch(st->ctx, st->snap[HQH_CKPT], st->k1, st->k2, NULL, &step);
+    return rc != HQ_OK ? rc : hqh_checkpoint_write_fields(path, step, 0, 1, st->nharb, st->nharb, st->k1, st->k2);
+}
+
+/* solver_output_wavefield, :4278 -- from_snapshot: the oldest pending one's rows; else a whole-field download at the
+ * (rare) output step, the rows' velocities taken on the host as hqh_wavefield_write takes them */
+static int hqh_wavefield_out(hqh_run_state* st, int32_t step, int from_snapshot)
+{
+    const hqh_run_params* rp = st->rp;
+    const double *d = st->w1, *v = st->w2;
+    int rc;
+    if (from_snapshot) {
+        rc = hq_snapshot_fetch(st->ctx, st->snap[HQH_WAVE], rp->wavefield_disp_file ? st->w1 : NULL, NULL,
+                               rp->wavefield_vel_file ? st->w2 : NULL, &step);
+    } else {
+        rc = hq_download(st->ctx, st->w1, rp->wavefield_vel_file ? st->w2 : NULL);
+        d += 3 * (size_t)st->wfirst; v += 3 * (size_t)st->wfirst;
+        if (rc == HQ_OK && rp->wavefield_vel_file)
+            for (size_t i = 3 * (size_t)st->wfirst; i < 3 * ((size_t)st->wfirst + (size_t)st->wcnt); i++)
+                st->w2[i] = (st->w1[i] - st->w2[i]) / st->deltaT;
+    }
+    const int32_t out_step = step / rp->wavefield_rate;
+    if (rc == HQ_OK && rp->wavefield_disp_file)
+        rc = hqh_wavefield_write_block(rp->wavefield_disp_file, st->wtotal, out_step, st->wgbase, st->wcnt, d);
+    if (rc == HQ_OK && rp->wavefield_vel_file)
+        rc = hqh_wavefield_write_block(rp->wavefield_vel_file, st->wtotal, out_step, st->wgbase, st->wcnt, v);
+    return rc;
+}
+
+/* the next sample of a recorder's batch: its step (-1: none left), and the sample itself */
+static int32_t hqh_recorder_head(const hqh_recorder* r) { return r->at < r->n ? r->steps[r->at] : -1; }
+static const double* hqh_recorder_take(hqh_recorder* r) { return r->vals + (size_t)r->ncomp * (size_t)r->npoints * (size_t)r->at++; }
+
+/* solver_output_planes, :4279 -- one record into every plane's file: Old_planes_print (io_planes.c:176-200) over gathered
+ * rows, or from_recorder, the sums the device took */
+static int hqh_planes_out(hqh_run_state* st, int from_recorder)
+{
+    const hqh_run_params* rp = st->rp;
+    if (from_recorder) {
+        hqh_recorder* r = &st->rec[HQH_PLANES];
+        const double* v = hqh_recorder_take(r);
+        for (int32_t k = 0; k < r->npoints; k++) memcpy(st->pbuf + 3 * st->pl_point[k], v + 3 * (size_t)k, 3 * sizeof(double));
+    } else {
+        int rc = hq_gather(st->ctx, (int32_t)(st->npp * 8), rp->plane_ids, st->pu, NULL);
+        if (rc != HQ_OK) return rc;
+        for (int64_t s = 0; s < st->npp; s++) {
+            if (rp->plane_mine && !rp->plane_mine[s]) continue;
+            for (int d = 0; d < 3; d++) {
+                double acc = 0.0;
+                for (int c = 0; c < 8; c++) acc += rp->plane_phi[8 * s + c] * st->pu[(8 * s + c) * 3 + d];
+                st->pbuf[3 * s + d] = acc;
             }
-            if (rc == HQ_OK)
-                rc = hqh_recorder_open(ctx, &rpl, (int32_t)nm, pl_ids, pl_phi, rp->plane_rate, 0, step0, end);
         }
     }
-    int ckpt_number = 0;                                         /* CheckpointNumber, io_checkpoint.c:38,126 */
-    const int do_ckpt = rp->checkpoint_rate > 0 && rp->checkpoint_dir != NULL;
-    /* hqh_solver_run_async: the 4D output and the checkpoints as field snapshots, fetched and written beside the steps */
-    const int32_t wcnt = rp->wavefield_count > 0 ? rp->wavefield_count : nharb;
-    const int32_t wfirst = rp->wavefield_count > 0 ? rp->wavefield_first_owned : 0;
-    const int64_t wgbase = rp->wavefield_count > 0 ? rp->wavefield_base_gnid : 0;
-    const int64_t wtotal = rp->wavefield_total_nodes > 0 ? rp->wavefield_total_nodes : nharb;
-    hqh_snapshot swv = { -1, 1, 0, slots }, sck = { -1, 1, 0, slots };
-    double *k1 = NULL, *k2 = NULL;
-    if (async && rc == HQ_OK && (do_wave || do_ckpt)) {
-        hq_info inf;
-        if (step0 < 0 || hq_get_info(ctx, &inf) != HQ_OK) rc = HQ_ERR_ARG;
-        else if (inf.step != step0) rc = HQ_ERR_STATE;           /* the due steps follow the context's own counter */
-        hq_snapshot_desc d;
-        if (rc == HQ_OK && do_ckpt) {                            /* first: at a step due for both it is launched, and fetched, first */
-            k1 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
-            k2 = (double*)malloc(sizeof(double) * 3 * (size_t)(nharb ? nharb : 1));
-            if (!k1 || !k2) rc = HQ_ERR_NOMEM;
-            memset(&d, 0, sizeof d);
-            d.first = 0; d.count = nharb; d.rate = rp->checkpoint_rate; d.first_step = step0 + 1;   /* "not at step0" */
-            d.fields = HQ_SNAP_TM1 | HQ_SNAP_TM2; d.slots = slots;
-            sck.rate = d.rate; sck.first_step = d.first_step;
-            if (rc == HQ_OK) rc = hq_snapshot_add(ctx, &d, &sck.handle);
-        }
-        if (rc == HQ_OK && do_wave) {
-            memset(&d, 0, sizeof d);
-            d.first = wfirst; d.count = wcnt; d.rate = rp->wavefield_rate; d.first_step = 0;
-            d.fields = (rp->wavefield_disp_file ? HQ_SNAP_TM1 : 0) | (rp->wavefield_vel_file ? HQ_SNAP_VEL : 0);
-            d.slots = slots;
-            swv.rate = d.rate; swv.first_step = 0;
-            rc = hq_snapshot_add(ctx, &d, &swv.handle);
-        }
+    int64_t off = 0;
+    for (int32_t i = 0; i < rp->nplanes; i++) {
+        const size_t n = 3 * (size_t)rp->plane_npoints[i];
+        if (fwrite(st->pbuf + 3 * off, sizeof(double), n, st->pfp[i]) != n) return HQ_ERR_ARG;
+        off += rp->plane_npoints[i];
     }
-    while (step < end && rc == HQ_OK) {
-        if (do_ckpt && !async && step != step0 && step % rp->checkpoint_rate == 0) {   /* solver_write_checkpoint, :4277 */
-            char path[1200];
-            snprintf(path, sizeof path, "%s/checkpoint.out%d", rp->checkpoint_dir, ckpt_number);
-            rc = hqh_checkpoint_write(ctx, path, step, 0, 1, nharb, nharb);
-            if (rc != HQ_OK) break;
-            ckpt_number = (ckpt_number + 1) % 2;
+    return HQ_OK;
+}
+
+/* solver_output_stations, :4280 -- the callback gets the step's rows: from_recorder as the device took them, else
+ * interpolated here from gathered rows */
+static int hqh_stations_out(hqh_run_state* st, int32_t step, int from_recorder)
+{
+    const hqh_run_params* rp = st->rp;
+    const double* rows = st->disp;
+    if (from_recorder) {
+        step = hqh_recorder_head(&st->rec[HQH_STATIONS]);
+        rows = hqh_recorder_take(&st->rec[HQH_STATIONS]);
+    } else {
+        const int dv = rp->station_derivs;
+        const size_t blk = 24 * (size_t)rp->nstations;
+        double* u = st->u;
+        int rc = dv == 2 ? hq_gather3(st->ctx, rp->nstations * 8, rp->station_ids, u, u + blk, u + 2 * blk)
+                         : hq_gather(st->ctx, rp->nstations * 8, rp->station_ids, u, dv ? u + blk : NULL);
+        if (rc != HQ_OK) return rc;
+        for (int32_t s = 0; s < rp->nstations; s++)
+            hqh_station_kinematics(rp->station_phi + 8 * s, u + 24 * s, u + blk + 24 * s, u + 2 * blk + 24 * s,
+                                   st->deltaT, dv, st->disp + 3 * (size_t)(1 + dv) * s);
+    }
+    rp->station_fn(rp->station_user, step, rp->nstations, rows);
+    return HQ_OK;
+}
+
+/* what the host takes itself at `step`, in the reference's order (:4277-4280) */
+static int hqh_emit_due(hqh_run_state* st, int32_t step)
+{
+    int rc = HQ_OK;
+    for (int i = 0; i < HQH_NOUT && rc == HQ_OK; i++) {
+        if (!st->sync[i] || !hq_cadence_due(st->due[i], step)) continue;
+        rc = i == HQH_CKPT ? hqh_checkpoint_out(st, step, 0) : i == HQH_WAVE ? hqh_wavefield_out(st, step, 0)
+           : i == HQH_PLANES ? hqh_planes_out(st, 0) : hqh_stations_out(st, step, 0);
+    }
+    return rc;
+}
+
+/* solver_read_source_forces, :4282 -- the next window of the force table, from `step` on; returns where it ends */
+static int hqh_refill_source(hqh_run_state* st, int32_t step, int32_t* win_end)
+{
+    const hqh_run_params* rp = st->rp;
+    const int32_t n = st->end - step < st->win ? st->end - step : st->win;
+    if (rp->force_file) {
+        int rc = hqh_forcefile_read(rp->force_file, step, n, st->F);
+        if (rc != HQ_OK) return rc;
+    } else {
+        hqh_source_table(rp, st->deltaT, step, n, st->F);
+    }
+    *win_end = step + n;
+    return hq_set_source(st->ctx, rp->nloaded, rp->loaded_lnid, step, n, st->F);
+}
+
+/* the batch's snapshots, in step order, while the device works through the batch: each fetch waits for its own slot's
+ * copy only.  At a step due for both, the checkpoint first (:4277-4278) */
+static int hqh_drain_snapshots(hqh_run_state* st)
+{
+    for (;;) {
+        int32_t n, head[2] = { -1, -1 };
+        for (int i = HQH_CKPT; i <= HQH_WAVE; i++) {
+            if (st->snap[i] < 0) continue;
+            int rc = hq_snapshot_pending(st->ctx, st->snap[i], &n, NULL, &head[i]);
+            if (rc != HQ_OK) return rc;
         }
-        if (do_wave && !async && step % rp->wavefield_rate == 0) {   /* solver_output_wavefield, :4278 */
-            rc = hq_download(ctx, w1, rp->wavefield_vel_file ? w2 : NULL);
-            const int32_t cnt = rp->wavefield_count > 0 ? rp->wavefield_count : nharb;
-            const int32_t first = rp->wavefield_count > 0 ? rp->wavefield_first_owned : 0;
-            const int64_t gbase = rp->wavefield_count > 0 ? rp->wavefield_base_gnid : 0;
-            const int64_t total = rp->wavefield_total_nodes > 0 ? rp->wavefield_total_nodes : nharb;
-            if (rc == HQ_OK && rp->wavefield_disp_file)
-                rc = hqh_wavefield_write(rp->wavefield_disp_file, total, 1, step / rp->wavefield_rate, gbase, first,
-                                         cnt, w1, NULL, deltaT);
-            if (rc == HQ_OK && rp->wavefield_vel_file)
-                rc = hqh_wavefield_write(rp->wavefield_vel_file, total, 2, step / rp->wavefield_rate, gbase, first,
-                                         cnt, w1, w2, deltaT);
-            if (rc != HQ_OK) break;
-        }
-        if (pfp && !dev_rec && step % rp->plane_rate == 0) {     /* solver_output_planes, :4279 */
-            rc = hq_gather(ctx, (int32_t)(npp * 8), rp->plane_ids, pu, NULL);
-            if (rc != HQ_OK) break;
-            int64_t off = 0;
-            for (int32_t i = 0; i < rp->nplanes && rc == HQ_OK; i++) {
-                for (int64_t s = off; s < off + rp->plane_npoints[i]; s++) {
-                    if (rp->plane_mine && !rp->plane_mine[s]) continue;
-                    for (int d = 0; d < 3; d++) {                /* Old_planes_print, io_planes.c:176-200 */
-                        double acc = 0.0;
-                        for (int c = 0; c < 8; c++) acc += rp->plane_phi[8 * s + c] * pu[(8 * s + c) * 3 + d];
-                        pbuf[3 * s + d] = acc;
-                    }
-                }
-                size_t n = 3 * (size_t)rp->plane_npoints[i];
-                if (fwrite(pbuf + 3 * off, sizeof(double), n, pfp[i]) != n) rc = HQ_ERR_ARG;
-                off += rp->plane_npoints[i];
-            }
-            if (rc != HQ_OK) break;
-        }
-        if (u && !dev_rec && step % rp->station_rate == 0) {     /* solver_output_stations, :4280 */
-            const int dv = rp->station_derivs;
-            const size_t blk = 24 * (size_t)rp->nstations;
-            rc = dv == 2 ? hq_gather3(ctx, rp->nstations * 8, rp->station_ids, u, u + blk, u + 2 * blk)
-                         : hq_gather(ctx, rp->nstations * 8, rp->station_ids, u, dv ? u + blk : NULL);
-            if (rc != HQ_OK) break;
-            for (int32_t s = 0; s < rp->nstations; s++)
-                hqh_station_kinematics(rp->station_phi + 8 * s, u + 24 * s, u + blk + 24 * s, u + 2 * blk + 24 * s,
-                                       deltaT, dv, disp + 3 * (size_t)(1 + dv) * s);
-            rp->station_fn(rp->station_user, step, rp->nstations, disp);
-        }
-        if (F && step >= win_end) {                              /* solver_read_source_forces, :4282 */
-            int32_t n = end - step < win ? end - step : win;
-            if (rp->force_file) {
-                rc = hqh_forcefile_read(rp->force_file, step, n, F);
-                if (rc != HQ_OK) break;
-            } else {
-                hqh_source_table(rp, deltaT, step, n, F);
-            }
-            rc = hq_set_source(ctx, rp->nloaded, rp->loaded_lnid, step, n, F);
-            if (rc != HQ_OK) break;
-            win_end = step + n;
-        }
-        int32_t next = end;
-        if (F && win_end < next) next = win_end;
-        if (u && !dev_rec) {
-            int32_t ns = (step / rp->station_rate + 1) * rp->station_rate;
-            if (ns < next) next = ns;
-        }
-        if (pfp && !dev_rec) {
-            int32_t ns = (step / rp->plane_rate + 1) * rp->plane_rate;
-            if (ns < next) next = ns;
-        }
-        if (do_ckpt && !async) {
-            int32_t ns = (step / rp->checkpoint_rate + 1) * rp->checkpoint_rate;
-            if (ns < next) next = ns;
-        }
-        if (do_wave && !async) {
-            int32_t ns = (step / rp->wavefield_rate + 1) * rp->wavefield_rate;
-            if (ns < next) next = ns;
-        }
-        if (async) {                                             /* ... and where the snapshots' slots would run out */
-            next = hqh_snapshot_limit(&sck, step, next);
-            next = hqh_snapshot_limit(&swv, step, next);
-        }
-        if (dev_rec) {                                           /* ... and where a ring would fill */
-            next = hqh_recorder_limit(&rst, step, next);
-            next = hqh_recorder_limit(&rpl, step, next);
-        }
-        rc = hq_run(ctx, next - step);
+        const int which = hq_merge_next(head[HQH_CKPT], head[HQH_WAVE]);
+        if (which < 0) return HQ_OK;
+        int rc = which == 0 ? hqh_checkpoint_out(st, -1, 1) : hqh_wavefield_out(st, -1, 1);
+        if (rc != HQ_OK) return rc;
+    }
+}
+
+/* the batch's samples, in step order; at a step both print at, the planes first (:4279-4280) */
+static int hqh_drain_recorders(hqh_run_state* st)
+{
+    int rc = HQ_OK, which;
+    for (int i = HQH_STATIONS; i >= HQH_PLANES && rc == HQ_OK; i--) {
+        hqh_recorder* r = &st->rec[i];
+        r->n = r->at = 0;
+        if (r->handle >= 0) rc = hq_record_fetch(st->ctx, r->handle, r->cap, r->vals, r->steps, &r->n);
+    }
+    while (rc == HQ_OK && (which = hq_merge_next(hqh_recorder_head(&st->rec[HQH_PLANES]), hqh_recorder_head(&st->rec[HQH_STATIONS]))) >= 0)
+        rc = which == 0 ? hqh_planes_out(st, 1) : hqh_stations_out(st, -1, 1);
+    return rc;
+}
+
+static int hqh_run_impl(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0, int32_t nsteps,
+                        int32_t slots)
+{
+    hqh_run_state st;
+    int rc = hqh_run_open(&st, ctx, deltaT, nharb, rp, step0, nsteps, slots);
+    int32_t step = step0, win_end = step0;
+    while (rc == HQ_OK && step < st.end) {
+        rc = hqh_emit_due(&st, step);                                                          /* :4277-4280 */
+        if (rc == HQ_OK && st.F && step >= win_end) rc = hqh_refill_source(&st, step, &win_end);   /* :4282 */
+        if (rc != HQ_OK) break;
+        const int32_t next = (int32_t)hq_batch_end(step, st.end, st.F ? win_end : st.end, st.sync_rates, st.nsync, st.dev, st.ndev);
+        rc = hq_run(ctx, next - step);                                                         /* the physics of [step, next) */
         step = next;
-        /* the batch's snapshots, in step order, while the device works through the batch: each fetch waits for its own
-         * slot's copy only.  At a step due for both, the checkpoint first (:4277-4278) */
-        while (async && rc == HQ_OK) {
-            int32_t nck = 0, nwv = 0, sck_step = -1, swv_step = -1, got = -1;
-            if (sck.handle >= 0) rc = hq_snapshot_pending(ctx, sck.handle, &nck, NULL, &sck_step);
-            if (rc == HQ_OK && swv.handle >= 0) rc = hq_snapshot_pending(ctx, swv.handle, &nwv, NULL, &swv_step);
-            if (rc != HQ_OK || (nck == 0 && nwv == 0)) break;
-            if (nck > 0 && (nwv == 0 || sck_step <= swv_step)) {
-                char path[1200];
-                snprintf(path, sizeof path, "%s/checkpoint.out%d", rp->checkpoint_dir, ckpt_number);
-                rc = hq_snapshot_fetch(ctx, sck.handle, k1, k2, NULL, &got);
-                if (rc == HQ_OK) rc = hqh_checkpoint_write_fields(path, got, 0, 1, nharb, nharb, k1, k2);
-                ckpt_number = (ckpt_number + 1) % 2;
-            } else {
-                rc = hq_snapshot_fetch(ctx, swv.handle, rp->wavefield_disp_file ? w1 : NULL, NULL,
-                                       rp->wavefield_vel_file ? w2 : NULL, &got);
-                if (rc == HQ_OK && rp->wavefield_disp_file)
-                    rc = hqh_wavefield_write_block(rp->wavefield_disp_file, wtotal, got / rp->wavefield_rate, wgbase, wcnt, w1);
-                if (rc == HQ_OK && rp->wavefield_vel_file)
-                    rc = hqh_wavefield_write_block(rp->wavefield_vel_file, wtotal, got / rp->wavefield_rate, wgbase, wcnt, w2);
-            }
-        }
-        if (dev_rec && rc == HQ_OK) {
-            /* the batch's samples, in step order; at a step both print at, the planes first (:4279-4280) */
-            int32_t nst = 0, npl = 0, i = 0, j = 0;
-            if (rst.handle >= 0) rc = hq_record_fetch(ctx, rst.handle, rst.cap, rst.vals, rst.steps, &nst);
-            if (rc == HQ_OK && rpl.handle >= 0) rc = hq_record_fetch(ctx, rpl.handle, rpl.cap, rpl.vals, rpl.steps, &npl);
-            while (rc == HQ_OK && (i < nst || j < npl)) {
-                if (j < npl && (i >= nst || rpl.steps[j] <= rst.steps[i])) {
-                    const double* v = rpl.vals + 3 * (size_t)rpl.npoints * (size_t)j;
-                    for (int32_t k = 0; k < rpl.npoints; k++)
-                        memcpy(pbuf + 3 * pl_point[k], v + 3 * (size_t)k, 3 * sizeof(double));
-                    int64_t off = 0;
-                    for (int32_t p = 0; p < rp->nplanes && rc == HQ_OK; p++) {
-                        size_t n = 3 * (size_t)rp->plane_npoints[p];
-                        if (fwrite(pbuf + 3 * off, sizeof(double), n, pfp[p]) != n) rc = HQ_ERR_ARG;
-                        off += rp->plane_npoints[p];
-                    }
-                    j++;
-                } else {
-                    rp->station_fn(rp->station_user, rst.steps[i], rp->nstations,
-                                   rst.vals + (size_t)rst.ncomp * (size_t)rst.npoints * (size_t)i);
-                    i++;
-                }
-            }
-        }
+        if (rc == HQ_OK && st.async) rc = hqh_drain_snapshots(&st);
+        if (rc == HQ_OK && st.dev_rec) rc = hqh_drain_recorders(&st);
     }
     if (rc == HQ_OK) rc = hq_sync(ctx);
-    if (dev_rec) {
-        int rc2 = hq_record_clear(ctx);
-        if (rc == HQ_OK) rc = rc2;
-    }
-    if (async) {
-        int rc2 = hq_snapshot_clear(ctx);
-        if (rc == HQ_OK) rc = rc2;
-    }
-    if (pfp) for (int32_t i = 0; i < rp->nplanes; i++) if (pfp[i]) fclose(pfp[i]);
-    free(F); free(u); free(disp); free(pu); free(pbuf); free(pfp); free(w1); free(w2);
-    free(rst.vals); free(rst.steps); free(rpl.vals); free(rpl.steps); free(pl_ids); free(pl_phi); free(pl_point);
-    free(k1); free(k2);
-    return rc;
+    return hqh_run_close(&st, rc);
 }
 
 int hqh_solver_run_on(hq_ctx* ctx, double deltaT, int32_t nharb, const hqh_run_params* rp, int32_t step0, int32_t nsteps)

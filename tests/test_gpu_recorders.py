@@ -22,6 +22,7 @@ all 13 500 values.  So the bit-for-bit comparisons below are made on one traject
     step, u(t - dt) that of the step before, u(t - 2 dt) that of two steps before; hqh_station_kinematics sums them on the host.
 Two separately run solvers are compared with the project's parity bar (1e-9 relative L-inf), not bit for bit."""
 import ctypes
+import shutil
 
 import numpy as np
 import pytest
@@ -556,3 +557,100 @@ def test_f32_library_records_doubles_of_the_widened_floats(c1):
     """libhq_solver_f32.so keeps the state in floats; the recorder widens every value to double BEFORE the sums, so its
     samples are the host kinematics of the hq_gather3 floats widened to double, bit for bit."""
     _cadence(c1, "f32")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. all four outputs at once, on every route
+# ---------------------------------------------------------------------------------------------------------------------
+
+def test_all_outputs_on_every_route(tmp_path):
+    """The C1 box driven by the reference's force file with every output of the runner asked for at once -- stations
+    (with velocities and accelerations) every 2 steps, planes every 3, both 4D files every 4, checkpoints every 5 -- over
+    24 steps in a call of 7 and a call of 17, on identical solvers: device_recorders 0 / 1 x hqh_solver_run_on /
+    hqh_solver_run_async(slots = 1).  Every route hands on the same steps in the same order; the values are those of the
+    synchronous host route to the bars the tests of each output apply (two solver runs: module docstring), the 4D and
+    checkpoint headers byte for byte; and no route leaves a recorder or a snapshot on its solver."""
+    from tests.test_gpu_snapshots import TOL as SNAP_TOL, _checkpoint, _payload
+    g, gp = H.load("c1_wavefield"), H.load("c1_planes")
+    box = host.Box(H.C1_NX, H.C1_NY, H.C1_NZ, H.C1_H, 1e-3, 5.0)
+    N, E = box.info["nharbored"], box.info["lenum"]
+    ff = tmp_path / "force_process.0"
+    host.forcefile_write(str(ff), g["loaded_lnid"], g["forces"])
+    st_ids, st_phi, mine = box.stations(H.C1_STATIONS)
+    assert mine.all()
+    lonc, latc = gp["surface_corners_lon_lat"][:, 0], gp["surface_corners_lon_lat"][:, 1]
+    planes = []
+    for lat, lon, depth, ds, ns, dd, nd, strike, dip in gp["plane_specs"]:
+        x, y = host.domain_coords(lon, lat, lonc, latc, gp["domain_xyz"][0], gp["domain_xyz"][1])
+        ids, phi, mine = box.stations(host.plane_points((x, y, depth), ds, int(ns), dd, int(nd), strike, dip))
+        assert mine.all()
+        planes.append((ids, phi))
+    made = {}
+    for q, name in (("disp", "displacement"), ("vel", "velocity")):
+        made[q] = str(tmp_path / (q + ".h4d"))
+        host.wavefield_create(made[q], name, N, E, (1000.0, 1000.0, 500.0), 1000.0 / 2 ** 30, 1e-3, 4, 24)
+    routes = [(dev, runner) for runner in ("sync", "async") for dev in (0, 1)]
+    calls, dirs, nbytes = {}, {}, {}
+    for route in routes:
+        dev, runner = route
+        d = tmp_path / ("%s%d" % (runner, dev))
+        d.mkdir()
+        dirs[route], calls[route] = d, []
+        for q in made:
+            shutil.copy(made[q], str(d / (q + ".h4d")))
+        s = box.create_solver()
+        rp = box.run_params(loaded=g["loaded_lnid"], force_file=str(ff), source_window=8, device_recorders=dev,
+                            station_ids=st_ids, station_phi=st_phi, station_rate=2, station_derivs=2,
+                            station_fn=lambda step, vals, route=route: calls[route].append((step, vals)),
+                            planes=planes, plane_rate=3, plane_dir=str(d),
+                            wavefield_rate=4, wavefield_disp_file=str(d / "disp.h4d"), wavefield_vel_file=str(d / "vel.h4d"),
+                            wavefield_total_nodes=N, checkpoint_rate=5, checkpoint_dir=str(d))
+        for step0, nsteps in ((0, 7), (7, 17)):
+            assert s.info()["step"] == step0
+            if runner == "sync":
+                box.solver_run(s, rp, step0, nsteps)
+            else:
+                box.solver_run_async(s, rp, step0, nsteps, slots=1)
+        assert s.info()["step"] == 24
+        nbytes[route] = s.info()["device_bytes"]
+        with pytest.raises(ha.HqError):
+            s.record_pending(0)                          # the runner left no recorder behind
+        with pytest.raises(ha.HqError):
+            s.snapshot_pending(0)                        # ... and no snapshot
+        s.close()
+    box.close()
+    base = (0, "sync")
+    want = np.array([c[1] for c in calls[base]])
+    assert want.shape == (12, 5, 9) and np.abs(want).max() > 0
+    for route in routes:
+        assert nbytes[route] == nbytes[base], route
+        # stations: the callback's steps, then its values per column group
+        assert [c[0] for c in calls[route]] == list(range(0, 24, 2)), route
+        got = np.array([c[1] for c in calls[route]])
+        for k in range(3):
+            err = H.rel_linf(got[:, :, 3 * k:3 * k + 3], want[:, :, 3 * k:3 * k + 3])
+            print("%s stations, column group %d: %.3e" % (route, k, err))
+            assert err < TOL
+        # planes: eight records (steps 0, 3, ..., 21) in every file, the second call's appended to the first's
+        for i, (ids, _) in enumerate(planes):
+            a = (dirs[base] / ("planedisplacements.%d" % i)).read_bytes()
+            b = (dirs[route] / ("planedisplacements.%d" % i)).read_bytes()
+            assert len(a) == len(b) == 8 * len(ids) * 24, (route, i)
+            err = H.rel_linf(np.frombuffer(b, "<f8"), np.frombuffer(a, "<f8"))
+            print("%s plane %d: %.3e" % (route, i, err))
+            assert err < TOL
+        # 4D files: the created header untouched, six output steps (0, 4, ..., 20)
+        for q in made:
+            ha_, a = _payload(str(dirs[base] / (q + ".h4d")), N)
+            hb_, b = _payload(str(dirs[route] / (q + ".h4d")), N)
+            assert ha_ == hb_ == open(made[q], "rb").read()[:136]
+            assert a.shape == b.shape == (6, N, 3) and np.abs(a[1:]).max() > 0
+            for k in range(6):
+                err = H.rel_linf(b[k], a[k]) if np.abs(a[k]).max() > 0 else float(np.abs(b[k]).max())
+                print("%s %s output step %d: %.3e" % (route, q, k, err))
+                assert err < SNAP_TOL
+        # checkpoints: the second call wrote steps 10, 15, 20 into .out0, .out1, .out0 (the first one step 5 into .out0)
+        for n, step in (("checkpoint.out0", 20), ("checkpoint.out1", 15)):
+            sa, sb = _checkpoint(str(dirs[base] / n), N), _checkpoint(str(dirs[route] / n), N)
+            assert sa[0] == sb[0] and list(np.frombuffer(sb[0], "<i4")) == [1, step, N], (route, n)
+            assert H.rel_linf(sb[1], sa[1]) < SNAP_TOL and H.rel_linf(sb[2], sa[2]) < SNAP_TOL
