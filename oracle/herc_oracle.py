@@ -513,9 +513,11 @@ def multi_rank_init(parts, edata_by_rank, face_by_rank, dt, freq, **kw):
     return ets, nts
 
 
-def multi_rank_run(parts, ets, nts, tm1s, tm2s, step0, nsteps, dt, loaded, forces):
+def multi_rank_run(parts, ets, nts, tm1s, tm2s, step0, nsteps, dt, loaded, forces, distribute=None):
     """solver_run (psolve.c:4265-4319) for all ranks in lockstep; tm1s/tm2s are the
-    reference's pre-swap arrays per rank, updated in place."""
+    reference's pre-swap arrays per rank, updated in place.
+    distribute: per-rank hanging-node tables for the DISTRIBUTION of the forces alone (None: every rank's own table, as
+    the reference does it) -- for tests that break that pass on purpose."""
     real = tm1s[0].dtype                  # solver_float: the records of every exchange have it (psolve.c:4985-5073)
     L = lib(real)
     K1, K2 = compute_K()
@@ -533,9 +535,10 @@ def multi_rank_run(parts, ets, nts, tm1s, tm2s, step0, nsteps, dt, loaded, force
             L.ho_addforce_effective(c64(n_e), _p(p["lnid"]), _p(et), _p(u1), _p(f), 1)
             L.ho_damping_addforce(c64(n_e), _p(p["lnid"]), _p(et), _p(u1), _p(u2), _p(K1), _p(K2), _p(f), 1)
         _exchange_sim(parts, frc, "dn_sched", True)             # :4298
-        for p, f in zip(parts, frc):                            # :4299
-            if len(p["dangling"][0]):
-                compute_adjust(f, 0, p["dangling"])
+        for r, (p, f) in enumerate(zip(parts, frc)):            # :4299
+            dn = p["dangling"] if distribute is None else distribute[r]
+            if len(dn[0]):
+                compute_adjust(f, 0, dn)
         _exchange_sim(parts, frc, "an_sched", True)             # :4301
         for p, nt, u1, u2, f in zip(parts, nts, a, b, frc):     # :4305
             L.ho_compute_displacement(c64(len(p["nodes"])), _p(nt), _p(u1), _p(u2), _p(f), None)

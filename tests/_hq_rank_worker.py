@@ -4,6 +4,8 @@ engine's host-staged transport (hq_comm_init_host) and torch.distributed's gloo,
 device through the IPC transport (hq_comm_ipc_export / hq_comm_init_ipc) with gloo only for the set-up all-gather;
 gloo stands in for the MPI of the reference's world (psolve.c:7344-7389 `mpiexec -np N`; schedule_senddata psolve.c:4945-5079).  Everything else is
 the product path: C host side for the partition, hq_create / hq_set_source / hq_run on the device.
+Kind "step" (tests/test_gpu_partition_step.py): the rank's tables, schedules and both fields come from <outdir>/rank<r>_in.npz
+as the parent wrote them.
 Writes this rank's final fields to <outdir>/rank<r>.npz."""
 import os
 import sys
@@ -27,13 +29,31 @@ def gloo_exchange(recvs, sends, tag):
         r.wait()
 
 
+def solver_from_file(path, rank, world):
+    """ha.Solver on one rank's rank<r>_in.npz: lnid, etable, ntable, dt, tm1, tm2, node_xyz, the hanging-node table
+    (dn_ids, dn_ptr, dn_anchors), the four message lists ({an,dn}_{c,s}_{peer,ptr,map}), precision.  -> (solver, gid)"""
+    z = np.load(path)
+
+    def messengers(name):
+        peer, ptr, flat = z[name + "_peer"], z[name + "_ptr"], z[name + "_map"]
+        return [(int(peer[i]), np.array(flat[ptr[i]:ptr[i + 1]], np.int32)) for i in range(len(peer))]
+    sched = {w: {k: messengers("%s_%s" % (w, k)) for k in ("c", "s")} for w in ("an", "dn")}
+    s = ha.Solver(z["lnid"], z["etable"], z["ntable"], float(z["dt"]), tm1=z["tm1"], tm2=z["tm2"], node_xyz=z["node_xyz"],
+                  dangling=(z["dn_ids"], z["dn_ptr"], z["dn_anchors"]), an_sched=sched["an"], dn_sched=sched["dn"], rank=rank,
+                  nranks=world, variant=ha.HQ_VARIANT_PATCH, precision=str(z["precision"]))
+    return s, z["gid"].astype(np.int64)
+
+
 def main():
     outdir, kind, nsteps = sys.argv[1], sys.argv[2], int(sys.argv[3])
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     dist.init_process_group("gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
     rng = np.random.default_rng(4321)
-    if kind == "box":
+    b, F, loaded = None, None, np.zeros(0, np.int32)
+    if kind == "step":
+        s, gid = solver_from_file(os.path.join(outdir, "rank%d_in.npz" % rank), rank, world)
+    elif kind == "box":
         nx, ny, nz, h, dt, freq = 64, 64, 32, 15.0, 3e-4, 30.0
         b = host.Box(nx, ny, nz, h, dt, freq, rank=rank, nranks=world)
         ijk = b.node_ijk.astype(np.int64)
@@ -64,15 +84,20 @@ def main():
         ref = H.two_level_mesh(16, 8, 6, 3)
         b = host.OctBox(16, 8, 6, 3, 31.25, ref["dt"], 5.0, rank=rank, nranks=world)
         gid, Ng, loaded, F = b.gid.astype(np.int64), ref["N"], np.zeros(0, np.int32), None
-    g1 = rng.uniform(-1, 1, (Ng, 3)) * 1e-3
-    g2 = g1 + rng.uniform(-1, 1, (Ng, 3)) * 1e-6
-    if kind == "basin":
+    if kind != "step":
+        g1 = rng.uniform(-1, 1, (Ng, 3)) * 1e-3
+        g2 = g1 + rng.uniform(-1, 1, (Ng, 3)) * 1e-6
+    if kind == "step":
+        pass
+    elif kind == "basin":
         g1[:], g2[:] = 0.0, 0.0
     elif kind != "box":
         from oracle import herc_oracle as ho                # (checker-side helper: hanging rows = means of their anchors)
         ho.compute_adjust(g1, 1, ref["dangling"])
         ho.compute_adjust(g2, 1, ref["dangling"])
-    if os.environ.get("HQ_TEST_SWAP_RANK") == str(rank):
+    if kind == "step":
+        pass
+    elif os.environ.get("HQ_TEST_SWAP_RANK") == str(rank):
         # a deliberately WRONG schedule on this rank: two records of one c-list messenger swapped, so that the owner adds
         # them to the wrong nodes -- what HQ_DEBUG_HALO exists to catch (the parent expects the run to fail)
         sch = b.schedules()
@@ -103,11 +128,13 @@ def main():
         open(os.path.join(outdir, "rank%d.err" % rank), "w").write(failed)
     tm1, tm2 = s.download()
     info = s.info()
-    np.savez(os.path.join(outdir, "rank%d.npz" % rank), gid=gid, tm1=tm1, tm2=tm2, brick_nodes=info["brick_nodes"],
+    nonfinite = -1 if failed else s.check_finite()
+    np.savez(os.path.join(outdir, "rank%d.npz" % rank), gid=gid, tm1=tm1, tm2=tm2, brick_nodes=info["brick_nodes"], nonfinite=nonfinite,
              kernel=s.dominant_kernel(), transport=info["transport"], ipc_arena_coarse=info["ipc_arena_coarse"],
              ipc_arena_kind=info["ipc_arena_kind"], debug_halo=info["debug_halo"])
     s.close()
-    b.close()
+    if b is not None:
+        b.close()
     dist.barrier()
     dist.destroy_process_group()
     if failed:
