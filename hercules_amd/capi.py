@@ -22,8 +22,10 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_stencil_coefficients", "hq_brick_plan_check", "hq_brick_plan_check_n", "hq_comm_init_host",
            "hq_comm_ipc_export", "hq_comm_init_ipc", "hq_comm_init_loopback",
            "hq_record_add", "hq_record_pending", "hq_record_fetch", "hq_record_clear",
-           "hq_snapshot_add", "hq_snapshot_pending", "hq_snapshot_fetch", "hq_snapshot_clear"]
+           "hq_snapshot_add", "hq_snapshot_pending", "hq_snapshot_fetch", "hq_snapshot_clear",
+           "hq_peak_add", "hq_peak_fetch", "hq_peak_load", "hq_peak_reset", "hq_peak_clear"]
 HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
+HQ_PEAK_DISP, HQ_PEAK_VEL, HQ_PEAK_ACC = 1, 2, 4
 
 
 class HqError(RuntimeError):
@@ -68,6 +70,12 @@ class _RecorderDesc(ctypes.Structure):
 class _SnapshotDesc(ctypes.Structure):
     _fields_ = [("first", ctypes.c_int32), ("count", ctypes.c_int32), ("rate", ctypes.c_int32),
                 ("first_step", ctypes.c_int32), ("fields", ctypes.c_int32), ("slots", ctypes.c_int32)]
+
+
+class _PeakDesc(ctypes.Structure):
+    _fields_ = [("npoints", ctypes.c_int32), ("nodes_per_point", ctypes.c_int32), ("ids", ctypes.c_void_p),
+                ("phi", ctypes.c_void_p), ("rate", ctypes.c_int32), ("first_step", ctypes.c_int32),
+                ("quantities", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class _Info(ctypes.Structure):
@@ -440,6 +448,66 @@ class Solver:
         """hq_snapshot_clear: wait, then drop every snapshot of the context and its memory."""
         _check(self._lib.hq_snapshot_clear(self._h), self._lib)
         self._snapshots = {}
+
+    def peak_add(self, ids, phi=None, rate=1, first_step=0, quantities=HQ_PEAK_VEL):
+        """hq_peak_add: a peak-motion tracker.  phi [n,8] with ids [n,8]: points inside elements, as record_add's; phi
+        None: ids [n] are single nodes (a surface map).  A sample is folded in at the head of every step s >= first_step
+        with s % rate == 0; `quantities` a mask of HQ_PEAK_DISP | VEL | ACC.  Returns its handle."""
+        if phi is None:
+            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32)
+            k = 1
+        else:
+            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
+            phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
+            if len(ids) != len(phi):
+                raise HqError("peak_add: %d rows of ids, %d of phi" % (len(ids), len(phi)))
+            k = 8
+        d = _PeakDesc(len(ids), k, ids.ctypes.data, None if phi is None else phi.ctypes.data, int(rate), int(first_step),
+                      int(quantities), 0)
+        h = ctypes.c_int32(-1)
+        _check(self._lib.hq_peak_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
+        if not hasattr(self, "_peaks"):
+            self._peaks = {}
+        self._peaks[h.value] = (len(ids), bin(int(quantities) & 7).count("1"))
+        return h.value
+
+    def _peak_shape(self, handle):
+        if handle not in getattr(self, "_peaks", {}):
+            raise HqError("unknown peak tracker handle %r" % (handle,))
+        return self._peaks[handle]
+
+    def peak_fetch(self, handle):
+        """hq_peak_fetch: (peaks [npoints, nq, 5] float64, when [npoints, nq, 2] int32, nsamples) -- per quantity of the
+        mask max |x|, |y|, |z|, the horizontal and the total SQUARED, and the steps the last two were last raised at (-1:
+        never).  Waits for the enqueued steps; the state stays on the device."""
+        npoints, nq = self._peak_shape(handle)
+        peaks = np.zeros((npoints, nq, 5))
+        when = np.full((npoints, nq, 2), -1, np.int32)
+        n = ctypes.c_int64()
+        pad = np.zeros(1)                                       # (an empty array has no address worth passing)
+        _check(self._lib.hq_peak_fetch(self._h, ctypes.c_int32(handle), _ptr(peaks if peaks.size else pad),
+                                       _ptr(when if when.size else pad), ctypes.byref(n)), self._lib)
+        return peaks, when, int(n.value)
+
+    def peak_load(self, handle, peaks, when, nsamples):
+        """hq_peak_load: put back what peak_fetch returned (a run that restarts from a checkpoint)."""
+        npoints, nq = self._peak_shape(handle)
+        peaks = np.ascontiguousarray(peaks, np.float64)
+        when = np.ascontiguousarray(when, np.int32)
+        if peaks.shape != (npoints, nq, 5) or when.shape != (npoints, nq, 2):
+            raise HqError("peak_load: the arrays are not those of peak_fetch")
+        pad = np.zeros(1)
+        _check(self._lib.hq_peak_load(self._h, ctypes.c_int32(handle), _ptr(peaks if peaks.size else pad),
+                                      _ptr(when if when.size else pad), ctypes.c_int64(int(nsamples))), self._lib)
+
+    def peak_reset(self, handle):
+        """hq_peak_reset: peaks 0, when -1, nsamples 0."""
+        _check(self._lib.hq_peak_reset(self._h, ctypes.c_int32(handle)), self._lib)
+
+    def peak_clear(self):
+        """hq_peak_clear: drop every tracker of the context and its device memory."""
+        _check(self._lib.hq_peak_clear(self._h), self._lib)
+        self._peaks = {}
 
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)

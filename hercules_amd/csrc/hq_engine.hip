@@ -42,6 +42,7 @@
 #include "hq_kernels.h"
 #include "hq_opts.h"
 #include "hq_cadence.h"
+#include "hq_peak.h"
 #include "hq_patch.h"
 #include "hq_brick.h"
 
@@ -284,6 +285,22 @@ struct hq_ctx {
     std::vector<hq_recorder> recs;
     int32_t rec_next_id = 0;
     hipEvent_t ev_recorded = nullptr;
+    /* peak-motion trackers (hq_peak_add): a running state per point updated in place by hq_k_peak -- no ring, no pending
+     * samples, nothing for hq_run to count.  ev_peaked exists from the first hq_peak_add on: on a due step of a tracker
+     * that reads u(t - 2 dt) (HQ_PEAK_ACC) the streams whose kernels overwrite that buffer wait for it, as for ev_recorded */
+    struct hq_peak_tracker {
+        int32_t id = 0, np = 0, K = 8, quantities = 0, nq = 0;
+        hq_cadence due = { 1, 0 };
+        int64_t nsamples = 0;         /* due steps folded or enqueued so far: accounted here, from `step` alone */
+        int64_t bytes = 0;
+        int32_t* d_ids = nullptr;     /* [K][np] device numbering */
+        double* d_phi = nullptr;      /* [8][np]; NULL for K = 1 */
+        double* d_pk = nullptr;       /* [nq][5][np] */
+        int32_t* d_when = nullptr;    /* [nq][2][np] */
+    };
+    std::vector<hq_peak_tracker> peaks;
+    int32_t peak_next_id = 0;
+    hipEvent_t ev_peaked = nullptr;
     /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
      * pinned host memory.  A slot holds the fields one behind the other,
      * each at a 256-byte boundary (off[]; the same layout on both sides, so one copy carries a slot).  sstream, the copy
@@ -706,6 +723,68 @@ hq_k_record(int32_t np, const int32_t* __restrict__ ids, const double* __restric
                 d[a] = d[a] + w[c] * (double)u3[row[c] + a];
             }
         for (int a = 0; a < 3; a++) o[6 + a] = d[a] / dt2;
+    }
+}
+
+/*
+ * One due step of a peak-motion tracker (hq_peak_add): the sample hq_k_record would take at the point -- every value
+ * widened to double first, hqh_station_kinematics' order of operations, contraction OFF, so that it IS the recorder's
+ * sample bit for bit -- folded into the point's running state in place (hq_peak.h) instead of being appended to a ring.
+ * One lane per point, no atomics: a point belongs to one lane, and the launches of one stream are ordered.
+ *   K = 8: eight nodes and trilinear weights per point (stations, planes), ids and phi transposed to [8][np] as the
+ *          recorder's are.
+ *   K = 1: the point is a node (surface maps): no weight table -- the recorder's sums with weights (1, 0, ..., 0) are
+ *          0 + u1, - u2, - u2 + u3 exactly (1 u is u, and adding 0 u changes nothing) -- and one gather per field.
+ * The state is [nq][5][np] doubles and [nq][2][np] int32, nq the set bits of `quantities` in the order displacement,
+ * velocity, acceleration: a wave reads each of its rows in whole lines, and a lane writes only what it raised -- once a
+ * point's peak has passed, the step costs it reads alone.  u2 / u3 are read only if the mask needs them.
+ * Bytes per point and step, K = 1, velocity only: 4 (id) + 48 (u1, u2; 24 in the f32 library) + 40 of peaks read (`when`
+ * is only ever written); K = 8, all three quantities: 96 of tables + 576 of gathers + 120 of state.
+ */
+template <int K>
+__global__ void __launch_bounds__(256)
+hq_k_peak(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
+          const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
+          double dt, double dt2, int32_t quantities, int32_t step, double* __restrict__ pk, int32_t* __restrict__ when)
+{
+#pragma clang fp contract(off)
+    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= np) return;
+    const bool vel = (quantities & HQ_PEAK_VEL) != 0, acc = (quantities & HQ_PEAK_ACC) != 0;
+    int64_t row[K];
+    double w[K];
+#pragma unroll
+    for (int c = 0; c < K; c++) {
+        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
+        w[c] = K == 1 ? 1.0 : phi[(int64_t)c * np + p];
+    }
+    double* s = pk + p;
+    int32_t* sw = when + p;
+    double d[3] = { 0.0, 0.0, 0.0 };
+#pragma unroll
+    for (int c = 0; c < K; c++)
+        for (int a = 0; a < 3; a++) d[a] = d[a] + w[c] * (double)u1[row[c] + a];
+    if (quantities & HQ_PEAK_DISP) {
+        hq_peak_fold(d[0], d[1], d[2], step, s, np, sw, np);
+        s += (int64_t)HQ_PEAK_NVAL * np; sw += (int64_t)HQ_PEAK_NWHEN * np;
+    }
+    if (vel || acc) {
+#pragma unroll
+        for (int c = 0; c < K; c++)
+            for (int a = 0; a < 3; a++) d[a] = d[a] - w[c] * (double)u2[row[c] + a];
+        if (vel) {
+            hq_peak_fold(d[0] / dt, d[1] / dt, d[2] / dt, step, s, np, sw, np);
+            s += (int64_t)HQ_PEAK_NVAL * np; sw += (int64_t)HQ_PEAK_NWHEN * np;
+        }
+    }
+    if (acc) {
+#pragma unroll
+        for (int c = 0; c < K; c++)
+            for (int a = 0; a < 3; a++) {
+                d[a] = d[a] - w[c] * (double)u2[row[c] + a];
+                d[a] = d[a] + w[c] * (double)u3[row[c] + a];
+            }
+        hq_peak_fold(d[0] / dt2, d[1] / dt2, d[2] / dt2, step, s, np, sw, np);
     }
 }
 
@@ -1406,6 +1485,63 @@ static int hq_record_enqueue(hq_ctx* c, bool brick_stream)
     return HQ_OK;
 }
 
+/* ---- peak-motion trackers ---- */
+
+/* free every tracker (the caller has waited for the streams) */
+static void hq_peak_drop_all(hq_ctx* c)
+{
+    for (auto& t : c->peaks) {
+        if (t.d_ids) hipFree(t.d_ids);
+        if (t.d_phi) hipFree(t.d_phi);
+        if (t.d_pk) hipFree(t.d_pk);
+        if (t.d_when) hipFree(t.d_when);
+        c->bytes -= t.bytes;
+    }
+    c->peaks.clear();
+    if (c->ev_peaked) { hipEventDestroy(c->ev_peaked); c->ev_peaked = nullptr; }
+}
+
+/* the state of one tracker as it is before its first sample: peaks 0, `when` -1 (every byte 0xff) -- ON the compute stream
+ * (hq_upload tells what a null-stream memset cost); the caller waits */
+static hipError_t hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
+{
+    const size_t n = (size_t)t.nq * (size_t)t.np;
+    if (n == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(t.d_pk, 0, sizeof(double) * HQ_PEAK_NVAL * n, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t.d_when, 0xff, sizeof(int32_t) * HQ_PEAK_NWHEN * n, c->stream);
+    return e;
+}
+
+/* head of a step, where hq_record_enqueue sits and behind the same waits: one hq_k_peak launch per due tracker on the
+ * compute stream.  A launch that tracks accelerations reads d_u[spare] as u(t - 2 dt), the buffer THIS step's bricks and
+ * exchange chain overwrite: their streams are held back behind it, exactly as behind hq_k_record.  Without accelerations
+ * the launch reads d_u[now] and d_u[prev] only, which this step only reads -- and the next step's kernels follow on the
+ * compute stream or wait for events recorded behind the launch -- so nothing is held: a velocity map must not serialise
+ * every step of its run. */
+static int hq_peak_enqueue(hq_ctx* c, bool brick_stream)
+{
+    bool hold = false;
+    for (auto& t : c->peaks) {
+        if (!hq_cadence_due(t.due, c->step)) continue;
+        t.nsamples++;
+        if (t.np <= 0) continue;
+        const bool acc = (t.quantities & HQ_PEAK_ACC) != 0;
+        const hq_real* u3 = acc ? c->d_u[c->spare] : c->d_u[c->prev];
+        if (t.K == 1)
+            hq_k_peak<1><<<hq_blocks(t.np, 256), 256, 0, c->stream>>>(t.np, t.d_ids, nullptr, c->d_u[c->now], c->d_u[c->prev], u3,
+                                                                       c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
+        else
+            hq_k_peak<8><<<hq_blocks(t.np, 256), 256, 0, c->stream>>>(t.np, t.d_ids, t.d_phi, c->d_u[c->now], c->d_u[c->prev], u3,
+                                                                       c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
+        hold |= acc;
+    }
+    if (hold && c->variant == HQ_VARIANT_PATCH && ((brick_stream && c->bstream) || (c->overlap && c->cstream))) {
+        HQ_HIP(hipEventRecord(c->ev_peaked, c->stream));
+        HQ_TRY(hq_hold_behind(c, brick_stream, c->ev_peaked));
+    }
+    return HQ_OK;
+}
+
 /* ---- field snapshots ---- */
 
 /* free every snapshot (the caller has waited for the streams, the copy stream included) */
@@ -1485,6 +1621,7 @@ static int hq_phase(hq_ctx* c, int ph)
             }
             if (!c->snaps.empty()) HQ_TRY(hq_snapshot_enqueue(c, bs));     /* solver_write_checkpoint / _output_wavefield, :4277-4278 */
             if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, bs));        /* solver_output_planes / _stations, :4279-4280 */
+            if (!c->peaks.empty()) HQ_TRY(hq_peak_enqueue(c, bs));
             auto launch_bricks = [&]() {
                 if (c->bricks.nunits > 0)
                     hq_brick_launch(&c->bricks, c->d_u[c->now], c->d_u[c->prev], c->d_u[c->spare], c->plan.d_nt3, F, c->dt2,
@@ -1549,6 +1686,7 @@ static int hq_phase(hq_ctx* c, int ph)
         } else {
             if (!c->snaps.empty()) HQ_TRY(hq_snapshot_enqueue(c, false));
             if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, false));
+            if (!c->peaks.empty()) HQ_TRY(hq_peak_enqueue(c, false));
             HQ_TRY(hq_launch_source(c));                                   /* :4288 */
             HQ_TRY(hq_launch_element_scatter(c));                          /* :4290-4291 */
         }
@@ -2096,6 +2234,7 @@ extern "C" int hq_destroy(hq_ctx* c)
                      c->dn.d_c_out_id, c->dn.d_c_in_id, c->dn.d_s_out_id, c->dn.d_s_in_id };
     for (void* p : ptrs) if (p) hipFree(p);
     hq_record_drop_all(c);
+    hq_peak_drop_all(c);
     hq_snapshot_drop_all(c);
     if (c->an.d_cmap_f && c->an.d_cmap_f != c->an.d_cmap) hipFree(c->an.d_cmap_f);
     if (c->an.d_smap_f && c->an.d_smap_f != c->an.d_smap) hipFree(c->an.d_smap_f);
@@ -2976,6 +3115,147 @@ extern "C" int hq_record_clear(hq_ctx* c)
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
     hq_record_drop_all(c);
+    return HQ_OK;
+}
+
+/* ---- peak-motion trackers: entry points (include/hq_solver.h) ---- */
+
+extern "C" int hq_peak_add(hq_ctx* c, const hq_peak_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const int32_t all = HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC;
+    const int32_t K = d->nodes_per_point;
+    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->quantities == 0 || (d->quantities & ~all) != 0 ||
+        (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
+        return hq_fail(HQ_ERR_ARG, "bad peak tracker description%s", "");
+    if ((d->quantities & HQ_PEAK_ACC) && c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    const int32_t np = d->npoints;
+    for (int64_t i = 0; i < (int64_t)K * np; i++)
+        if (d->ids[i] < 0 || d->ids[i] >= c->N) return hq_fail(HQ_ERR_ARG, "node id out of range%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    /* the tables: device numbering, transposed to [K][np] */
+    std::vector<int32_t> ids((size_t)np * K);
+    std::vector<double> phi(K == 8 ? (size_t)np * 8 : 0);
+    for (int32_t p = 0; p < np; p++)
+        for (int k = 0; k < K; k++) {
+            const int32_t id = d->ids[(size_t)K * p + k];
+            ids[(size_t)k * np + p] = c->perm.empty() ? id : c->perm[(size_t)id];
+            if (K == 8) phi[(size_t)k * np + p] = d->phi[8 * (size_t)p + k];
+        }
+    hq_ctx::hq_peak_tracker t;
+    t.np = np; t.K = K; t.quantities = d->quantities; t.nq = hq_peak_nq(d->quantities);
+    t.due = { d->rate, d->first_step };
+    const size_t n = (size_t)t.nq * (size_t)np;
+    const int64_t bytes0 = c->bytes;
+    const bool had_event = c->ev_peaked != nullptr;
+    int rc = hq_dev_alloc(c, &t.d_ids, ids.size());
+    if (rc == HQ_OK && K == 8) rc = hq_dev_alloc(c, &t.d_phi, phi.size());
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_pk, HQ_PEAK_NVAL * n);
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_when, HQ_PEAK_NWHEN * n);
+    hipError_t e = hipSuccess;
+    if (rc == HQ_OK && !c->ev_peaked) e = hipEventCreateWithFlags(&c->ev_peaked, hipEventDisableTiming);
+    if (rc == HQ_OK && e == hipSuccess && np > 0) {
+        e = hipMemcpyAsync(t.d_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && K == 8)
+            e = hipMemcpyAsync(t.d_phi, phi.data(), sizeof(double) * phi.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hq_peak_zero(c, t);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   /* (the host tables go out of scope; the state is in place) */
+    }
+    if (rc != HQ_OK || e != hipSuccess) {
+        if (t.d_ids) hipFree(t.d_ids);
+        if (t.d_phi) hipFree(t.d_phi);
+        if (t.d_pk) hipFree(t.d_pk);
+        if (t.d_when) hipFree(t.d_when);
+        if (!had_event && c->ev_peaked) { hipEventDestroy(c->ev_peaked); c->ev_peaked = nullptr; }
+        c->bytes = bytes0;
+        (void)hipGetLastError();
+        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_peak_add failed: %s", hipGetErrorString(e));
+    }
+    t.bytes = c->bytes - bytes0;
+    c->h2d_bytes += 4 * (int64_t)ids.size() + 8 * (int64_t)phi.size();
+    t.id = c->peak_next_id++;
+    *handle = t.id;
+    c->peaks.push_back(t);
+    return HQ_OK;
+}
+
+static hq_ctx::hq_peak_tracker* hq_peak_find(hq_ctx* c, int32_t handle)
+{
+    for (auto& t : c->peaks)
+        if (t.id == handle) return &t;
+    return nullptr;
+}
+
+/* the state crosses PCIe as the device keeps it ([nq][5][np], [nq][2][np]); the caller's arrays are [np][nq][5], [np][nq][2] */
+extern "C" int hq_peak_fetch(hq_ctx* c, int32_t handle, double* peaks, int32_t* when, int64_t* nsamples)
+{
+    if (!c || !peaks || !when || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_peak_tracker* t = hq_peak_find(c, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->np, nq = (size_t)t->nq, n = np * nq;
+    *nsamples = t->nsamples;
+    if (n == 0) return HQ_OK;
+    std::vector<double> pk(HQ_PEAK_NVAL * n);
+    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
+    HQ_HIP(hipMemcpyAsync(pk.data(), t->d_pk, sizeof(double) * pk.size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_HIP(hipMemcpyAsync(wh.data(), t->d_when, sizeof(int32_t) * wh.size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    for (size_t p = 0; p < np; p++)
+        for (size_t q = 0; q < nq; q++) {
+            for (size_t j = 0; j < HQ_PEAK_NVAL; j++) peaks[(p * nq + q) * HQ_PEAK_NVAL + j] = pk[(q * HQ_PEAK_NVAL + j) * np + p];
+            for (size_t j = 0; j < HQ_PEAK_NWHEN; j++) when[(p * nq + q) * HQ_PEAK_NWHEN + j] = wh[(q * HQ_PEAK_NWHEN + j) * np + p];
+        }
+    c->d2h_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_peak_load(hq_ctx* c, int32_t handle, const double* peaks, const int32_t* when, int64_t nsamples)
+{
+    if (!c || !peaks || !when || nsamples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
+    hq_ctx::hq_peak_tracker* t = hq_peak_find(c, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->np, nq = (size_t)t->nq, n = np * nq;
+    t->nsamples = nsamples;
+    if (n == 0) return HQ_OK;
+    std::vector<double> pk(HQ_PEAK_NVAL * n);
+    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
+    for (size_t p = 0; p < np; p++)
+        for (size_t q = 0; q < nq; q++) {
+            for (size_t j = 0; j < HQ_PEAK_NVAL; j++) pk[(q * HQ_PEAK_NVAL + j) * np + p] = peaks[(p * nq + q) * HQ_PEAK_NVAL + j];
+            for (size_t j = 0; j < HQ_PEAK_NWHEN; j++) wh[(q * HQ_PEAK_NWHEN + j) * np + p] = when[(p * nq + q) * HQ_PEAK_NWHEN + j];
+        }
+    HQ_HIP(hipMemcpyAsync(t->d_pk, pk.data(), sizeof(double) * pk.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipMemcpyAsync(t->d_when, wh.data(), sizeof(int32_t) * wh.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    c->h2d_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_peak_reset(hq_ctx* c, int32_t handle)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_peak_tracker* t = hq_peak_find(c, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    HQ_HIP(hq_peak_zero(c, *t));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    t->nsamples = 0;
+    return HQ_OK;
+}
+
+extern "C" int hq_peak_clear(hq_ctx* c)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (c->peaks.empty()) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    hq_peak_drop_all(c);
     return HQ_OK;
 }
 

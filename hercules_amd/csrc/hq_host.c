@@ -34,6 +34,7 @@
 
 #include "hq_host.h"
 #include "hq_cadence.h"
+#include "hq_peak.h"
 
 #define HQH_PI 3.14159265358979323846
 
@@ -1419,6 +1420,28 @@ int hqh_station_kinematics(const double* phi, const double* tm1, const double* t
             for (int a = 0; a < 3; a++) { d[a] -= phi[c] * tm2[3 * c + a]; d[a] += phi[c] * tm3[3 * c + a]; }
         for (int a = 0; a < 3; a++) vals[6 + a] = d[a] / dt2;
     }
+    return HQ_OK;
+}
+
+int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps, const double* samples,
+                  double* peaks, int32_t* when)
+{
+    if (npoints < 0 || nsamples < 0 || quantities == 0 || (quantities & ~(HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC)) != 0)
+        return HQ_ERR_ARG;
+    if (npoints == 0 || nsamples == 0) return HQ_OK;
+    if (!steps || !samples || !peaks || !when) return HQ_ERR_ARG;
+    const int32_t nq = hq_peak_nq(quantities), ncomp = 3 * (1 + hq_peak_derivs(quantities));
+    for (int32_t k = 0; k < nsamples; k++)
+        for (int32_t p = 0; p < npoints; p++) {
+            const double* v = samples + ((int64_t)k * npoints + p) * ncomp;
+            double* pk = peaks + (int64_t)p * nq * HQ_PEAK_NVAL;
+            int32_t* w = when + (int64_t)p * nq * HQ_PEAK_NWHEN;
+            for (int q = 0; q < HQ_PEAK_NQ; q++) {
+                if (!(quantities & (1 << q))) continue;
+                hq_peak_fold(v[3 * q], v[3 * q + 1], v[3 * q + 2], steps[k], pk, 1, w, 1);
+                pk += HQ_PEAK_NVAL; w += HQ_PEAK_NWHEN;
+            }
+        }
     return HQ_OK;
 }
 

@@ -18,7 +18,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_forcefile_info", "hqh_forcefile_read", "hqh_forcefile_write",
            "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
-           "hqh_station_kinematics", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
+           "hqh_station_kinematics", "hqh_peak_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
            "hqh_cvm_open", "hqh_cvm_close", "hqh_cvm_info", "hqh_cvm_query", "hqh_cvm_grid"]
 
@@ -773,6 +773,31 @@ def checkpoint_read(solver, path, rank=0, nranks=1):
     if rc != 0:
         raise capi.HqError("hqh_checkpoint_read failed: %d" % rc)
     return step.value
+
+
+def peak_fold(steps, samples, quantities, peaks=None, when=None):
+    """hqh_peak_fold: recorder samples [k, npoints, 3 (1 + derivs)] taken at `steps` [k] (record_fetch's pair; derivs = 2 with
+    HQ_PEAK_ACC in `quantities`, else 1 with HQ_PEAK_VEL, else 0) folded into (peaks [npoints, nq, 5], when [npoints, nq, 2]),
+    the state Solver.peak_fetch returns.  peaks / when None: a fresh state (0 / -1); given, they are folded into in place
+    (float64 / int32, C-contiguous) -- two calls in sequence equal one on the concatenation.  Returns (peaks, when)."""
+    quantities = int(quantities)
+    nq = bin(quantities & 7).count("1")
+    derivs = 2 if quantities & capi.HQ_PEAK_ACC else 1 if quantities & capi.HQ_PEAK_VEL else 0
+    steps = np.ascontiguousarray(steps, np.int32).reshape(-1)
+    samples = np.ascontiguousarray(samples, np.float64)
+    if samples.ndim != 3 or samples.shape[0] != len(steps) or samples.shape[2] != 3 * (1 + derivs):
+        raise capi.HqError("peak_fold: samples %r do not match %d steps of %d columns" % (samples.shape, len(steps), 3 * (1 + derivs)))
+    npoints = samples.shape[1]
+    if peaks is None:
+        peaks = np.zeros((npoints, nq, 5))
+        when = np.full((npoints, nq, 2), -1, np.int32)
+    if (peaks.dtype != np.float64 or when.dtype != np.int32 or peaks.shape != (npoints, nq, 5) or when.shape != (npoints, nq, 2)
+            or not peaks.flags.c_contiguous or not when.flags.c_contiguous):
+        raise capi.HqError("peak_fold: peaks / when are not a state of %d points and %d quantities" % (npoints, nq))
+    capi._check(load_library().hqh_peak_fold(ctypes.c_int32(npoints), ctypes.c_int32(quantities), ctypes.c_int32(len(steps)),
+                                             ctypes.c_void_p(steps.ctypes.data), ctypes.c_void_p(samples.ctypes.data),
+                                             ctypes.c_void_p(peaks.ctypes.data), ctypes.c_void_p(when.ctypes.data)))
+    return peaks, when
 
 
 def station_header(derivs=0):

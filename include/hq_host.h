@@ -293,6 +293,14 @@ HQ_API int hqh_station_header(char* buf, int32_t cap, int32_t derivs);
  * [8][3]; tm2 / tm3 may be NULL below derivs 1 / 2), in the reference's order of operations. */
 HQ_API int hqh_station_kinematics(const double* phi, const double* tm1, const double* tm2, const double* tm3,
                                   double dt, int32_t derivs, double* vals);
+/* The peak-motion fold on the host (csrc/hq_peak.h, the text hq_k_peak compiles): recorder samples folded into the state
+ * hq_peak_fetch delivers -- the route of a caller without device trackers.  samples [nsamples][npoints][3 (1 + derivs)] in
+ * the layout of hq_record_fetch, derivs = 2 if `quantities` (a mask of HQ_PEAK_*) has HQ_PEAK_ACC, else 1 if it has
+ * HQ_PEAK_VEL, else 0; steps[k] is the step of sample k.  peaks [npoints][nq][5] and when [npoints][nq][2] are folded
+ * INTO: the caller starts them at 0 and -1, and two calls in sequence equal one call on the concatenation.
+ * HQ_ERR_ARG for null pointers (where there is something to read), negative counts, quantities 0 or with unknown bits. */
+HQ_API int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps,
+                         const double* samples, double* peaks, int32_t* when);
 
 /*
  * Two-level layered box: the top nz_fine layers of elements of edge h over nz_coarse

@@ -492,6 +492,59 @@ HQ_API int hq_snapshot_fetch(hq_ctx* ctx, int32_t handle, hq_real* tm1, hq_real*
 HQ_API int hq_snapshot_clear(hq_ctx* ctx);
 
 /*
+ * Peak-motion trackers (additive under ABI 6): the running PGD / PGV / PGA map -- the largest displacement, velocity and
+ * acceleration every point saw over the run -- kept ON THE DEVICE.  A peak is a reduction over time: one slot per point
+ * updated in place has no ring, cuts no batch, moves nothing over PCIe until it is fetched and never stops the queue;
+ * the other route is a recorder at rate 1 and a fold of every sample on the host (hqh_peak_fold, hq_host.h).
+ * A tracker is a list of points: with nodes_per_point = 8 the trilinear sum over the 8 nodes of an element, as a
+ * recorder's; with nodes_per_point = 1 single nodes (a surface map), with no weights at all.  At the head of every step
+ * s >= first_step with s % rate == 0 -- where hq_k_record sits, before any of that step's kernels, on exactly the state
+ * hq_gather3 documents -- one launch of hq_k_peak forms the sample hq_k_record would take at the point (every value
+ * widened to double first, hqh_station_kinematics' order of operations, no contraction: the recorder's sample bit for
+ * bit) and folds it into the point's state.  Per point and quantity q of the mask, in the order displacement, velocity
+ * (u1 - u2) / dt, acceleration (u1 - 2 u2 + u3) / dt^2, that state is (csrc/hq_peak.h):
+ *   peaks[p][q][0..2] = max |v_x|, |v_y|, |v_z|
+ *   peaks[p][q][3]    = max (v_x v_x + v_y v_y)             horizontal, SQUARED (z is depth)
+ *   peaks[p][q][4]    = max (v_x v_x + v_y v_y) + v_z v_z   total, SQUARED, summed in this order
+ *   when[p][q][0]     = the step at which [3] was last raised, when[p][q][1] the same for [4]; -1 = never
+ * always double, in both libraries.  A value enters only if it is strictly greater: the first occurrence of a maximum
+ * is kept, a sample of exactly 0 leaves `when` at -1, a NaN never enters.  The device takes no root -- the caller takes
+ * sqrt of [3] and [4] -- so the state equals the host fold of a recorder's samples of the same run bit for bit.
+ * Step 0 samples the initial state; as with recorders, the state after the last step is not sampled until a further
+ * step begins.
+ * hq_peak_fetch waits for the enqueued work (as hq_record_fetch does), copies the state out -- peaks [np][nq][5], when
+ * [np][nq][2], nq the number of set bits of `quantities` -- and leaves it in place; *nsamples counts the due steps folded
+ * so far, accounted on the host from the step counter.  It adds exactly the fetched bytes, 48 np nq, to
+ * hq_info.pcie_d2h_bytes; between fetches a tracker moves nothing.  hq_peak_load puts fetched values back (a run that
+ * restarts from a checkpoint); hq_peak_reset zeroes the state, sets `when` to -1 and nsamples to 0.  hq_upload keeps
+ * trackers and their state; the due steps follow the new step number.  hq_peak_clear drops every tracker of the context
+ * and its memory (hq_destroy does, too); handles are not reused.  Trackers are neither recorders nor snapshots:
+ * hq_record_clear, hq_snapshot_clear and the hqh_solver_run* runners leave them alone, and no run call has anything to
+ * count for them -- add a tracker, run through any runner, fetch.  The device memory counts in hq_info.device_bytes.
+ * Only a tracker with HQ_PEAK_ACC reads u(t - 2 dt), the buffer the step's own kernels overwrite: its due steps hold the
+ * streams of those kernels back behind the launch, as a recorder's do; a displacement / velocity map holds nothing.
+ * Errors: HQ_ERR_ARG for null pointers, npoints < 0, nodes_per_point not 1 or 8, rate < 1, quantities 0 or with unknown
+ * bits, an id outside [0, nharbored), an unknown handle; HQ_ERR_STATE for HQ_PEAK_ACC in the scatter variant (as
+ * hq_gather3); HQ_ERR_NOMEM if the device memory cannot be allocated -- nothing is kept then.  npoints == 0 is valid.
+ * A context without trackers enqueues exactly what it did before they existed.
+ */
+enum { HQ_PEAK_DISP = 1, HQ_PEAK_VEL = 2, HQ_PEAK_ACC = 4 };
+typedef struct {
+    int32_t        npoints;
+    int32_t        nodes_per_point;  /* 8: ids [np][8] + phi [np][8], as hqh_stations returns them; 1: ids [np], phi ignored (may be NULL) */
+    const int32_t* ids;              /* local node ids, octor numbering */
+    const double*  phi;
+    int32_t        rate, first_step; /* a sample at the head of every step s >= first_step with s % rate == 0 */
+    int32_t        quantities;       /* mask of HQ_PEAK_*; non-zero, no unknown bits */
+    int32_t        reserved;
+} hq_peak_desc;
+HQ_API int hq_peak_add(hq_ctx* ctx, const hq_peak_desc* desc, int32_t* handle);
+HQ_API int hq_peak_fetch(hq_ctx* ctx, int32_t handle, double* peaks, int32_t* when, int64_t* nsamples);
+HQ_API int hq_peak_load(hq_ctx* ctx, int32_t handle, const double* peaks, const int32_t* when, int64_t nsamples);
+HQ_API int hq_peak_reset(hq_ctx* ctx, int32_t handle);
+HQ_API int hq_peak_clear(hq_ctx* ctx);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
