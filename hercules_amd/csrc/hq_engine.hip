@@ -43,6 +43,8 @@
 #include "hq_opts.h"
 #include "hq_cadence.h"
 #include "hq_peak.h"
+#define HQ_SAMPLE_REAL hq_real
+#include "hq_sample.h"
 #include "hq_patch.h"
 #include "hq_brick.h"
 
@@ -258,67 +260,17 @@ struct hq_ctx {
     size_t clock_at = 0;
     double clk_us[5] = { 0, 0, 0, 0, 0 };   /* step, shell, interior, chain, chain behind the interior's end */
     int64_t clk_steps = 0;
-    /* what a recorder and a snapshot share (hq_cadence.h): the steps it is due at and the ring of its pending slots,
-     * accounted on the host -- which steps are due follows from `step` alone */
-    struct hq_output {
-        int32_t id = 0;
-        hq_cadence due = { 1, 0 };
-        hq_step_ring ring = { nullptr, 0, 0, 0 };
-        std::vector<int32_t> steps;   /* [capacity] the ring's storage: a move keeps the buffer, and so ring.steps */
-        int64_t bytes = 0;            /* device memory of this output (part of `bytes`) */
-        void open(int32_t rate, int64_t first_step, int32_t capacity)
-        {
-            due = { rate, first_step };
-            steps.assign((size_t)capacity, 0);
-            ring = { steps.data(), capacity, 0, 0 };
-        }
-    };
-    /* sample recorders (hq_record_add): rings in device memory.  ev_recorded exists from the first hq_record_add on: behind
-     * a due step's hq_k_record launches, waited for by the streams whose kernels of that step overwrite the buffer the
-     * launches read as u(t - 2 dt) */
-    struct hq_recorder : hq_output {
-        int32_t np = 0, derivs = 0;
-        int32_t* d_ids = nullptr;     /* [8][np] device numbering */
-        double* d_phi = nullptr;      /* [8][np] */
-        double* d_ring = nullptr;     /* [capacity][np][3 (1 + derivs)] */
-    };
+    /* device outputs (recorders, trackers, snapshots).  hq_outputs.h, included ahead of hq_phase, DEFINES the structs: no code
+     * above that include may touch recs, peaks or snaps.  ev_output: recorded behind a due step's launches for the streams to wait on */
+    struct hq_output; struct hq_recorder; struct hq_peak_tracker; struct hq_snapshot;
     std::vector<hq_recorder> recs;
     int32_t rec_next_id = 0;
-    hipEvent_t ev_recorded = nullptr;
-    /* peak-motion trackers (hq_peak_add): a running state per point updated in place by hq_k_peak -- no ring, no pending
-     * samples, nothing for hq_run to count.  ev_peaked exists from the first hq_peak_add on: on a due step of a tracker
-     * that reads u(t - 2 dt) (HQ_PEAK_ACC) the streams whose kernels overwrite that buffer wait for it, as for ev_recorded */
-    struct hq_peak_tracker {
-        int32_t id = 0, np = 0, K = 8, quantities = 0, nq = 0;
-        hq_cadence due = { 1, 0 };
-        int64_t nsamples = 0;         /* due steps folded or enqueued so far: accounted here, from `step` alone */
-        int64_t bytes = 0;
-        int32_t* d_ids = nullptr;     /* [K][np] device numbering */
-        double* d_phi = nullptr;      /* [8][np]; NULL for K = 1 */
-        double* d_pk = nullptr;       /* [nq][5][np] */
-        int32_t* d_when = nullptr;    /* [nq][2][np] */
-    };
     std::vector<hq_peak_tracker> peaks;
     int32_t peak_next_id = 0;
-    hipEvent_t ev_peaked = nullptr;
-    /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
-     * pinned host memory.  A slot holds the fields one behind the other,
-     * each at a 256-byte boundary (off[]; the same layout on both sides, so one copy carries a slot).  sstream, the copy
-     * stream, and ev_snapped exist from the first hq_snapshot_add on: behind each hq_k_snapshot launch the event is
-     * recorded on the compute stream and waited for by sstream, which copies the slot and records the slot's done event */
-    struct hq_snapshot : hq_output {
-        int32_t first = 0, count = 0, fields = 0;
-        int32_t* d_map = nullptr;     /* [count] device id of node first + i; NULL on contexts without a renumbering */
-        char* d_stage = nullptr;      /* [slots][slot_bytes] */
-        char* h_stage = nullptr;      /* the same, pinned host memory */
-        size_t off[3] = { 0, 0, 0 };  /* tm1, tm2, vel inside a slot */
-        size_t slot_bytes = 0;
-        std::vector<hipEvent_t> done; /* [slots] the slot's copy has arrived */
-    };
     std::vector<hq_snapshot> snaps;
     int32_t snap_next_id = 0;
-    hipStream_t sstream = nullptr;
-    hipEvent_t ev_snapped = nullptr;
+    hipStream_t sstream = nullptr;              /* the snapshots' copy stream: from the first hq_snapshot_add on */
+    hipEvent_t ev_output = nullptr;
     /* timing */
     std::vector<hipEvent_t> ev;     /* per-launch marks */
     hipEvent_t ev_span[2] = { nullptr, nullptr };
@@ -675,206 +627,6 @@ __global__ void hq_k_gather(int32_t n, const int32_t* __restrict__ ids,
     int i = t / 3, d = t - 3 * i;
     oa[t] = a[3 * (int64_t)ids[i] + d];
     ob[t] = b[3 * (int64_t)ids[i] + d];
-}
-
-/*
- * One sample of a recorder (hq_record_add): interpolate_station_displacements (psolve.c:6705-6787) / Old_planes_print
- * (io_planes.c:176-200) on the device-resident state.  One lane per point, consecutive lanes on consecutive points; ids
- * and phi are stored transposed ([8][np]) so that a wave reads them in whole lines.  Eight gathers of one 3-vector from
- * each of u1 = u(t), u2 = u(t - dt), u3 = u(t - 2 dt) as far as `derivs` needs them, every value widened to double first
- * (hq_real is float in the f32 library), summed in hqh_station_kinematics' exact order of operations (hq_host.c): the
- * displacement accumulator over the 8 nodes; then phi * u2 taken off node by node, over dt; then phi * u2 off once more
- * and phi * u3 added, node by node, over dt^2.  Contraction is OFF: the host library is compiled without FMA, and the
- * samples must equal the host route's bit for bit (tests/test_gpu_recorders.py).
- * A memory-bound gather of up to 3 x 8 x 24 bytes per point; a plane's points are the bulk of it.
- */
-__global__ void __launch_bounds__(256)
-hq_k_record(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
-            const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
-            double dt, double dt2, int32_t derivs, double* __restrict__ out)
-{
-#pragma clang fp contract(off)
-    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
-    if (p >= np) return;
-    int64_t row[8];
-    double w[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
-        w[c] = phi[(int64_t)c * np + p];
-    }
-    double* o = out + (int64_t)p * (3 * (1 + derivs));
-    double d[3] = { 0.0, 0.0, 0.0 };
-#pragma unroll
-    for (int c = 0; c < 8; c++)
-        for (int a = 0; a < 3; a++) d[a] = d[a] + w[c] * (double)u1[row[c] + a];
-    for (int a = 0; a < 3; a++) o[a] = d[a];
-    if (derivs >= 1) {
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-            for (int a = 0; a < 3; a++) d[a] = d[a] - w[c] * (double)u2[row[c] + a];
-        for (int a = 0; a < 3; a++) o[3 + a] = d[a] / dt;
-    }
-    if (derivs == 2) {
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-            for (int a = 0; a < 3; a++) {
-                d[a] = d[a] - w[c] * (double)u2[row[c] + a];
-                d[a] = d[a] + w[c] * (double)u3[row[c] + a];
-            }
-        for (int a = 0; a < 3; a++) o[6 + a] = d[a] / dt2;
-    }
-}
-
-/*
- * One due step of a peak-motion tracker (hq_peak_add): the sample hq_k_record would take at the point -- every value
- * widened to double first, hqh_station_kinematics' order of operations, contraction OFF, so that it IS the recorder's
- * sample bit for bit -- folded into the point's running state in place (hq_peak.h) instead of being appended to a ring.
- * One lane per point, no atomics: a point belongs to one lane, and the launches of one stream are ordered.
- *   K = 8: eight nodes and trilinear weights per point (stations, planes), ids and phi transposed to [8][np] as the
- *          recorder's are.
- *   K = 1: the point is a node (surface maps): no weight table -- the recorder's sums with weights (1, 0, ..., 0) are
- *          0 + u1, - u2, - u2 + u3 exactly (1 u is u, and adding 0 u changes nothing) -- and one gather per field.
- * The state is [nq][5][np] doubles and [nq][2][np] int32, nq the set bits of `quantities` in the order displacement,
- * velocity, acceleration: a wave reads each of its rows in whole lines, and a lane writes only what it raised -- once a
- * point's peak has passed, the step costs it reads alone.  u2 / u3 are read only if the mask needs them.
- * Bytes per point and step, K = 1, velocity only: 4 (id) + 48 (u1, u2; 24 in the f32 library) + 40 of peaks read (`when`
- * is only ever written); K = 8, all three quantities: 96 of tables + 576 of gathers + 120 of state.
- */
-template <int K>
-__global__ void __launch_bounds__(256)
-hq_k_peak(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
-          const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
-          double dt, double dt2, int32_t quantities, int32_t step, double* __restrict__ pk, int32_t* __restrict__ when)
-{
-#pragma clang fp contract(off)
-    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
-    if (p >= np) return;
-    const bool vel = (quantities & HQ_PEAK_VEL) != 0, acc = (quantities & HQ_PEAK_ACC) != 0;
-    int64_t row[K];
-    double w[K];
-#pragma unroll
-    for (int c = 0; c < K; c++) {
-        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
-        w[c] = K == 1 ? 1.0 : phi[(int64_t)c * np + p];
-    }
-    double* s = pk + p;
-    int32_t* sw = when + p;
-    double d[3] = { 0.0, 0.0, 0.0 };
-#pragma unroll
-    for (int c = 0; c < K; c++)
-        for (int a = 0; a < 3; a++) d[a] = d[a] + w[c] * (double)u1[row[c] + a];
-    if (quantities & HQ_PEAK_DISP) {
-        hq_peak_fold(d[0], d[1], d[2], step, s, np, sw, np);
-        s += (int64_t)HQ_PEAK_NVAL * np; sw += (int64_t)HQ_PEAK_NWHEN * np;
-    }
-    if (vel || acc) {
-#pragma unroll
-        for (int c = 0; c < K; c++)
-            for (int a = 0; a < 3; a++) d[a] = d[a] - w[c] * (double)u2[row[c] + a];
-        if (vel) {
-            hq_peak_fold(d[0] / dt, d[1] / dt, d[2] / dt, step, s, np, sw, np);
-            s += (int64_t)HQ_PEAK_NVAL * np; sw += (int64_t)HQ_PEAK_NWHEN * np;
-        }
-    }
-    if (acc) {
-#pragma unroll
-        for (int c = 0; c < K; c++)
-            for (int a = 0; a < 3; a++) {
-                d[a] = d[a] - w[c] * (double)u2[row[c] + a];
-                d[a] = d[a] + w[c] * (double)u3[row[c] + a];
-            }
-        hq_peak_fold(d[0] / dt2, d[1] / dt2, d[2] / dt2, step, s, np, sw, np);
-    }
-}
-
-/*
- * One field snapshot (hq_snapshot_add): the rows [first, first + count) of u1 = u(t), u2 = u(t - dt) out of the device's
- * numbering into a staging slot in the caller's (octor) order -- hq_field_to_host's un-permutation, done at HBM speed
- * ahead of the copy instead of on the host behind it.  A streaming permutation: per node 4 bytes of map, 24-48 bytes of
- * state read, 24-72 written; no arithmetic but the velocity's, (double)u1 - (double)u2 over dt, contraction off
- * (hqh_wavefield_write's write_velocity, bit for bit).
- * The OUTPUT is what the lanes are laid over: the slot's fields are flat arrays of 3 count scalars, and a lane owns V =
- * 16 / sizeof(T) consecutive ones (2 doubles, 4 floats -- they may straddle two rows), so every store is a 16-byte store
- * and a wave's stores cover 1 KiB of consecutive output rows.  The reads are gathers of single scalars, lane by lane: the
- * three lanes (or one and a half) of a row read its 24 (12) bytes side by side, and wherever the map runs on -- inside a
- * brick's tile the x-neighbours of the octor order are neighbours on the device too, 64 at a time, and on contexts without
- * a renumbering everywhere -- consecutive lanes read consecutive addresses and the wave's loads merge into whole lines
- * like those of a plain copy.  Where the map jumps, the other rows of the lines it touches are read by the same workgroup
- * (a tile of 256 V consecutive octor rows is a compact cube of the mesh) and come out of L2.
- * A workgroup takes tiles of 256 V rows = 768 lane groups, three per thread (independent: their loads are in flight
- * together); 256 V rows are a multiple of 16 bytes in every field, so each group's stores are aligned.  map == NULL: the
- * device numbers the nodes as the caller does.  o1 / o2 / ov == NULL: that field is not wanted.
- */
-template <typename T>
-__global__ void __launch_bounds__(256)
-hq_k_snapshot(int32_t first, int32_t count, const int32_t* __restrict__ map, const T* __restrict__ u1,
-              const T* __restrict__ u2, double dt, T* __restrict__ o1, T* __restrict__ o2, double* __restrict__ ov)
-{
-#pragma clang fp contract(off)
-    constexpr int V = 16 / (int)sizeof(T);
-    constexpr int32_t TR = 256 * V;                              /* rows per tile */
-    typedef T vecT __attribute__((ext_vector_type(V)));         /* 16 bytes: one global_store_dwordx4 */
-    typedef double vecD __attribute__((ext_vector_type(2)));
-    const int32_t ntiles = (count + TR - 1) / TR;
-    const bool want1 = o1 != nullptr || ov != nullptr, want2 = o2 != nullptr || ov != nullptr;
-    for (int32_t tile = (int32_t)blockIdx.x; tile < ntiles; tile += (int32_t)gridDim.x) {
-        const int32_t row0 = tile * TR;
-        const int32_t nscal = 3 * min(TR, count - row0);         /* scalars of this tile */
-        const int64_t base = 3 * (int64_t)row0;
-#pragma unroll
-        for (int m = 0; m < 3; m++) {
-            const int32_t j0 = ((int32_t)threadIdx.x + 256 * m) * V;
-            if (j0 >= nscal) continue;
-            T a[V], b[V];
-#pragma unroll
-            for (int k = 0; k < V; k++) {
-                const int32_t j = min(j0 + k, nscal - 1);        /* (a lane group past the end re-reads the last scalar) */
-                const int32_t n = j / 3;
-                const int64_t row = map ? (int64_t)map[row0 + n] : (int64_t)first + row0 + n;
-                const int64_t src = 3 * row + (j - 3 * n);
-                a[k] = want1 ? u1[src] : (T)0;
-                b[k] = want2 ? u2[src] : (T)0;
-            }
-            const bool whole = j0 + V <= nscal;
-            if (o1) {
-                if (whole) {
-                    vecT w;
-#pragma unroll
-                    for (int k = 0; k < V; k++) w[k] = a[k];
-                    *(vecT*)(o1 + base + j0) = w;
-                }
-                else {
-#pragma unroll
-                    for (int k = 0; k < V; k++) if (j0 + k < nscal) o1[base + j0 + k] = a[k];
-                }
-            }
-            if (o2) {
-                if (whole) {
-                    vecT w;
-#pragma unroll
-                    for (int k = 0; k < V; k++) w[k] = b[k];
-                    *(vecT*)(o2 + base + j0) = w;
-                }
-                else {
-#pragma unroll
-                    for (int k = 0; k < V; k++) if (j0 + k < nscal) o2[base + j0 + k] = b[k];
-                }
-            }
-            if (ov) {
-                double v[V];
-#pragma unroll
-                for (int k = 0; k < V; k++) v[k] = ((double)a[k] - (double)b[k]) / dt;
-                if (whole) {
-#pragma unroll
-                    for (int k = 0; k < V; k += 2) { vecD w = { v[k], v[k + 1] }; *(vecD*)(ov + base + j0 + k) = w; }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < V; k++) if (j0 + k < nscal) ov[base + j0 + k] = v[k];
-                }
-            }
-        }
-    }
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1408,188 +1160,7 @@ static bool hq_use_brick_stream(hq_ctx* c)
     return true;
 }
 
-/* ---- device outputs: what recorders and snapshots share (hq_cadence.h) ---- */
-
-/* do the due steps of [c->step, c->step + nsteps) fit into every ring's free slots? */
-template <typename T>
-static bool hq_outputs_have_room(const std::vector<T>& outs, int64_t step, int32_t nsteps)
-{
-    for (const auto& o : outs)
-        if (hq_cadence_count(o.due, step, step + nsteps) > hq_step_ring_room(&o.ring)) return false;
-    return true;
-}
-
-/* the recorders' rings and the snapshots' slots: what hq_run, hq_group_run and hq_run_timed ask before they enqueue */
-static int hq_output_check_room(const hq_ctx* c, int32_t nsteps)
-{
-    if (!hq_outputs_have_room(c->recs, c->step, nsteps))
-        return hq_fail(HQ_ERR_STATE, "a recorder's ring would overflow: fetch its samples first (hq_record_fetch)%s", "");
-    if (!hq_outputs_have_room(c->snaps, c->step, nsteps))
-        return hq_fail(HQ_ERR_STATE, "a snapshot's slots would run out: fetch the pending ones first (hq_snapshot_fetch)%s", "");
-    return HQ_OK;
-}
-
-template <typename T>
-static T* hq_output_find(std::vector<T>& outs, int32_t handle)
-{
-    for (auto& o : outs)
-        if (o.id == handle) return &o;
-    return nullptr;
-}
-
-/* hold the bricks' own stream and the exchange chain's behind `ev`, recorded on the compute stream */
-static int hq_hold_behind(hq_ctx* c, bool brick_stream, hipEvent_t ev)
-{
-    if (brick_stream && c->bstream) HQ_HIP(hipStreamWaitEvent(c->bstream, ev, 0));
-    if (c->overlap && c->cstream) HQ_HIP(hipStreamWaitEvent(c->cstream, ev, 0));
-    return HQ_OK;
-}
-
-/* ---- sample recorders ---- */
-
-/* free every recorder (the caller has waited for the streams) */
-static void hq_record_drop_all(hq_ctx* c)
-{
-    for (auto& r : c->recs) {
-        if (r.d_ids) hipFree(r.d_ids);
-        if (r.d_phi) hipFree(r.d_phi);
-        if (r.d_ring) hipFree(r.d_ring);
-        c->bytes -= r.bytes;
-    }
-    c->recs.clear();
-    if (c->ev_recorded) { hipEventDestroy(c->ev_recorded); c->ev_recorded = nullptr; }
-}
-
-/* head of a step: one hq_k_record launch per due recorder on the compute stream, behind the waits phase 0 has already
- * made for the last step's shared displacements and bricks.  On a due step only, the streams whose kernels of THIS
- * step write into d_u[spare] -- which the launch reads as u(t - 2 dt) -- are held back behind it: the bricks' own stream,
- * and the exchange chain's (hq_k_interface_update, the unpack).  The patches follow on the compute stream itself. */
-static int hq_record_enqueue(hq_ctx* c, bool brick_stream)
-{
-    bool any = false;
-    for (auto& r : c->recs) {
-        if (!hq_cadence_due(r.due, c->step)) continue;
-        const int32_t slot = hq_step_ring_push(&r.ring, c->step);
-        if (slot < 0) return hq_fail(HQ_ERR_STATE, "a recorder's ring is full%s", "");   /* (hq_output_check_room saw to it) */
-        if (r.np <= 0) continue;
-        const int32_t ncomp = 3 * (1 + r.derivs);
-        hq_k_record<<<hq_blocks(r.np, 256), 256, 0, c->stream>>>(
-            r.np, r.d_ids, r.d_phi, c->d_u[c->now], c->d_u[c->prev], r.derivs == 2 ? c->d_u[c->spare] : c->d_u[c->prev],
-            c->dt, c->dt2, r.derivs, r.d_ring + (int64_t)slot * r.np * ncomp);
-        any = true;
-    }
-    if (any && c->variant == HQ_VARIANT_PATCH && ((brick_stream && c->bstream) || (c->overlap && c->cstream))) {
-        HQ_HIP(hipEventRecord(c->ev_recorded, c->stream));
-        HQ_TRY(hq_hold_behind(c, brick_stream, c->ev_recorded));
-    }
-    return HQ_OK;
-}
-
-/* ---- peak-motion trackers ---- */
-
-/* free every tracker (the caller has waited for the streams) */
-static void hq_peak_drop_all(hq_ctx* c)
-{
-    for (auto& t : c->peaks) {
-        if (t.d_ids) hipFree(t.d_ids);
-        if (t.d_phi) hipFree(t.d_phi);
-        if (t.d_pk) hipFree(t.d_pk);
-        if (t.d_when) hipFree(t.d_when);
-        c->bytes -= t.bytes;
-    }
-    c->peaks.clear();
-    if (c->ev_peaked) { hipEventDestroy(c->ev_peaked); c->ev_peaked = nullptr; }
-}
-
-/* the state of one tracker as it is before its first sample: peaks 0, `when` -1 (every byte 0xff) -- ON the compute stream
- * (hq_upload tells what a null-stream memset cost); the caller waits */
-static hipError_t hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
-{
-    const size_t n = (size_t)t.nq * (size_t)t.np;
-    if (n == 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(t.d_pk, 0, sizeof(double) * HQ_PEAK_NVAL * n, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t.d_when, 0xff, sizeof(int32_t) * HQ_PEAK_NWHEN * n, c->stream);
-    return e;
-}
-
-/* head of a step, where hq_record_enqueue sits and behind the same waits: one hq_k_peak launch per due tracker on the
- * compute stream.  A launch that tracks accelerations reads d_u[spare] as u(t - 2 dt), the buffer THIS step's bricks and
- * exchange chain overwrite: their streams are held back behind it, exactly as behind hq_k_record.  Without accelerations
- * the launch reads d_u[now] and d_u[prev] only, which this step only reads -- and the next step's kernels follow on the
- * compute stream or wait for events recorded behind the launch -- so nothing is held: a velocity map must not serialise
- * every step of its run. */
-static int hq_peak_enqueue(hq_ctx* c, bool brick_stream)
-{
-    bool hold = false;
-    for (auto& t : c->peaks) {
-        if (!hq_cadence_due(t.due, c->step)) continue;
-        t.nsamples++;
-        if (t.np <= 0) continue;
-        const bool acc = (t.quantities & HQ_PEAK_ACC) != 0;
-        const hq_real* u3 = acc ? c->d_u[c->spare] : c->d_u[c->prev];
-        if (t.K == 1)
-            hq_k_peak<1><<<hq_blocks(t.np, 256), 256, 0, c->stream>>>(t.np, t.d_ids, nullptr, c->d_u[c->now], c->d_u[c->prev], u3,
-                                                                       c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
-        else
-            hq_k_peak<8><<<hq_blocks(t.np, 256), 256, 0, c->stream>>>(t.np, t.d_ids, t.d_phi, c->d_u[c->now], c->d_u[c->prev], u3,
-                                                                       c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
-        hold |= acc;
-    }
-    if (hold && c->variant == HQ_VARIANT_PATCH && ((brick_stream && c->bstream) || (c->overlap && c->cstream))) {
-        HQ_HIP(hipEventRecord(c->ev_peaked, c->stream));
-        HQ_TRY(hq_hold_behind(c, brick_stream, c->ev_peaked));
-    }
-    return HQ_OK;
-}
-
-/* ---- field snapshots ---- */
-
-/* free every snapshot (the caller has waited for the streams, the copy stream included) */
-static void hq_snapshot_drop_all(hq_ctx* c)
-{
-    for (auto& sn : c->snaps) {
-        if (sn.d_map) hipFree(sn.d_map);
-        if (sn.d_stage) hipFree(sn.d_stage);
-        if (sn.h_stage) hipHostFree(sn.h_stage);
-        for (hipEvent_t e : sn.done) if (e) hipEventDestroy(e);
-        c->bytes -= sn.bytes;
-    }
-    c->snaps.clear();
-    if (c->ev_snapped) { hipEventDestroy(c->ev_snapped); c->ev_snapped = nullptr; }
-    if (c->sstream) { hipStreamDestroy(c->sstream); c->sstream = nullptr; }
-}
-
-/* head of a step, where hq_record_enqueue sits and behind the same waits: one hq_k_snapshot launch per due snapshot on the
- * compute stream into the next free slot; the copy stream waits for it, carries the slot to its pinned mirror and records
- * the slot's done event.  The launch reads d_u[now] and d_u[prev], which this step only reads; the next step overwrites
- * d_u[prev], and its kernels follow this launch on the compute stream or wait for events recorded behind it.  The bricks'
- * and the exchange chain's streams are held back behind the launch all the same, as they are behind hq_k_record: the
- * launch then has the memory system to itself and its time is the whole of what a snapshot adds to its step. */
-static int hq_snapshot_enqueue(hq_ctx* c, bool brick_stream)
-{
-    bool any = false;
-    for (auto& sn : c->snaps) {
-        if (!hq_cadence_due(sn.due, c->step)) continue;
-        const int32_t slot = hq_step_ring_push(&sn.ring, c->step);
-        if (slot < 0) return hq_fail(HQ_ERR_STATE, "a snapshot's slots are all pending%s", "");   /* (hq_output_check_room saw to it) */
-        char* d = sn.d_stage + (size_t)slot * sn.slot_bytes;
-        constexpr int32_t tile_rows = 256 * (16 / (int32_t)sizeof(hq_real));
-        const int64_t ntiles = ((int64_t)sn.count + tile_rows - 1) / tile_rows;
-        hq_k_snapshot<hq_real><<<(unsigned)std::min<int64_t>(ntiles, 8192), 256, 0, c->stream>>>(
-            sn.first, sn.count, sn.d_map, c->d_u[c->now], c->d_u[c->prev], c->dt,
-            (sn.fields & HQ_SNAP_TM1) ? (hq_real*)(d + sn.off[0]) : nullptr,
-            (sn.fields & HQ_SNAP_TM2) ? (hq_real*)(d + sn.off[1]) : nullptr,
-            (sn.fields & HQ_SNAP_VEL) ? (double*)(d + sn.off[2]) : nullptr);
-        HQ_HIP(hipEventRecord(c->ev_snapped, c->stream));
-        HQ_HIP(hipStreamWaitEvent(c->sstream, c->ev_snapped, 0));
-        HQ_HIP(hipMemcpyAsync(sn.h_stage + (size_t)slot * sn.slot_bytes, d, sn.slot_bytes, hipMemcpyDeviceToHost, c->sstream));
-        HQ_HIP(hipEventRecord(sn.done[(size_t)slot], c->sstream));
-        c->d2h_bytes += (int64_t)sn.slot_bytes;
-        any = true;
-    }
-    if (any && c->variant == HQ_VARIANT_PATCH) HQ_TRY(hq_hold_behind(c, brick_stream, c->ev_snapped));   /* (the last launch's record) */
-    return HQ_OK;
-}
+#include "hq_outputs.h"
 
 static int hq_phase(hq_ctx* c, int ph)
 {
@@ -1619,9 +1190,7 @@ static int hq_phase(hq_ctx* c, int ph)
                 if (c->ev_shared) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_shared, 0));
                 HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_patches, 0));
             }
-            if (!c->snaps.empty()) HQ_TRY(hq_snapshot_enqueue(c, bs));     /* solver_write_checkpoint / _output_wavefield, :4277-4278 */
-            if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, bs));        /* solver_output_planes / _stations, :4279-4280 */
-            if (!c->peaks.empty()) HQ_TRY(hq_peak_enqueue(c, bs));
+            HQ_TRY(hq_outputs_enqueue(c, bs));     /* solver_write_checkpoint / _output_wavefield / _planes / _stations, :4277-4280 */
             auto launch_bricks = [&]() {
                 if (c->bricks.nunits > 0)
                     hq_brick_launch(&c->bricks, c->d_u[c->now], c->d_u[c->prev], c->d_u[c->spare], c->plan.d_nt3, F, c->dt2,
@@ -1684,9 +1253,7 @@ static int hq_phase(hq_ctx* c, int ph)
              *  kernel time from the phase clock's events instead, and a timed batch enqueues exactly what hq_run does) */
             hq_mark(c);
         } else {
-            if (!c->snaps.empty()) HQ_TRY(hq_snapshot_enqueue(c, false));
-            if (!c->recs.empty()) HQ_TRY(hq_record_enqueue(c, false));
-            if (!c->peaks.empty()) HQ_TRY(hq_peak_enqueue(c, false));
+            HQ_TRY(hq_outputs_enqueue(c, false));
             HQ_TRY(hq_launch_source(c));                                   /* :4288 */
             HQ_TRY(hq_launch_element_scatter(c));                          /* :4290-4291 */
         }
@@ -2077,7 +1644,8 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
     auto bail = [&](int r) { hq_destroy(c); return r; };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
         return bail(hq_fail(HQ_ERR_DEVICE, "hipStreamCreate failed%s", ""));
-    if (hipEventCreateWithFlags(&c->ev_sent, hipEventDisableTiming) != hipSuccess)
+    if (hipEventCreateWithFlags(&c->ev_sent, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_output, hipEventDisableTiming) != hipSuccess)
         return bail(hq_fail(HQ_ERR_DEVICE, "hipEventCreate failed%s", ""));
 
     /* HQ_PATCH_VERBOSE: where hq_create's time goes */
@@ -2233,9 +1801,10 @@ extern "C" int hq_destroy(hq_ctx* c)
                      c->d_gkey, c->d_halo_err, c->an.d_c_out_id, c->an.d_c_in_id, c->an.d_s_out_id, c->an.d_s_in_id,
                      c->dn.d_c_out_id, c->dn.d_c_in_id, c->dn.d_s_out_id, c->dn.d_s_in_id };
     for (void* p : ptrs) if (p) hipFree(p);
-    hq_record_drop_all(c);
-    hq_peak_drop_all(c);
-    hq_snapshot_drop_all(c);
+    hq_outputs_drop(c, c->recs);
+    hq_outputs_drop(c, c->peaks);
+    hq_outputs_drop(c, c->snaps);
+    if (c->sstream) hipStreamDestroy(c->sstream);
     if (c->an.d_cmap_f && c->an.d_cmap_f != c->an.d_cmap) hipFree(c->an.d_cmap_f);
     if (c->an.d_smap_f && c->an.d_smap_f != c->an.d_smap) hipFree(c->an.d_smap_f);
     if (c->dn.d_cmap_f && c->dn.d_cmap_f != c->dn.d_cmap) hipFree(c->dn.d_cmap_f);
@@ -2249,6 +1818,7 @@ extern "C" int hq_destroy(hq_ctx* c)
         if (sc->d_s_dst) hipFree(sc->d_s_dst);
     }
     if (c->ev_sent) hipEventDestroy(c->ev_sent);
+    if (c->ev_output) hipEventDestroy(c->ev_output);
     if (c->cstream) { hipStreamSynchronize(c->cstream); hipStreamDestroy(c->cstream); }
     if (c->bstream) { hipStreamSynchronize(c->bstream); hipStreamDestroy(c->bstream); }
     for (auto& sl : c->clock) for (hipEvent_t e : sl.e) if (e) hipEventDestroy(e);
@@ -3017,363 +2587,6 @@ static int hq_gather_impl(hq_ctx* c, int32_t n, const int32_t* lnid, hq_real* o1
     }
     e = hq_quiesce(c);
     if (e != hipSuccess) return hq_fail(HQ_ERR_DEVICE, "gather failed: %s", hipGetErrorString(e));
-    return HQ_OK;
-}
-
-/* ---- sample recorders: entry points (include/hq_solver.h) ---- */
-
-extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* handle)
-{
-    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    if (d->npoints < 0 || d->rate <= 0 || d->capacity <= 0 || d->derivs < 0 || d->derivs > 2 ||
-        (d->npoints > 0 && (!d->ids || !d->phi)))
-        return hq_fail(HQ_ERR_ARG, "bad recorder description%s", "");
-    if (d->derivs == 2 && c->variant != HQ_VARIANT_PATCH)
-        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
-    const int32_t np = d->npoints;
-    for (int64_t i = 0; i < 8 * (int64_t)np; i++)
-        if (d->ids[i] < 0 || d->ids[i] >= c->N) return hq_fail(HQ_ERR_ARG, "node id out of range%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    /* the tables: device numbering, transposed to [8][np] */
-    std::vector<int32_t> ids((size_t)np * 8);
-    std::vector<double> phi((size_t)np * 8);
-    for (int32_t p = 0; p < np; p++)
-        for (int k = 0; k < 8; k++) {
-            const int32_t id = d->ids[8 * (size_t)p + k];
-            ids[(size_t)k * np + p] = c->perm.empty() ? id : c->perm[(size_t)id];
-            phi[(size_t)k * np + p] = d->phi[8 * (size_t)p + k];
-        }
-    hq_ctx::hq_recorder r;
-    r.np = np; r.derivs = d->derivs;
-    const size_t ring = (size_t)d->capacity * (size_t)np * 3 * (size_t)(1 + d->derivs);
-    const int64_t bytes0 = c->bytes;
-    int rc = hq_dev_alloc(c, &r.d_ids, ids.size());
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &r.d_phi, phi.size());
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &r.d_ring, ring);
-    hipError_t e = hipSuccess;
-    if (rc == HQ_OK && !c->ev_recorded) e = hipEventCreateWithFlags(&c->ev_recorded, hipEventDisableTiming);
-    if (rc == HQ_OK && e == hipSuccess && np > 0) {
-        e = hipMemcpy(r.d_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(r.d_phi, phi.data(), sizeof(double) * phi.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   /* the steps read the tables on other streams */
-    }
-    if (rc != HQ_OK || e != hipSuccess) {
-        if (r.d_ids) hipFree(r.d_ids);
-        if (r.d_phi) hipFree(r.d_phi);
-        if (r.d_ring) hipFree(r.d_ring);
-        c->bytes = bytes0;
-        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_record_add failed: %s", hipGetErrorString(e));
-    }
-    r.bytes = c->bytes - bytes0;
-    c->h2d_bytes += 12 * (int64_t)ids.size();
-    r.open(d->rate, INT32_MIN, d->capacity);                     /* every multiple of the rate, wherever `step` is set to */
-    r.id = c->rec_next_id++;
-    *handle = r.id;
-    c->recs.push_back(std::move(r));
-    return HQ_OK;
-}
-
-extern "C" int hq_record_pending(hq_ctx* c, int32_t handle, int32_t* nsamples, int32_t* first_step)
-{
-    if (!c || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const hq_ctx::hq_recorder* r = hq_output_find(c->recs, handle);
-    if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
-    *nsamples = r->ring.count;
-    if (first_step) *first_step = hq_step_ring_first_step(&r->ring);
-    return HQ_OK;
-}
-
-extern "C" int hq_record_fetch(hq_ctx* c, int32_t handle, int32_t max_samples, double* out, int32_t* steps,
-                               int32_t* nfetched)
-{
-    if (!c || !out || !steps || !nfetched || max_samples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
-    hq_ctx::hq_recorder* r = hq_output_find(c->recs, handle);
-    if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
-    *nfetched = 0;
-    const int32_t n = std::min(max_samples, r->ring.count), head = r->ring.head;
-    if (n == 0) return HQ_OK;
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t row = (size_t)r->np * 3 * (size_t)(1 + r->derivs);          /* doubles per sample */
-    const int32_t first = std::min(n, r->ring.capacity - head);              /* up to the ring's end, then from its start */
-    if (row > 0) {
-        HQ_HIP(hipMemcpy(out, r->d_ring + (size_t)head * row, sizeof(double) * row * (size_t)first, hipMemcpyDeviceToHost));
-        if (n > first)
-            HQ_HIP(hipMemcpy(out + (size_t)first * row, r->d_ring, sizeof(double) * row * (size_t)(n - first), hipMemcpyDeviceToHost));
-    }
-    for (int32_t k = 0; k < n; k++) steps[k] = r->steps[(size_t)hq_step_ring_slot_at(&r->ring, k)];
-    c->d2h_bytes += 8 * (int64_t)row * n;
-    hq_step_ring_pop(&r->ring, n);
-    *nfetched = n;
-    return HQ_OK;
-}
-
-extern "C" int hq_record_clear(hq_ctx* c)
-{
-    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    if (c->recs.empty()) return HQ_OK;
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    hq_record_drop_all(c);
-    return HQ_OK;
-}
-
-/* ---- peak-motion trackers: entry points (include/hq_solver.h) ---- */
-
-extern "C" int hq_peak_add(hq_ctx* c, const hq_peak_desc* d, int32_t* handle)
-{
-    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const int32_t all = HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC;
-    const int32_t K = d->nodes_per_point;
-    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->quantities == 0 || (d->quantities & ~all) != 0 ||
-        (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
-        return hq_fail(HQ_ERR_ARG, "bad peak tracker description%s", "");
-    if ((d->quantities & HQ_PEAK_ACC) && c->variant != HQ_VARIANT_PATCH)
-        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
-    const int32_t np = d->npoints;
-    for (int64_t i = 0; i < (int64_t)K * np; i++)
-        if (d->ids[i] < 0 || d->ids[i] >= c->N) return hq_fail(HQ_ERR_ARG, "node id out of range%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    /* the tables: device numbering, transposed to [K][np] */
-    std::vector<int32_t> ids((size_t)np * K);
-    std::vector<double> phi(K == 8 ? (size_t)np * 8 : 0);
-    for (int32_t p = 0; p < np; p++)
-        for (int k = 0; k < K; k++) {
-            const int32_t id = d->ids[(size_t)K * p + k];
-            ids[(size_t)k * np + p] = c->perm.empty() ? id : c->perm[(size_t)id];
-            if (K == 8) phi[(size_t)k * np + p] = d->phi[8 * (size_t)p + k];
-        }
-    hq_ctx::hq_peak_tracker t;
-    t.np = np; t.K = K; t.quantities = d->quantities; t.nq = hq_peak_nq(d->quantities);
-    t.due = { d->rate, d->first_step };
-    const size_t n = (size_t)t.nq * (size_t)np;
-    const int64_t bytes0 = c->bytes;
-    const bool had_event = c->ev_peaked != nullptr;
-    int rc = hq_dev_alloc(c, &t.d_ids, ids.size());
-    if (rc == HQ_OK && K == 8) rc = hq_dev_alloc(c, &t.d_phi, phi.size());
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_pk, HQ_PEAK_NVAL * n);
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_when, HQ_PEAK_NWHEN * n);
-    hipError_t e = hipSuccess;
-    if (rc == HQ_OK && !c->ev_peaked) e = hipEventCreateWithFlags(&c->ev_peaked, hipEventDisableTiming);
-    if (rc == HQ_OK && e == hipSuccess && np > 0) {
-        e = hipMemcpyAsync(t.d_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && K == 8)
-            e = hipMemcpyAsync(t.d_phi, phi.data(), sizeof(double) * phi.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hq_peak_zero(c, t);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   /* (the host tables go out of scope; the state is in place) */
-    }
-    if (rc != HQ_OK || e != hipSuccess) {
-        if (t.d_ids) hipFree(t.d_ids);
-        if (t.d_phi) hipFree(t.d_phi);
-        if (t.d_pk) hipFree(t.d_pk);
-        if (t.d_when) hipFree(t.d_when);
-        if (!had_event && c->ev_peaked) { hipEventDestroy(c->ev_peaked); c->ev_peaked = nullptr; }
-        c->bytes = bytes0;
-        (void)hipGetLastError();
-        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_peak_add failed: %s", hipGetErrorString(e));
-    }
-    t.bytes = c->bytes - bytes0;
-    c->h2d_bytes += 4 * (int64_t)ids.size() + 8 * (int64_t)phi.size();
-    t.id = c->peak_next_id++;
-    *handle = t.id;
-    c->peaks.push_back(t);
-    return HQ_OK;
-}
-
-static hq_ctx::hq_peak_tracker* hq_peak_find(hq_ctx* c, int32_t handle)
-{
-    for (auto& t : c->peaks)
-        if (t.id == handle) return &t;
-    return nullptr;
-}
-
-/* the state crosses PCIe as the device keeps it ([nq][5][np], [nq][2][np]); the caller's arrays are [np][nq][5], [np][nq][2] */
-extern "C" int hq_peak_fetch(hq_ctx* c, int32_t handle, double* peaks, int32_t* when, int64_t* nsamples)
-{
-    if (!c || !peaks || !when || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_peak_tracker* t = hq_peak_find(c, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->np, nq = (size_t)t->nq, n = np * nq;
-    *nsamples = t->nsamples;
-    if (n == 0) return HQ_OK;
-    std::vector<double> pk(HQ_PEAK_NVAL * n);
-    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
-    HQ_HIP(hipMemcpyAsync(pk.data(), t->d_pk, sizeof(double) * pk.size(), hipMemcpyDeviceToHost, c->stream));
-    HQ_HIP(hipMemcpyAsync(wh.data(), t->d_when, sizeof(int32_t) * wh.size(), hipMemcpyDeviceToHost, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    for (size_t p = 0; p < np; p++)
-        for (size_t q = 0; q < nq; q++) {
-            for (size_t j = 0; j < HQ_PEAK_NVAL; j++) peaks[(p * nq + q) * HQ_PEAK_NVAL + j] = pk[(q * HQ_PEAK_NVAL + j) * np + p];
-            for (size_t j = 0; j < HQ_PEAK_NWHEN; j++) when[(p * nq + q) * HQ_PEAK_NWHEN + j] = wh[(q * HQ_PEAK_NWHEN + j) * np + p];
-        }
-    c->d2h_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
-    return HQ_OK;
-}
-
-extern "C" int hq_peak_load(hq_ctx* c, int32_t handle, const double* peaks, const int32_t* when, int64_t nsamples)
-{
-    if (!c || !peaks || !when || nsamples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
-    hq_ctx::hq_peak_tracker* t = hq_peak_find(c, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->np, nq = (size_t)t->nq, n = np * nq;
-    t->nsamples = nsamples;
-    if (n == 0) return HQ_OK;
-    std::vector<double> pk(HQ_PEAK_NVAL * n);
-    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
-    for (size_t p = 0; p < np; p++)
-        for (size_t q = 0; q < nq; q++) {
-            for (size_t j = 0; j < HQ_PEAK_NVAL; j++) pk[(q * HQ_PEAK_NVAL + j) * np + p] = peaks[(p * nq + q) * HQ_PEAK_NVAL + j];
-            for (size_t j = 0; j < HQ_PEAK_NWHEN; j++) wh[(q * HQ_PEAK_NWHEN + j) * np + p] = when[(p * nq + q) * HQ_PEAK_NWHEN + j];
-        }
-    HQ_HIP(hipMemcpyAsync(t->d_pk, pk.data(), sizeof(double) * pk.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipMemcpyAsync(t->d_when, wh.data(), sizeof(int32_t) * wh.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    c->h2d_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
-    return HQ_OK;
-}
-
-extern "C" int hq_peak_reset(hq_ctx* c, int32_t handle)
-{
-    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_peak_tracker* t = hq_peak_find(c, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    HQ_HIP(hq_peak_zero(c, *t));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    t->nsamples = 0;
-    return HQ_OK;
-}
-
-extern "C" int hq_peak_clear(hq_ctx* c)
-{
-    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    if (c->peaks.empty()) return HQ_OK;
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    hq_peak_drop_all(c);
-    return HQ_OK;
-}
-
-/* ---- field snapshots: entry points (include/hq_solver.h) ---- */
-
-extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* handle)
-{
-    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const int32_t all = HQ_SNAP_TM1 | HQ_SNAP_TM2 | HQ_SNAP_VEL;
-    if (d->count < 1 || d->first < 0 || (int64_t)d->first + d->count > c->N || d->rate < 1 || d->slots < 1 ||
-        d->fields == 0 || (d->fields & ~all) != 0)
-        return hq_fail(HQ_ERR_ARG, "bad snapshot description%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    hq_ctx::hq_snapshot sn;
-    sn.first = d->first; sn.count = d->count; sn.fields = d->fields;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t n3 = 3 * (size_t)d->count;
-    size_t at = 0;
-    sn.off[0] = at; if (d->fields & HQ_SNAP_TM1) at += pad(sizeof(hq_real) * n3);
-    sn.off[1] = at; if (d->fields & HQ_SNAP_TM2) at += pad(sizeof(hq_real) * n3);
-    sn.off[2] = at; if (d->fields & HQ_SNAP_VEL) at += pad(sizeof(double) * n3);
-    sn.slot_bytes = at;
-    const int64_t bytes0 = c->bytes;
-    const bool had_stream = c->sstream != nullptr, had_event = c->ev_snapped != nullptr;
-    int rc = hq_dev_alloc(c, &sn.d_stage, sn.slot_bytes * (size_t)d->slots);
-    if (rc == HQ_OK && !c->perm.empty()) rc = hq_dev_alloc(c, &sn.d_map, (size_t)d->count);
-    if (rc == HQ_OK && hipHostMalloc((void**)&sn.h_stage, sn.slot_bytes * (size_t)d->slots, hipHostMallocDefault) != hipSuccess) {
-        sn.h_stage = nullptr;
-        rc = hq_fail(HQ_ERR_NOMEM, "hipHostMalloc failed for the snapshot's pinned buffers%s", "");
-    }
-    hipError_t e = hipSuccess;
-    if (rc == HQ_OK && !c->sstream) e = hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking);
-    if (rc == HQ_OK && e == hipSuccess && !c->ev_snapped) e = hipEventCreateWithFlags(&c->ev_snapped, hipEventDisableTiming);
-    sn.done.assign((size_t)d->slots, nullptr);
-    for (int32_t k = 0; k < d->slots && rc == HQ_OK && e == hipSuccess; k++)
-        e = hipEventCreateWithFlags(&sn.done[(size_t)k], hipEventDisableTiming);
-    if (rc == HQ_OK && e == hipSuccess && sn.d_map) {            /* perm[first .. first + count): the caller's id -> the device's */
-        e = hipMemcpy(sn.d_map, c->perm.data() + d->first, sizeof(int32_t) * (size_t)d->count, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  /* the steps read the map on other streams */
-    }
-    if (rc != HQ_OK || e != hipSuccess) {
-        if (sn.d_stage) hipFree(sn.d_stage);
-        if (sn.d_map) hipFree(sn.d_map);
-        if (sn.h_stage) hipHostFree(sn.h_stage);
-        for (hipEvent_t ev : sn.done) if (ev) hipEventDestroy(ev);
-        if (!had_stream && c->sstream) { hipStreamDestroy(c->sstream); c->sstream = nullptr; }
-        if (!had_event && c->ev_snapped) { hipEventDestroy(c->ev_snapped); c->ev_snapped = nullptr; }
-        c->bytes = bytes0;
-        (void)hipGetLastError();
-        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_snapshot_add failed: %s", hipGetErrorString(e));
-    }
-    sn.bytes = c->bytes - bytes0;
-    if (sn.d_map) c->h2d_bytes += 4 * (int64_t)d->count;
-    sn.open(d->rate, d->first_step, d->slots);
-    sn.id = c->snap_next_id++;
-    *handle = sn.id;
-    c->snaps.push_back(std::move(sn));
-    return HQ_OK;
-}
-
-extern "C" int hq_snapshot_pending(hq_ctx* c, int32_t handle, int32_t* npending, int32_t* nready, int32_t* first_step)
-{
-    if (!c || !npending) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const hq_ctx::hq_snapshot* sn = hq_output_find(c->snaps, handle);
-    if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
-    *npending = sn->ring.count;
-    if (nready) {
-        int32_t n = 0;
-        for (int32_t k = 0; k < sn->ring.count; k++)
-            n += hipEventQuery(sn->done[(size_t)hq_step_ring_slot_at(&sn->ring, k)]) == hipSuccess;
-        (void)hipGetLastError();                                 /* (hipErrorNotReady is an answer, not an error) */
-        *nready = n;
-    }
-    if (first_step) *first_step = hq_step_ring_first_step(&sn->ring);
-    return HQ_OK;
-}
-
-/* `bytes` from the pinned mirror into the caller's array; the large ones on all host threads (one thread moves ~10 GB/s) */
-static void hq_host_copy(void* dst, const void* src, size_t bytes)
-{
-    const size_t chunk = (size_t)4 << 20;
-    const int64_t nchunks = (int64_t)((bytes + chunk - 1) / chunk);
-#pragma omp parallel for schedule(static) if (nchunks > 4)
-    for (int64_t k = 0; k < nchunks; k++) {
-        const size_t at = (size_t)k * chunk;
-        memcpy((char*)dst + at, (const char*)src + at, std::min(chunk, bytes - at));
-    }
-}
-
-extern "C" int hq_snapshot_fetch(hq_ctx* c, int32_t handle, hq_real* tm1, hq_real* tm2, double* vel, int32_t* step)
-{
-    if (!c || !step) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_snapshot* sn = hq_output_find(c->snaps, handle);
-    if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
-    if ((tm1 && !(sn->fields & HQ_SNAP_TM1)) || (tm2 && !(sn->fields & HQ_SNAP_TM2)) || (vel && !(sn->fields & HQ_SNAP_VEL)))
-        return hq_fail(HQ_ERR_ARG, "the snapshot does not hold a field that an output pointer was given for%s", "");
-    *step = -1;
-    if (sn->ring.count == 0) return HQ_OK;
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hipEventSynchronize(sn->done[(size_t)sn->ring.head]));   /* this slot's copy -- not the steps enqueued behind it */
-    const char* h = sn->h_stage + (size_t)sn->ring.head * sn->slot_bytes;
-    const size_t n3 = 3 * (size_t)sn->count;
-    if (tm1) hq_host_copy(tm1, h + sn->off[0], sizeof(hq_real) * n3);
-    if (tm2) hq_host_copy(tm2, h + sn->off[1], sizeof(hq_real) * n3);
-    if (vel) hq_host_copy(vel, h + sn->off[2], sizeof(double) * n3);
-    *step = hq_step_ring_first_step(&sn->ring);
-    hq_step_ring_pop(&sn->ring, 1);
-    return HQ_OK;
-}
-
-extern "C" int hq_snapshot_clear(hq_ctx* c)
-{
-    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    if (c->snaps.empty()) return HQ_OK;
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    if (c->sstream) HQ_HIP(hipStreamSynchronize(c->sstream));
-    hq_snapshot_drop_all(c);
     return HQ_OK;
 }
 

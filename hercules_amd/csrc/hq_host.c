@@ -35,6 +35,7 @@
 #include "hq_host.h"
 #include "hq_cadence.h"
 #include "hq_peak.h"
+#include "hq_sample.h"
 
 #define HQH_PI 3.14159265358979323846
 
@@ -1397,27 +1398,25 @@ int hqh_station_header(char* buf, int32_t cap, int32_t derivs)
     return HQ_OK;
 }
 
-/* interpolate_station_displacements, psolve.c:6705-6787: the displacement sum over the 8 nodes;
- * for the velocity the same accumulator has phi * tm2 taken off node by node and is divided by dt;
- * for the acceleration phi * tm2 comes off once more and phi * tm3 is added, over dt^2. */
+static const int64_t hqh_block_rows[8] = { 0, 3, 6, 9, 12, 15, 18, 21 };   /* a point's nodes in a contiguous [8][3] block */
+
+/* interpolate_station_displacements, psolve.c:6705-6787: hq_sample.h's accumulator, the text the device's recorders and
+ * trackers compile, on the caller's contiguous blocks */
 int hqh_station_kinematics(const double* phi, const double* tm1, const double* tm2, const double* tm3,
                            double dt, int32_t derivs, double* vals)
 {
     if (!phi || !tm1 || !vals || derivs < 0 || derivs > 2 || (derivs >= 1 && !tm2) || (derivs == 2 && !tm3))
         return HQ_ERR_ARG;
     double d[3] = { 0.0, 0.0, 0.0 };
-    for (int c = 0; c < 8; c++)
-        for (int a = 0; a < 3; a++) d[a] += phi[c] * tm1[3 * c + a];
+    hq_sample_disp(8, phi, hqh_block_rows, tm1, d);
     for (int a = 0; a < 3; a++) vals[a] = d[a];
     if (derivs >= 1) {
-        for (int c = 0; c < 8; c++)
-            for (int a = 0; a < 3; a++) d[a] -= phi[c] * tm2[3 * c + a];
+        hq_sample_vel(8, phi, hqh_block_rows, tm2, d);
         for (int a = 0; a < 3; a++) vals[3 + a] = d[a] / dt;
     }
     if (derivs == 2) {
         const double dt2 = dt * dt;                              /* Param.theDeltaTSquared, psolve.c:998 */
-        for (int c = 0; c < 8; c++)
-            for (int a = 0; a < 3; a++) { d[a] -= phi[c] * tm2[3 * c + a]; d[a] += phi[c] * tm3[3 * c + a]; }
+        hq_sample_acc(8, phi, hqh_block_rows, tm2, tm3, d);
         for (int a = 0; a < 3; a++) vals[6 + a] = d[a] / dt2;
     }
     return HQ_OK;
@@ -1736,11 +1735,9 @@ static int hqh_planes_out(hqh_run_state* st, int from_recorder)
         if (rc != HQ_OK) return rc;
         for (int64_t s = 0; s < st->npp; s++) {
             if (rp->plane_mine && !rp->plane_mine[s]) continue;
-            for (int d = 0; d < 3; d++) {
-                double acc = 0.0;
-                for (int c = 0; c < 8; c++) acc += rp->plane_phi[8 * s + c] * st->pu[(8 * s + c) * 3 + d];
-                st->pbuf[3 * s + d] = acc;
-            }
+            double* d = st->pbuf + 3 * s;
+            d[0] = d[1] = d[2] = 0.0;
+            hq_sample_disp(8, rp->plane_phi + 8 * s, hqh_block_rows, st->pu + 24 * s, d);
         }
     }
     int64_t off = 0;

@@ -1,0 +1,731 @@
+/*
+ * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion trackers, field
+ * snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at the head of a step and the hq_record_*
+ * / hq_peak_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
+ */
+#ifndef HQ_OUTPUTS_H
+#define HQ_OUTPUTS_H
+
+/*
+ * One sample of a recorder (hq_record_add): interpolate_station_displacements (psolve.c:6705-6787) / Old_planes_print
+ * (io_planes.c:176-200) on the device-resident state.  One lane per point, consecutive lanes on consecutive points; ids
+ * and phi are stored transposed ([8][np]) so that a wave reads them in whole lines.  Eight gathers of one 3-vector from
+ * each of u1 = u(t), u2 = u(t - dt), u3 = u(t - 2 dt) as far as `derivs` needs them, every value widened to double first
+ * (hq_real is float in the f32 library), summed by hq_sample.h, the text hqh_station_kinematics (hq_host.c) compiles: the
+ * samples must equal the host route's bit for bit (tests/test_gpu_recorders.py).
+ * A memory-bound gather of up to 3 x 8 x 24 bytes per point; a plane's points are the bulk of it.
+ */
+__global__ void __launch_bounds__(256)
+hq_k_record(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
+            const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
+            double dt, double dt2, int32_t derivs, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= np) return;
+    int64_t row[8];
+    double w[8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
+        w[c] = phi[(int64_t)c * np + p];
+    }
+    double* o = out + (int64_t)p * (3 * (1 + derivs));
+    double d[3] = { 0.0, 0.0, 0.0 };
+    hq_sample_disp(8, w, row, u1, d);
+    for (int a = 0; a < 3; a++) o[a] = d[a];
+    if (derivs >= 1) {
+        hq_sample_vel(8, w, row, u2, d);
+        for (int a = 0; a < 3; a++) o[3 + a] = d[a] / dt;
+    }
+    if (derivs == 2) {
+        hq_sample_acc(8, w, row, u2, u3, d);
+        for (int a = 0; a < 3; a++) o[6 + a] = d[a] / dt2;
+    }
+}
+
+/*
+ * One due step of a peak-motion tracker (hq_peak_add): the sample hq_k_record would take at the point -- hq_sample.h's
+ * stages, the text the recorder compiles, so that it IS the recorder's sample bit for bit -- folded into the point's
+ * running state in place (hq_peak.h) instead of being appended to a ring.
+ * One lane per point, no atomics: a point belongs to one lane, and the launches of one stream are ordered.
+ *   K = 8: eight nodes and trilinear weights per point (stations, planes), ids and phi transposed to [8][np] as the
+ *          recorder's are.
+ *   K = 1: the point is a node (surface maps): no weight table -- weight 1, exactly the recorder's sums with weights
+ *          (1, 0, ..., 0) (hq_sample.h tells why) -- and one gather per field.
+ * The state is [nq][5][np] doubles and [nq][2][np] int32, nq the set bits of `quantities` in the order displacement,
+ * velocity, acceleration: a wave reads each of its rows in whole lines, and a lane writes only what it raised -- once a
+ * point's peak has passed, the step costs it reads alone.  u2 / u3 are read only if the mask needs them.
+ * Bytes per point and step, K = 1, velocity only: 4 (id) + 48 (u1, u2; 24 in the f32 library) + 40 of peaks read (`when`
+ * is only ever written); K = 8, all three quantities: 96 of tables + 576 of gathers + 120 of state.
+ */
+template <int K>
+__global__ void __launch_bounds__(256)
+hq_k_peak(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
+          const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
+          double dt, double dt2, int32_t quantities, int32_t step, double* __restrict__ pk, int32_t* __restrict__ when)
+{
+#pragma clang fp contract(off)
+    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= np) return;
+    const bool vel = (quantities & HQ_PEAK_VEL) != 0, acc = (quantities & HQ_PEAK_ACC) != 0;
+    int64_t row[K];
+    double wk[K];
+#pragma unroll
+    for (int c = 0; c < K; c++) {
+        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
+        if (K > 1) wk[c] = phi[(int64_t)c * np + p];
+    }
+    const double* w = K > 1 ? wk : nullptr;                      /* (a node: weight 1, hq_sample.h) */
+    double* s = pk + p;
+    int32_t* sw = when + p;
+    double d[3] = { 0.0, 0.0, 0.0 };
+    hq_sample_disp(K, w, row, u1, d);
+    if (quantities & HQ_PEAK_DISP) {
+        hq_peak_fold(d[0], d[1], d[2], step, s, np, sw, np);
+        s += (int64_t)HQ_PEAK_NVAL * np; sw += (int64_t)HQ_PEAK_NWHEN * np;
+    }
+    if (vel || acc) {
+        hq_sample_vel(K, w, row, u2, d);
+        if (vel) {
+            hq_peak_fold(d[0] / dt, d[1] / dt, d[2] / dt, step, s, np, sw, np);
+            s += (int64_t)HQ_PEAK_NVAL * np; sw += (int64_t)HQ_PEAK_NWHEN * np;
+        }
+    }
+    if (acc) {
+        hq_sample_acc(K, w, row, u2, u3, d);
+        hq_peak_fold(d[0] / dt2, d[1] / dt2, d[2] / dt2, step, s, np, sw, np);
+    }
+}
+
+/*
+ * One field snapshot (hq_snapshot_add): the rows [first, first + count) of u1 = u(t), u2 = u(t - dt) out of the device's
+ * numbering into a staging slot in the caller's (octor) order -- hq_field_to_host's un-permutation, done at HBM speed
+ * ahead of the copy instead of on the host behind it.  A streaming permutation: per node 4 bytes of map, 24-48 bytes of
+ * state read, 24-72 written; no arithmetic but the velocity's, (double)u1 - (double)u2 over dt, contraction off
+ * (hqh_wavefield_write's write_velocity, bit for bit).
+ * The OUTPUT is what the lanes are laid over: the slot's fields are flat arrays of 3 count scalars, and a lane owns V =
+ * 16 / sizeof(T) consecutive ones (2 doubles, 4 floats -- they may straddle two rows), so every store is a 16-byte store
+ * and a wave's stores cover 1 KiB of consecutive output rows.  The reads are gathers of single scalars, lane by lane: the
+ * three lanes (or one and a half) of a row read its 24 (12) bytes side by side, and wherever the map runs on -- inside a
+ * brick's tile the x-neighbours of the octor order are neighbours on the device too, 64 at a time, and on contexts without
+ * a renumbering everywhere -- consecutive lanes read consecutive addresses and the wave's loads merge into whole lines
+ * like those of a plain copy.  Where the map jumps, the other rows of the lines it touches are read by the same workgroup
+ * (a tile of 256 V consecutive octor rows is a compact cube of the mesh) and come out of L2.
+ * A workgroup takes tiles of 256 V rows = 768 lane groups, three per thread (independent: their loads are in flight
+ * together); 256 V rows are a multiple of 16 bytes in every field, so each group's stores are aligned.  map == NULL: the
+ * device numbers the nodes as the caller does.  o1 / o2 / ov == NULL: that field is not wanted.
+ */
+template <typename T>
+__global__ void __launch_bounds__(256)
+hq_k_snapshot(int32_t first, int32_t count, const int32_t* __restrict__ map, const T* __restrict__ u1,
+              const T* __restrict__ u2, double dt, T* __restrict__ o1, T* __restrict__ o2, double* __restrict__ ov)
+{
+#pragma clang fp contract(off)
+    constexpr int V = 16 / (int)sizeof(T);
+    constexpr int32_t TR = 256 * V;                              /* rows per tile */
+    typedef T vecT __attribute__((ext_vector_type(V)));         /* 16 bytes: one global_store_dwordx4 */
+    typedef double vecD __attribute__((ext_vector_type(2)));
+    const int32_t ntiles = (count + TR - 1) / TR;
+    const bool want1 = o1 != nullptr || ov != nullptr, want2 = o2 != nullptr || ov != nullptr;
+    for (int32_t tile = (int32_t)blockIdx.x; tile < ntiles; tile += (int32_t)gridDim.x) {
+        const int32_t row0 = tile * TR;
+        const int32_t nscal = 3 * min(TR, count - row0);         /* scalars of this tile */
+        const int64_t base = 3 * (int64_t)row0;
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            const int32_t j0 = ((int32_t)threadIdx.x + 256 * m) * V;
+            if (j0 >= nscal) continue;
+            T a[V], b[V];
+#pragma unroll
+            for (int k = 0; k < V; k++) {
+                const int32_t j = min(j0 + k, nscal - 1);        /* (a lane group past the end re-reads the last scalar) */
+                const int32_t n = j / 3;
+                const int64_t row = map ? (int64_t)map[row0 + n] : (int64_t)first + row0 + n;
+                const int64_t src = 3 * row + (j - 3 * n);
+                a[k] = want1 ? u1[src] : (T)0;
+                b[k] = want2 ? u2[src] : (T)0;
+            }
+            const bool whole = j0 + V <= nscal;
+            if (o1) {
+                if (whole) {
+                    vecT w;
+#pragma unroll
+                    for (int k = 0; k < V; k++) w[k] = a[k];
+                    *(vecT*)(o1 + base + j0) = w;
+                }
+                else {
+#pragma unroll
+                    for (int k = 0; k < V; k++) if (j0 + k < nscal) o1[base + j0 + k] = a[k];
+                }
+            }
+            if (o2) {
+                if (whole) {
+                    vecT w;
+#pragma unroll
+                    for (int k = 0; k < V; k++) w[k] = b[k];
+                    *(vecT*)(o2 + base + j0) = w;
+                }
+                else {
+#pragma unroll
+                    for (int k = 0; k < V; k++) if (j0 + k < nscal) o2[base + j0 + k] = b[k];
+                }
+            }
+            if (ov) {
+                double v[V];
+#pragma unroll
+                for (int k = 0; k < V; k++) v[k] = ((double)a[k] - (double)b[k]) / dt;
+                if (whole) {
+#pragma unroll
+                    for (int k = 0; k < V; k += 2) { vecD w = { v[k], v[k + 1] }; *(vecD*)(ov + base + j0 + k) = w; }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < V; k++) if (j0 + k < nscal) ov[base + j0 + k] = v[k];
+                }
+            }
+        }
+    }
+}
+
+/* ---- the outputs' state: the structs hq_ctx declares ---- */
+
+/* what the outputs share (hq_cadence.h): the steps one is due at and the ring of its pending slots, accounted on the
+ * host -- which steps are due follows from `step` alone.  (A tracker keeps no ring: capacity 0, never asked for room.) */
+struct hq_ctx::hq_output {
+    int32_t id = 0;
+    hq_cadence due = { 1, 0 };
+    hq_step_ring ring = { nullptr, 0, 0, 0 };
+    std::vector<int32_t> steps;   /* [capacity] the ring's storage: a move keeps the buffer, and so ring.steps */
+    int64_t bytes = 0;            /* device memory of this output (part of `bytes`) */
+    void open(int32_t rate, int64_t first_step, int32_t capacity)
+    {
+        due = { rate, first_step };
+        steps.assign((size_t)capacity, 0);
+        ring = { steps.data(), capacity, 0, 0 };
+    }
+};
+/* the points of a recorder or a tracker (hq_points_build): K nodes each, ids and weights transposed so that a wave reads
+ * them in whole lines */
+struct hq_point_set {
+    int32_t np = 0, K = 8;
+    int32_t* d_ids = nullptr;     /* [K][np] device numbering */
+    double* d_phi = nullptr;      /* [8][np]; NULL for K = 1 */
+    int64_t h2d() const { return (K == 8 ? 12 : 4) * (int64_t)K * np; }   /* bytes the upload carried: 4 per id, 8 per weight */
+};
+/* sample recorders (hq_record_add): rings in device memory */
+struct hq_ctx::hq_recorder : hq_ctx::hq_output {
+    hq_point_set pts;
+    int32_t derivs = 0;
+    double* d_ring = nullptr;     /* [capacity][np][3 (1 + derivs)] */
+};
+/* peak-motion trackers (hq_peak_add): a running state per point updated in place by hq_k_peak -- no ring, no pending
+ * samples, nothing for hq_run to count */
+struct hq_ctx::hq_peak_tracker : hq_ctx::hq_output {
+    hq_point_set pts;
+    int32_t quantities = 0, nq = 0;
+    int64_t nsamples = 0;         /* due steps folded or enqueued so far: accounted here, from `step` alone */
+    double* d_pk = nullptr;       /* [nq][5][np] */
+    int32_t* d_when = nullptr;    /* [nq][2][np] */
+};
+/* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
+ * pinned host memory.  A slot holds the fields one behind the other,
+ * each at a 256-byte boundary (off[]; the same layout on both sides, so one copy carries a slot).  sstream, the copy
+ * stream, exists from the first hq_snapshot_add on: behind each hq_k_snapshot launch ev_output is
+ * recorded on the compute stream and waited for by sstream, which copies the slot and records the slot's done event */
+struct hq_ctx::hq_snapshot : hq_ctx::hq_output {
+    int32_t first = 0, count = 0, fields = 0;
+    int32_t* d_map = nullptr;     /* [count] device id of node first + i; NULL on contexts without a renumbering */
+    char* d_stage = nullptr;      /* [slots][slot_bytes] */
+    char* h_stage = nullptr;      /* the same, pinned host memory */
+    size_t off[3] = { 0, 0, 0 };  /* tm1, tm2, vel inside a slot */
+    size_t slot_bytes = 0;
+    std::vector<hipEvent_t> done; /* [slots] the slot's copy has arrived */
+};
+
+/* ---- device outputs: what the three kinds share (hq_cadence.h) ---- */
+
+/* do the due steps of [c->step, c->step + nsteps) fit into every ring's free slots? */
+template <typename T>
+static bool hq_outputs_have_room(const std::vector<T>& outs, int64_t step, int32_t nsteps)
+{
+    for (const auto& o : outs)
+        if (hq_cadence_count(o.due, step, step + nsteps) > hq_step_ring_room(&o.ring)) return false;
+    return true;
+}
+
+/* the recorders' rings and the snapshots' slots: what hq_run, hq_group_run and hq_run_timed ask before they enqueue */
+static int hq_output_check_room(const hq_ctx* c, int32_t nsteps)
+{
+    if (!hq_outputs_have_room(c->recs, c->step, nsteps))
+        return hq_fail(HQ_ERR_STATE, "a recorder's ring would overflow: fetch its samples first (hq_record_fetch)%s", "");
+    if (!hq_outputs_have_room(c->snaps, c->step, nsteps))
+        return hq_fail(HQ_ERR_STATE, "a snapshot's slots would run out: fetch the pending ones first (hq_snapshot_fetch)%s", "");
+    return HQ_OK;
+}
+
+template <typename T>
+static T* hq_output_find(std::vector<T>& outs, int32_t handle)
+{
+    for (auto& o : outs)
+        if (o.id == handle) return &o;
+    return nullptr;
+}
+
+static void hq_points_free(hq_point_set* ps)
+{
+    if (ps->d_ids) hipFree(ps->d_ids);
+    if (ps->d_phi) hipFree(ps->d_phi);
+    ps->d_ids = nullptr; ps->d_phi = nullptr;
+}
+
+/* the tables of np points from the caller's [np][K] ids and [np][8] weights (K = 8 only): every id checked, device numbering,
+ * transposed to [K][np], uploaded ON the compute stream and waited for -- the steps read the tables on other streams, the host
+ * tables go out of scope, hq_upload tells what a null-stream operation cost.  A failure leaves nothing allocated; h2d() the caller counts. */
+static int hq_points_build(hq_ctx* c, int32_t np, int32_t K, const int32_t* ids_in, const double* phi_in, hq_point_set* ps, const char* who)
+{
+    for (int64_t i = 0; i < (int64_t)K * np; i++)
+        if (ids_in[i] < 0 || ids_in[i] >= c->N) return hq_fail(HQ_ERR_ARG, "node id out of range%s", "");
+    std::vector<int32_t> ids((size_t)np * K);
+    std::vector<double> phi(K == 8 ? (size_t)np * 8 : 0);
+    for (int32_t p = 0; p < np; p++)
+        for (int k = 0; k < K; k++) {
+            const int32_t id = ids_in[(size_t)K * p + k];
+            ids[(size_t)k * np + p] = c->perm.empty() ? id : c->perm[(size_t)id];
+            if (K == 8) phi[(size_t)k * np + p] = phi_in[8 * (size_t)p + k];
+        }
+    ps->np = np; ps->K = K;
+    const int64_t bytes0 = c->bytes;
+    int rc = hq_dev_alloc(c, &ps->d_ids, ids.size());
+    if (rc == HQ_OK && K == 8) rc = hq_dev_alloc(c, &ps->d_phi, phi.size());
+    hipError_t e = hipSuccess;
+    if (rc == HQ_OK && np > 0) {
+        e = hipMemcpyAsync(ps->d_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && K == 8)
+            e = hipMemcpyAsync(ps->d_phi, phi.data(), sizeof(double) * phi.size(), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    if (rc != HQ_OK || e != hipSuccess) {
+        hq_points_free(ps);
+        c->bytes = bytes0;
+        (void)hipGetLastError();
+        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "%s failed: %s", who, hipGetErrorString(e));
+    }
+    return HQ_OK;
+}
+
+static void hq_output_free(hq_ctx::hq_recorder& r)
+{
+    hq_points_free(&r.pts);
+    if (r.d_ring) hipFree(r.d_ring);
+}
+
+/* head of a step: one hq_k_record launch per due recorder on the compute stream, behind the waits phase 0 has already
+ * made for the last step's shared displacements and bricks.  On a due step only, the streams whose kernels of THIS
+ * step write into d_u[spare] -- which the launch reads as u(t - 2 dt) -- are held back behind it: the bricks' own stream,
+ * and the exchange chain's (hq_k_interface_update, the unpack).  The patches follow on the compute stream itself. */
+static int hq_record_launch(hq_ctx* c, hq_ctx::hq_recorder& r)
+{
+    const int32_t slot = hq_step_ring_push(&r.ring, c->step);
+    if (slot < 0) return hq_fail(HQ_ERR_STATE, "a recorder's ring is full%s", "");   /* (hq_output_check_room saw to it) */
+    if (r.pts.np <= 0) return HQ_OK;
+    const int32_t ncomp = 3 * (1 + r.derivs);
+    hq_k_record<<<hq_blocks(r.pts.np, 256), 256, 0, c->stream>>>(
+        r.pts.np, r.pts.d_ids, r.pts.d_phi, c->d_u[c->now], c->d_u[c->prev], r.derivs == 2 ? c->d_u[c->spare] : c->d_u[c->prev],
+        c->dt, c->dt2, r.derivs, r.d_ring + (int64_t)slot * r.pts.np * ncomp);
+    return HQ_OK;
+}
+
+static void hq_output_free(hq_ctx::hq_peak_tracker& t)
+{
+    hq_points_free(&t.pts);
+    if (t.d_pk) hipFree(t.d_pk);
+    if (t.d_when) hipFree(t.d_when);
+}
+
+/* the state of one tracker as it is before its first sample: peaks 0, `when` -1 (every byte 0xff) -- ON the compute stream
+ * (hq_upload tells what a null-stream memset cost); the caller waits */
+static hipError_t hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
+{
+    const size_t n = (size_t)t.nq * (size_t)t.pts.np;
+    if (n == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(t.d_pk, 0, sizeof(double) * HQ_PEAK_NVAL * n, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t.d_when, 0xff, sizeof(int32_t) * HQ_PEAK_NWHEN * n, c->stream);
+    return e;
+}
+
+/* head of a step, where hq_record_launch sits and behind the same waits: one hq_k_peak launch per due tracker on the
+ * compute stream.  A launch that tracks accelerations reads d_u[spare] as u(t - 2 dt), the buffer THIS step's bricks and
+ * exchange chain overwrite: their streams are held back behind it, exactly as behind hq_k_record.  Without accelerations
+ * the launch reads d_u[now] and d_u[prev] only, which this step only reads -- and the next step's kernels follow on the
+ * compute stream or wait for events recorded behind the launch -- so nothing is held: a velocity map must not serialise
+ * every step of its run. */
+static void hq_peak_launch(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
+{
+    t.nsamples++;
+    if (t.pts.np <= 0) return;
+    const hq_real* u3 = (t.quantities & HQ_PEAK_ACC) ? c->d_u[c->spare] : c->d_u[c->prev];
+    const auto k = t.pts.K == 1 ? hq_k_peak<1> : hq_k_peak<8>;
+    k<<<hq_blocks(t.pts.np, 256), 256, 0, c->stream>>>(t.pts.np, t.pts.d_ids, t.pts.d_phi, c->d_u[c->now], c->d_u[c->prev], u3,
+                                                        c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
+}
+
+static void hq_output_free(hq_ctx::hq_snapshot& sn)
+{
+    if (sn.d_map) hipFree(sn.d_map);
+    if (sn.d_stage) hipFree(sn.d_stage);
+    if (sn.h_stage) hipHostFree(sn.h_stage);
+    for (hipEvent_t e : sn.done) if (e) hipEventDestroy(e);
+}
+
+/* head of a step, where hq_record_launch sits and behind the same waits: one hq_k_snapshot launch per due snapshot on the
+ * compute stream into the next free slot; the copy stream waits for it, carries the slot to its pinned mirror and records
+ * the slot's done event.  The launch reads d_u[now] and d_u[prev], which this step only reads; the next step overwrites
+ * d_u[prev], and its kernels follow this launch on the compute stream or wait for events recorded behind it.  The bricks'
+ * and the exchange chain's streams are held back behind the launch all the same, as they are behind hq_k_record: the
+ * launch then has the memory system to itself and its time is the whole of what a snapshot adds to its step. */
+static int hq_snapshot_launch(hq_ctx* c, hq_ctx::hq_snapshot& sn)
+{
+    const int32_t slot = hq_step_ring_push(&sn.ring, c->step);
+    if (slot < 0) return hq_fail(HQ_ERR_STATE, "a snapshot's slots are all pending%s", "");   /* (hq_output_check_room saw to it) */
+    char* d = sn.d_stage + (size_t)slot * sn.slot_bytes;
+    constexpr int32_t tile_rows = 256 * (16 / (int32_t)sizeof(hq_real));
+    const int64_t ntiles = ((int64_t)sn.count + tile_rows - 1) / tile_rows;
+    hq_k_snapshot<hq_real><<<(unsigned)std::min<int64_t>(ntiles, 8192), 256, 0, c->stream>>>(
+        sn.first, sn.count, sn.d_map, c->d_u[c->now], c->d_u[c->prev], c->dt,
+        (sn.fields & HQ_SNAP_TM1) ? (hq_real*)(d + sn.off[0]) : nullptr,
+        (sn.fields & HQ_SNAP_TM2) ? (hq_real*)(d + sn.off[1]) : nullptr,
+        (sn.fields & HQ_SNAP_VEL) ? (double*)(d + sn.off[2]) : nullptr);
+    HQ_HIP(hipEventRecord(c->ev_output, c->stream));
+    HQ_HIP(hipStreamWaitEvent(c->sstream, c->ev_output, 0));    /* (the record just made, whatever ev_output names later) */
+    HQ_HIP(hipMemcpyAsync(sn.h_stage + (size_t)slot * sn.slot_bytes, d, sn.slot_bytes, hipMemcpyDeviceToHost, c->sstream));
+    HQ_HIP(hipEventRecord(sn.done[(size_t)slot], c->sstream));
+    c->d2h_bytes += (int64_t)sn.slot_bytes;
+    return HQ_OK;
+}
+
+/* The head of a step: every due output in solver_run's order (psolve.c:4277-4280: checkpoint / wavefield, then planes /
+ * stations), then the trackers.  The launches that the step's other streams must stay behind (every snapshot, every recorder,
+ * a tracker of accelerations: the comments above tell why) go first; ONE record of ev_output behind the last of them -- a
+ * snapshot's own serves if nothing followed it -- holds the bricks' stream and the exchange chain's, on the patch variant,
+ * where there is such a stream.  The trackers that need no hold follow that record: the streams never wait for them. */
+static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
+{
+    const bool hold_b = brick_stream && c->bstream, hold_c = c->overlap && c->cstream;   /* the streams there are to hold */
+    bool hold = false, recorded = false;         /* recorded: ev_output's record is behind the last launch so far */
+    for (auto& sn : c->snaps)
+        if (hq_cadence_due(sn.due, c->step)) { HQ_TRY(hq_snapshot_launch(c, sn)); hold = recorded = true; }
+    for (auto& r : c->recs)
+        if (hq_cadence_due(r.due, c->step)) { HQ_TRY(hq_record_launch(c, r)); if (r.pts.np > 0) { hold = true; recorded = false; } }
+    for (auto& t : c->peaks)                     /* the trackers that read u(t - 2 dt) */
+        if ((t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) { hq_peak_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
+    if (hold && c->variant == HQ_VARIANT_PATCH && (hold_b || hold_c)) {
+        if (!recorded) HQ_HIP(hipEventRecord(c->ev_output, c->stream));
+        if (hold_b) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_output, 0));
+        if (hold_c) HQ_HIP(hipStreamWaitEvent(c->cstream, c->ev_output, 0));
+    }
+    for (auto& t : c->peaks)                     /* the other trackers: no stream waits for them */
+        if (!(t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) hq_peak_launch(c, t);
+    return HQ_OK;
+}
+
+/* free every output of one kind (the caller has waited for every stream that serves them) */
+template <typename T>
+static void hq_outputs_drop(hq_ctx* c, std::vector<T>& outs)
+{
+    for (auto& o : outs) { hq_output_free(o); c->bytes -= o.bytes; }
+    outs.clear();
+}
+
+/* hq_record_clear, hq_peak_clear: every output of one kind goes, behind the steps enqueued so far */
+template <typename T>
+static int hq_outputs_clear(hq_ctx* c, std::vector<T> hq_ctx::*outs)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if ((c->*outs).empty()) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    hq_outputs_drop(c, c->*outs);
+    return HQ_OK;
+}
+
+/* ---- sample recorders: entry points (include/hq_solver.h) ---- */
+
+extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (d->npoints < 0 || d->rate <= 0 || d->capacity <= 0 || d->derivs < 0 || d->derivs > 2 ||
+        (d->npoints > 0 && (!d->ids || !d->phi)))
+        return hq_fail(HQ_ERR_ARG, "bad recorder description%s", "");
+    if (d->derivs == 2 && c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    hq_ctx::hq_recorder r;
+    r.derivs = d->derivs;
+    const int64_t bytes0 = c->bytes;
+    HQ_TRY(hq_points_build(c, d->npoints, 8, d->ids, d->phi, &r.pts, "hq_record_add"));
+    const int rc = hq_dev_alloc(c, &r.d_ring, (size_t)d->capacity * (size_t)d->npoints * 3 * (size_t)(1 + d->derivs));
+    if (rc != HQ_OK) { hq_output_free(r); c->bytes = bytes0; return rc; }
+    r.bytes = c->bytes - bytes0;
+    c->h2d_bytes += r.pts.h2d();
+    r.open(d->rate, INT32_MIN, d->capacity);                     /* every multiple of the rate, wherever `step` is set to */
+    r.id = c->rec_next_id++;
+    *handle = r.id;
+    c->recs.push_back(std::move(r));
+    return HQ_OK;
+}
+
+extern "C" int hq_record_pending(hq_ctx* c, int32_t handle, int32_t* nsamples, int32_t* first_step)
+{
+    if (!c || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const hq_ctx::hq_recorder* r = hq_output_find(c->recs, handle);
+    if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
+    *nsamples = r->ring.count;
+    if (first_step) *first_step = hq_step_ring_first_step(&r->ring);
+    return HQ_OK;
+}
+
+extern "C" int hq_record_fetch(hq_ctx* c, int32_t handle, int32_t max_samples, double* out, int32_t* steps,
+                               int32_t* nfetched)
+{
+    if (!c || !out || !steps || !nfetched || max_samples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
+    hq_ctx::hq_recorder* r = hq_output_find(c->recs, handle);
+    if (!r) return hq_fail(HQ_ERR_ARG, "unknown recorder handle%s", "");
+    *nfetched = 0;
+    const int32_t n = std::min(max_samples, r->ring.count), head = r->ring.head;
+    if (n == 0) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t row = (size_t)r->pts.np * 3 * (size_t)(1 + r->derivs);          /* doubles per sample */
+    const int32_t first = std::min(n, r->ring.capacity - head);              /* up to the ring's end, then from its start */
+    if (row > 0) {
+        HQ_HIP(hipMemcpy(out, r->d_ring + (size_t)head * row, sizeof(double) * row * (size_t)first, hipMemcpyDeviceToHost));
+        if (n > first)
+            HQ_HIP(hipMemcpy(out + (size_t)first * row, r->d_ring, sizeof(double) * row * (size_t)(n - first), hipMemcpyDeviceToHost));
+    }
+    for (int32_t k = 0; k < n; k++) steps[k] = r->steps[(size_t)hq_step_ring_slot_at(&r->ring, k)];
+    c->d2h_bytes += 8 * (int64_t)row * n;
+    hq_step_ring_pop(&r->ring, n);
+    *nfetched = n;
+    return HQ_OK;
+}
+
+extern "C" int hq_record_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::recs); }
+
+/* ---- peak-motion trackers: entry points (include/hq_solver.h) ---- */
+
+extern "C" int hq_peak_add(hq_ctx* c, const hq_peak_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const int32_t all = HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC;
+    const int32_t K = d->nodes_per_point;
+    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->quantities == 0 || (d->quantities & ~all) != 0 ||
+        (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
+        return hq_fail(HQ_ERR_ARG, "bad peak tracker description%s", "");
+    if ((d->quantities & HQ_PEAK_ACC) && c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    hq_ctx::hq_peak_tracker t;
+    t.quantities = d->quantities; t.nq = hq_peak_nq(d->quantities); t.due = { d->rate, d->first_step };
+    const size_t n = (size_t)t.nq * (size_t)d->npoints;
+    const int64_t bytes0 = c->bytes;
+    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts, "hq_peak_add"));
+    int rc = hq_dev_alloc(c, &t.d_pk, HQ_PEAK_NVAL * n);
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_when, HQ_PEAK_NWHEN * n);
+    hipError_t e = rc == HQ_OK ? hq_peak_zero(c, t) : hipSuccess;
+    if (rc == HQ_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);   /* (the state is in place) */
+    if (rc != HQ_OK || e != hipSuccess) {
+        hq_output_free(t);
+        c->bytes = bytes0;
+        (void)hipGetLastError();
+        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_peak_add failed: %s", hipGetErrorString(e));
+    }
+    t.bytes = c->bytes - bytes0;
+    c->h2d_bytes += t.pts.h2d();
+    t.id = c->peak_next_id++;
+    *handle = t.id;
+    c->peaks.push_back(std::move(t));
+    return HQ_OK;
+}
+
+/* the state between the device's tables ([nr][np], nr = nq x 5 or nq x 2 rows) and the caller's ([np][nr]), either way */
+template <typename T>
+static void hq_peak_transpose(size_t np, size_t nr, bool to_caller, const T* src, T* dst)
+{
+    for (size_t p = 0, ic = 0; p < np; p++)
+        for (size_t r = 0; r < nr; r++, ic++)
+            if (to_caller) dst[ic] = src[r * np + p]; else dst[r * np + p] = src[ic];
+}
+
+/* the state crosses PCIe as the device keeps it ([nq][5][np], [nq][2][np]); the caller's arrays are [np][nq][5], [np][nq][2] */
+extern "C" int hq_peak_fetch(hq_ctx* c, int32_t handle, double* peaks, int32_t* when, int64_t* nsamples)
+{
+    if (!c || !peaks || !when || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_peak_tracker* t = hq_output_find(c->peaks, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq;
+    *nsamples = t->nsamples;
+    if (n == 0) return HQ_OK;
+    std::vector<double> pk(HQ_PEAK_NVAL * n);
+    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
+    HQ_HIP(hipMemcpyAsync(pk.data(), t->d_pk, sizeof(double) * pk.size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_HIP(hipMemcpyAsync(wh.data(), t->d_when, sizeof(int32_t) * wh.size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    hq_peak_transpose(np, nq * HQ_PEAK_NVAL, true, pk.data(), peaks);
+    hq_peak_transpose(np, nq * HQ_PEAK_NWHEN, true, wh.data(), when);
+    c->d2h_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_peak_load(hq_ctx* c, int32_t handle, const double* peaks, const int32_t* when, int64_t nsamples)
+{
+    if (!c || !peaks || !when || nsamples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
+    hq_ctx::hq_peak_tracker* t = hq_output_find(c->peaks, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq;
+    t->nsamples = nsamples;
+    if (n == 0) return HQ_OK;
+    std::vector<double> pk(HQ_PEAK_NVAL * n);
+    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
+    hq_peak_transpose(np, nq * HQ_PEAK_NVAL, false, peaks, pk.data());
+    hq_peak_transpose(np, nq * HQ_PEAK_NWHEN, false, when, wh.data());
+    HQ_HIP(hipMemcpyAsync(t->d_pk, pk.data(), sizeof(double) * pk.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipMemcpyAsync(t->d_when, wh.data(), sizeof(int32_t) * wh.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    c->h2d_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_peak_reset(hq_ctx* c, int32_t handle)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_peak_tracker* t = hq_output_find(c->peaks, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    HQ_HIP(hq_peak_zero(c, *t));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    t->nsamples = 0;
+    return HQ_OK;
+}
+
+extern "C" int hq_peak_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::peaks); }
+
+/* ---- field snapshots: entry points (include/hq_solver.h) ---- */
+
+extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const int32_t all = HQ_SNAP_TM1 | HQ_SNAP_TM2 | HQ_SNAP_VEL;
+    if (d->count < 1 || d->first < 0 || (int64_t)d->first + d->count > c->N || d->rate < 1 || d->slots < 1 ||
+        d->fields == 0 || (d->fields & ~all) != 0)
+        return hq_fail(HQ_ERR_ARG, "bad snapshot description%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    hq_ctx::hq_snapshot sn;
+    sn.first = d->first; sn.count = d->count; sn.fields = d->fields;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t n3 = 3 * (size_t)d->count;
+    size_t at = 0;
+    sn.off[0] = at; if (d->fields & HQ_SNAP_TM1) at += pad(sizeof(hq_real) * n3);
+    sn.off[1] = at; if (d->fields & HQ_SNAP_TM2) at += pad(sizeof(hq_real) * n3);
+    sn.off[2] = at; if (d->fields & HQ_SNAP_VEL) at += pad(sizeof(double) * n3);
+    sn.slot_bytes = at;
+    const int64_t bytes0 = c->bytes;
+    const bool had_stream = c->sstream != nullptr;
+    int rc = hq_dev_alloc(c, &sn.d_stage, sn.slot_bytes * (size_t)d->slots);
+    if (rc == HQ_OK && !c->perm.empty()) rc = hq_dev_alloc(c, &sn.d_map, (size_t)d->count);
+    if (rc == HQ_OK && hipHostMalloc((void**)&sn.h_stage, sn.slot_bytes * (size_t)d->slots, hipHostMallocDefault) != hipSuccess) {
+        sn.h_stage = nullptr;
+        rc = hq_fail(HQ_ERR_NOMEM, "hipHostMalloc failed for the snapshot's pinned buffers%s", "");
+    }
+    hipError_t e = hipSuccess;
+    if (rc == HQ_OK && !c->sstream) e = hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking);
+    sn.done.assign((size_t)d->slots, nullptr);
+    for (int32_t k = 0; k < d->slots && rc == HQ_OK && e == hipSuccess; k++)
+        e = hipEventCreateWithFlags(&sn.done[(size_t)k], hipEventDisableTiming);
+    if (rc == HQ_OK && e == hipSuccess && sn.d_map) {            /* perm[first .. first + count): the caller's id -> the device's */
+        e = hipMemcpy(sn.d_map, c->perm.data() + d->first, sizeof(int32_t) * (size_t)d->count, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  /* the steps read the map on other streams */
+    }
+    if (rc != HQ_OK || e != hipSuccess) {
+        hq_output_free(sn);
+        if (!had_stream && c->sstream) { hipStreamDestroy(c->sstream); c->sstream = nullptr; }
+        c->bytes = bytes0;
+        (void)hipGetLastError();
+        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_snapshot_add failed: %s", hipGetErrorString(e));
+    }
+    sn.bytes = c->bytes - bytes0;
+    if (sn.d_map) c->h2d_bytes += 4 * (int64_t)d->count;
+    sn.open(d->rate, d->first_step, d->slots);
+    sn.id = c->snap_next_id++;
+    *handle = sn.id;
+    c->snaps.push_back(std::move(sn));
+    return HQ_OK;
+}
+
+extern "C" int hq_snapshot_pending(hq_ctx* c, int32_t handle, int32_t* npending, int32_t* nready, int32_t* first_step)
+{
+    if (!c || !npending) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const hq_ctx::hq_snapshot* sn = hq_output_find(c->snaps, handle);
+    if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
+    *npending = sn->ring.count;
+    if (nready) {
+        int32_t n = 0;
+        for (int32_t k = 0; k < sn->ring.count; k++)
+            n += hipEventQuery(sn->done[(size_t)hq_step_ring_slot_at(&sn->ring, k)]) == hipSuccess;
+        (void)hipGetLastError();                                 /* (hipErrorNotReady is an answer, not an error) */
+        *nready = n;
+    }
+    if (first_step) *first_step = hq_step_ring_first_step(&sn->ring);
+    return HQ_OK;
+}
+
+/* `bytes` from the pinned mirror into the caller's array; the large ones on all host threads (one thread moves ~10 GB/s) */
+static void hq_host_copy(void* dst, const void* src, size_t bytes)
+{
+    const size_t chunk = (size_t)4 << 20;
+    const int64_t nchunks = (int64_t)((bytes + chunk - 1) / chunk);
+#pragma omp parallel for schedule(static) if (nchunks > 4)
+    for (int64_t k = 0; k < nchunks; k++) {
+        const size_t at = (size_t)k * chunk;
+        memcpy((char*)dst + at, (const char*)src + at, std::min(chunk, bytes - at));
+    }
+}
+
+extern "C" int hq_snapshot_fetch(hq_ctx* c, int32_t handle, hq_real* tm1, hq_real* tm2, double* vel, int32_t* step)
+{
+    if (!c || !step) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_snapshot* sn = hq_output_find(c->snaps, handle);
+    if (!sn) return hq_fail(HQ_ERR_ARG, "unknown snapshot handle%s", "");
+    if ((tm1 && !(sn->fields & HQ_SNAP_TM1)) || (tm2 && !(sn->fields & HQ_SNAP_TM2)) || (vel && !(sn->fields & HQ_SNAP_VEL)))
+        return hq_fail(HQ_ERR_ARG, "the snapshot does not hold a field that an output pointer was given for%s", "");
+    *step = -1;
+    if (sn->ring.count == 0) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hipEventSynchronize(sn->done[(size_t)sn->ring.head]));   /* this slot's copy -- not the steps enqueued behind it */
+    const char* h = sn->h_stage + (size_t)sn->ring.head * sn->slot_bytes;
+    const size_t n3 = 3 * (size_t)sn->count;
+    if (tm1) hq_host_copy(tm1, h + sn->off[0], sizeof(hq_real) * n3);
+    if (tm2) hq_host_copy(tm2, h + sn->off[1], sizeof(hq_real) * n3);
+    if (vel) hq_host_copy(vel, h + sn->off[2], sizeof(double) * n3);
+    *step = hq_step_ring_first_step(&sn->ring);
+    hq_step_ring_pop(&sn->ring, 1);
+    return HQ_OK;
+}
+
+extern "C" int hq_snapshot_clear(hq_ctx* c)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (c->snaps.empty()) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    HQ_HIP(hipStreamSynchronize(c->sstream));
+    hq_outputs_drop(c, c->snaps);
+    hipStreamDestroy(c->sstream); c->sstream = nullptr;   /* (the copy stream goes with the snapshots: here and in hq_destroy) */
+    return HQ_OK;
+}
+
+#endif

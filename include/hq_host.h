@@ -290,7 +290,8 @@ HQ_API int hqh_station_format_derivs(char* buf, int32_t cap, double time, const 
 /* The first line of a station file (psolve.c:6636-6648; no newline: every data line starts with one). */
 HQ_API int hqh_station_header(char* buf, int32_t cap, int32_t derivs);
 /* Displacement, velocity, acceleration of one station from the 8 node rows of tm1, tm2, tm3 (each
- * [8][3]; tm2 / tm3 may be NULL below derivs 1 / 2), in the reference's order of operations. */
+ * [8][3]; tm2 / tm3 may be NULL below derivs 1 / 2), in the reference's order of operations
+ * (csrc/hq_sample.h, the text the device's recorders and trackers compile). */
 HQ_API int hqh_station_kinematics(const double* phi, const double* tm1, const double* tm2, const double* tm3,
                                   double dt, int32_t derivs, double* vals);
 /* The peak-motion fold on the host (csrc/hq_peak.h, the text hq_k_peak compiles): recorder samples folded into the state

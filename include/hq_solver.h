@@ -424,7 +424,7 @@ HQ_API int hq_upload(hq_ctx* ctx, const hq_real* tm1, const hq_real* tm2, int32_
  * of that step's kernels, on exactly the state hq_gather3 documents -- one launch of hq_k_record appends one sample to
  * a ring in device memory:  out[sample][point][3 (1 + derivs)], always double, in both libraries (the f32 library
  * widens each state value first): displacement; with derivs >= 1 the velocity (u1 - u2) / dt; with derivs == 2 the
- * acceleration (u1 - 2 u2 + u3) / dt^2 -- summed in hqh_station_kinematics' order of operations without contraction, so
+ * acceleration (u1 - 2 u2 + u3) / dt^2 -- summed by csrc/hq_sample.h, the text hqh_station_kinematics compiles, so
  * the numbers equal the host route's bit for bit.  Step 0 records the initial state; the state after the last step is
  * not sampled until a further step begins.
  * The ring is accounted on the host: which steps are due follows from the step counter alone.  hq_run, hq_group_run
@@ -500,7 +500,7 @@ HQ_API int hq_snapshot_clear(hq_ctx* ctx);
  * recorder's; with nodes_per_point = 1 single nodes (a surface map), with no weights at all.  At the head of every step
  * s >= first_step with s % rate == 0 -- where hq_k_record sits, before any of that step's kernels, on exactly the state
  * hq_gather3 documents -- one launch of hq_k_peak forms the sample hq_k_record would take at the point (every value
- * widened to double first, hqh_station_kinematics' order of operations, no contraction: the recorder's sample bit for
+ * widened to double first, csrc/hq_sample.h's order of operations, no contraction: the recorder's sample bit for
  * bit) and folds it into the point's state.  Per point and quantity q of the mask, in the order displacement, velocity
  * (u1 - u2) / dt, acceleration (u1 - 2 u2 + u3) / dt^2, that state is (csrc/hq_peak.h):
  *   peaks[p][q][0..2] = max |v_x|, |v_y|, |v_z|

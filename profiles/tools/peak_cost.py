@@ -9,7 +9,7 @@ The configurations take turns, run by run, so that drift of the box's clocks or 
 Every run starts from the same state (hq_upload of a seeded field, step 0) with the same source; the time is a host clock
 around hq_run + hq_sync of K steps after a warm-up of W.  Prints one line per run, then per configuration the median and
 what it adds to the no-tracker median per step and per DUE step, beside the bytes per point and due step the model of
-hq_k_peak predicts (hq_engine.hip): 4 of id + 24 per field read (12 in the f32 library) + 40 per quantity of peaks read; the
+hq_k_peak predicts (hq_outputs.h): 4 of id + 24 per field read (12 in the f32 library) + 40 per quantity of peaks read; the
 stores come on top only where a peak is raised.  The tracker's state is fetched at the end of every run, so the map is real.
 Under `rocprofv3 --kernel-trace --stats -- python profiles/tools/peak_cost.py --runs 1` the kernel statistics give hq_k_peak's
 own time."""

@@ -25,7 +25,7 @@ def _kernel_notes(tmp_path):
     kernels = {}
     for block in txt.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        kernels[name] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|"
+        kernels[name] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|"
                                                           r"private_segment_fixed_size|group_segment_fixed_size):\s+(\d+)", block)}
     return kernels
 

@@ -254,6 +254,65 @@ def test_samples_are_taken_before_the_bricks_overwrite_the_oldest_field(big_box,
         assert H.rel_linf(vals[:, :, 3 * k:3 * k + 3], gvals[:, :, 3 * k:3 * k + 3]) < TOL
 
 
+@pytest.mark.parametrize("brick_stream", [1, 0])
+def test_all_three_kinds_due_on_one_step_share_one_hold(big_box, brick_mode, brick_stream):
+    """Recorders, trackers and a snapshot on ONE solver beside the bricks' stream, 40 steps in ONE hq_run: every step has a
+    recorder with accelerations, the unit-weight rows recorder, a K = 8 tracker of all three quantities and a K = 1 velocity
+    tracker (which holds nothing back) due, every fourth a snapshot of tm1 | tm2 | vel over all nodes as well -- the head
+    of such a step holds the other streams once, behind the last launch that reads what they overwrite.  All comparisons
+    are made on this one trajectory (module docstring), bit for bit."""
+    b = big_box
+    ids, phi, dt = b["ids"], b["phi"], b["dt"]
+    flat = np.asarray(ids).reshape(-1)
+    ALL = capi.HQ_PEAK_DISP | capi.HQ_PEAK_VEL | capi.HQ_PEAK_ACC
+    s = b["box"].create_solver(tm1=b["u1"], tm2=b["u2"], options={"brick_stream": brick_stream})
+    s.set_source(b["loaded"], b["F"])
+    h = s.record_add(ids, phi, rate=1, derivs=2, capacity=40)
+    hr = _add_rows_recorder(s, ids, 40)
+    hp8 = s.peak_add(ids, phi, rate=1, quantities=ALL)
+    hp1 = s.peak_add(np.ascontiguousarray(ids[:, 0]), None, rate=1, quantities=capi.HQ_PEAK_VEL)
+    hs = s.snapshot_add(rate=4, fields=capi.HQ_SNAP_TM1 | capi.HQ_SNAP_TM2 | capi.HQ_SNAP_VEL, slots=10)
+    s.run(40)
+    assert s.record_pending(h) == (40, 0) and s.record_pending(hr) == (40, 0)
+    npending, _, first = s.snapshot_pending(hs)
+    assert (npending, first) == (10, 0)
+    steps, vals = s.record_fetch(h)
+    rsteps, rows = s.record_fetch(hr)
+    pk8, when8, n8 = s.peak_fetch(hp8)
+    pk1, when1, n1 = s.peak_fetch(hp1)
+    snaps = [s.snapshot_fetch(hs) for _ in range(10)]
+    assert s.record_pending(h) == (0, -1) and s.snapshot_pending(hs)[0] == 0 and s.snapshot_fetch(hs)[0] == -1
+    info = s.info()
+    if brick_mode == "bricks":
+        assert info["brick_units"] > 0 and info["brick_stream"] == brick_stream
+    else:
+        assert info["brick_units"] == 0
+    tm2, tm3 = _start_rows(s, ids, b["u2"])
+    s.close()
+    assert np.array_equal(steps, np.arange(40)) and np.array_equal(rsteps, steps)
+    assert [sn[0] for sn in snaps] == list(range(0, 40, 4))
+    # the recorder: the host route on the rows of the same batch
+    rvals = _route_from_rows(rows, tm2, tm3, 0, steps, phi, dt, 2)
+    assert vals.shape == (40, 64, 9) and np.abs(rvals[:, :, 6:]).max() > 0
+    assert np.array_equal(vals, rvals)
+    # the K = 8 tracker: the fold of the recorder's samples
+    want8 = host.peak_fold(steps, vals, ALL)
+    assert n8 == 40 and pk8.shape == (64, 3, 5) and (pk8[:, :, 4] > 0).all()
+    assert np.array_equal(pk8, want8[0]) and np.array_equal(when8, want8[1])
+    # the K = 1 tracker: the fold of (0 + u1, (0 + u1 - u2) / dt) at the stations' first nodes, from the rows recorder
+    u1 = np.asarray(rows, np.float64)[:, 0::8, :]
+    u2 = np.concatenate([tm2[None, 0::8, :], u1[:-1]])
+    d = 0.0 + u1
+    want1 = host.peak_fold(steps, np.ascontiguousarray(np.concatenate([d, (d - u2) / dt], axis=2)), capi.HQ_PEAK_VEL)
+    assert n1 == 40 and pk1.shape == (64, 1, 5) and (pk1[:, 0, 4] > 0).all()
+    assert np.array_equal(pk1, want1[0]) and np.array_equal(when1, want1[1])
+    # the snapshots: u(t) and u(t - dt) at the stations' nodes are the rows of that step and of the step before
+    for step, s1, s2, sv in snaps:
+        assert np.array_equal(np.asarray(s1, np.float64)[flat], rows[step])
+        assert np.array_equal(np.asarray(s2, np.float64)[flat], rows[step - 1] if step else tm2)
+        assert sv.shape == s1.shape and np.abs(sv).max() > 0
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. two partitions in one process
 # ---------------------------------------------------------------------------------------------------------------------
