@@ -23,9 +23,11 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_comm_ipc_export", "hq_comm_init_ipc", "hq_comm_init_loopback",
            "hq_record_add", "hq_record_pending", "hq_record_fetch", "hq_record_clear",
            "hq_snapshot_add", "hq_snapshot_pending", "hq_snapshot_fetch", "hq_snapshot_clear",
-           "hq_peak_add", "hq_peak_fetch", "hq_peak_load", "hq_peak_reset", "hq_peak_clear"]
+           "hq_peak_add", "hq_peak_fetch", "hq_peak_load", "hq_peak_reset", "hq_peak_clear",
+           "hq_spec_add", "hq_spec_coefficients", "hq_spec_fetch", "hq_spec_load", "hq_spec_reset", "hq_spec_clear"]
 HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
 HQ_PEAK_DISP, HQ_PEAK_VEL, HQ_PEAK_ACC = 1, 2, 4
+HQ_SPEC_MAX_PERIODS, HQ_SPEC_NVAL = 32, 4
 
 
 class HqError(RuntimeError):
@@ -76,6 +78,13 @@ class _PeakDesc(ctypes.Structure):
     _fields_ = [("npoints", ctypes.c_int32), ("nodes_per_point", ctypes.c_int32), ("ids", ctypes.c_void_p),
                 ("phi", ctypes.c_void_p), ("rate", ctypes.c_int32), ("first_step", ctypes.c_int32),
                 ("quantities", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class _SpecDesc(ctypes.Structure):
+    _fields_ = [("npoints", ctypes.c_int32), ("nodes_per_point", ctypes.c_int32), ("ids", ctypes.c_void_p),
+                ("phi", ctypes.c_void_p), ("rate", ctypes.c_int32), ("first_step", ctypes.c_int32),
+                ("nperiods", ctypes.c_int32), ("reserved", ctypes.c_int32), ("periods", ctypes.c_void_p),
+                ("damping", ctypes.c_double)]
 
 
 class _Info(ctypes.Structure):
@@ -508,6 +517,80 @@ class Solver:
         """hq_peak_clear: drop every tracker of the context and its device memory."""
         _check(self._lib.hq_peak_clear(self._h), self._lib)
         self._peaks = {}
+
+    def spec_add(self, ids, phi=None, rate=1, first_step=0, periods=(1.0,), damping=0.05):
+        """hq_spec_add: a response-spectrum tracker.  Points as peak_add's (phi None: single nodes).  At the head of every
+        step s >= first_step with s % rate == 0 the point's acceleration sample drives one damped oscillator per period
+        (seconds) and axis, step h = rate dt; the maxima of |x| are SD -- PSV = omega SD, PSA = omega^2 SD are the
+        caller's.  Returns its handle."""
+        if phi is None:
+            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32)
+            k = 1
+        else:
+            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
+            phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
+            if len(ids) != len(phi):
+                raise HqError("spec_add: %d rows of ids, %d of phi" % (len(ids), len(phi)))
+            k = 8
+        periods = np.ascontiguousarray(np.asarray(periods, np.float64).reshape(-1))
+        d = _SpecDesc(len(ids), k, ids.ctypes.data, None if phi is None else phi.ctypes.data, int(rate), int(first_step),
+                      len(periods), 0, periods.ctypes.data if len(periods) else None, float(damping))
+        h = ctypes.c_int32(-1)
+        _check(self._lib.hq_spec_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
+        if not hasattr(self, "_specs"):
+            self._specs = {}
+        self._specs[h.value] = (len(ids), len(periods))
+        return h.value
+
+    def _spec_shape(self, handle):
+        if handle not in getattr(self, "_specs", {}):
+            raise HqError("unknown spectrum tracker handle %r" % (handle,))
+        return self._specs[handle]
+
+    def spec_coefficients(self, handle):
+        """hq_spec_coefficients: [nperiods, 8] = A11, A12, A21, A22, B11, B12, B21, B22 per period, as the kernel reads them."""
+        _, nper = self._spec_shape(handle)
+        coef = np.zeros((nper, 8))
+        _check(self._lib.hq_spec_coefficients(self._h, ctypes.c_int32(handle), _ptr(coef)), self._lib)
+        return coef
+
+    def spec_fetch(self, handle, osc=True, aprev=True):
+        """hq_spec_fetch: (sd [npoints, nperiods, 4], osc [npoints, nperiods, 2, 3] or None, aprev [npoints, 3] or None,
+        nsamples) -- per period max |x| per axis and the horizontal resultant SQUARED; the oscillators (x then v) and the
+        last sample as they stand.  Waits for the enqueued steps; the state stays on the device."""
+        npoints, nper = self._spec_shape(handle)
+        sd = np.zeros((npoints, nper, 4))
+        o = np.zeros((npoints, nper, 2, 3)) if osc else None
+        a = np.zeros((npoints, 3)) if aprev else None
+        n = ctypes.c_int64()
+        pad = np.zeros(1)                                       # (an empty array has no address worth passing)
+        arg = lambda x: None if x is None else _ptr(x if x.size else pad)
+        _check(self._lib.hq_spec_fetch(self._h, ctypes.c_int32(handle), arg(sd), arg(o), arg(a), ctypes.byref(n)), self._lib)
+        return sd, o, a, int(n.value)
+
+    def spec_load(self, handle, sd, osc, aprev, nsamples):
+        """hq_spec_load: put back what spec_fetch returned (a run that restarts from a checkpoint)."""
+        npoints, nper = self._spec_shape(handle)
+        if sd is None or osc is None or aprev is None:
+            raise HqError("spec_load: sd, osc and aprev are all required")
+        sd = np.ascontiguousarray(sd, np.float64)
+        osc = np.ascontiguousarray(osc, np.float64)
+        aprev = np.ascontiguousarray(aprev, np.float64)
+        if sd.shape != (npoints, nper, 4) or osc.shape != (npoints, nper, 2, 3) or aprev.shape != (npoints, 3):
+            raise HqError("spec_load: the arrays are not those of spec_fetch")
+        pad = np.zeros(1)
+        _check(self._lib.hq_spec_load(self._h, ctypes.c_int32(handle), _ptr(sd if sd.size else pad),
+                                      _ptr(osc if osc.size else pad), _ptr(aprev if aprev.size else pad),
+                                      ctypes.c_int64(int(nsamples))), self._lib)
+
+    def spec_reset(self, handle):
+        """hq_spec_reset: the oscillators at rest, sd 0, the previous sample 0, nsamples 0."""
+        _check(self._lib.hq_spec_reset(self._h, ctypes.c_int32(handle)), self._lib)
+
+    def spec_clear(self):
+        """hq_spec_clear: drop every spectrum tracker of the context and its device memory."""
+        _check(self._lib.hq_spec_clear(self._h), self._lib)
+        self._specs = {}
 
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)

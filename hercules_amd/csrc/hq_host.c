@@ -35,6 +35,7 @@
 #include "hq_host.h"
 #include "hq_cadence.h"
 #include "hq_peak.h"
+#include "hq_sdof.h"
 #include "hq_sample.h"
 
 #define HQH_PI 3.14159265358979323846
@@ -1440,6 +1441,32 @@ int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const i
                 hq_peak_fold(v[3 * q], v[3 * q + 1], v[3 * q + 2], steps[k], pk, 1, w, 1);
                 pk += HQ_PEAK_NVAL; w += HQ_PEAK_NWHEN;
             }
+        }
+    return HQ_OK;
+}
+
+int hqh_sdof_coef(double period, double damping, double h, double* c)
+{
+    if (!c || !(period > 0.0) || !(h > 0.0) || !(damping >= 0.0 && damping < 1.0) || period - period != 0.0 || h - h != 0.0)
+        return HQ_ERR_ARG;
+    hq_sdof_coef(period, damping, h, c);
+    return HQ_OK;
+}
+
+int hqh_spec_fold(int32_t npoints, int32_t nperiods, const double* coef, int32_t nsamples, const double* acc,
+                  int64_t acc_stride, double* sd, double* osc, double* aprev)
+{
+    if (npoints < 0 || nperiods < 0 || nsamples < 0 || acc_stride < 3) return HQ_ERR_ARG;
+    if (npoints == 0 || nsamples == 0) return HQ_OK;
+    if (!acc || !aprev || (nperiods > 0 && (!coef || !sd || !osc))) return HQ_ERR_ARG;
+    for (int32_t k = 0; k < nsamples; k++)
+        for (int32_t p = 0; p < npoints; p++) {
+            const double* a1 = acc + ((int64_t)k * npoints + p) * acc_stride;
+            double* a0 = aprev + 3 * (int64_t)p;
+            for (int32_t j = 0; j < nperiods; j++)
+                hq_spec_fold(coef + (int64_t)HQ_SDOF_NCOEF * j, a0, a1, osc + ((int64_t)p * nperiods + j) * HQ_SPEC_NOSC, 1,
+                             sd + ((int64_t)p * nperiods + j) * HQ_SPEC_NSD, 1);
+            for (int a = 0; a < 3; a++) a0[a] = a1[a];
         }
     return HQ_OK;
 }

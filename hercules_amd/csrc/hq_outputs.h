@@ -1,7 +1,7 @@
 /*
- * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion trackers, field
- * snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at the head of a step and the hq_record_*
- * / hq_peak_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
+ * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion and response-spectrum
+ * trackers, field snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at the head of a step and
+ * the hq_record_* / hq_peak_* / hq_spec_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
  */
 #ifndef HQ_OUTPUTS_H
 #define HQ_OUTPUTS_H
@@ -96,6 +96,89 @@ hq_k_peak(int32_t np, const int32_t* __restrict__ ids, const double* __restrict_
         hq_sample_acc(K, w, row, u2, u3, d);
         hq_peak_fold(d[0] / dt2, d[1] / dt2, d[2] / dt2, step, s, np, sw, np);
     }
+}
+
+/*
+ * One due step of a response-spectrum tracker (hq_spec_add): the acceleration sample hq_k_record takes at the point with
+ * derivs = 2 -- hq_sample.h's three stages on u1, u2, u3, every value widened to double first, d / dt2: the recorder's
+ * acceleration column bit for bit -- drives, per period, the three oscillators of hq_sdof.h one exact step from the
+ * point's previous sample `aprev`, and their |x| is folded into the running maxima (hq_spec_fold, the text hqh_spec_fold
+ * compiles).  One lane per point, no atomics, no LDS: a point belongs to one lane, the launches of one stream are ordered.
+ * K as in hq_k_peak: 8 nodes and weights per point, or the point is a node.
+ * State, all double in both libraries, consecutive lanes on consecutive addresses so that a wave reads whole lines:
+ *   aprev [3][np]            the sample of the last due step (0 before the first)
+ *   osc   [nper][2][3][np]   x then v
+ *   sd    [nper][4][np]      max |x_x|, |x_y|, |x_z|, max (x_x^2 + x_y^2)
+ * coef [nper][8] is read with a wave-uniform index: scalar loads, no VGPRs.  The periods are independent chains: period
+ * j + 1's ten state values are loaded into registers BEFORE period j's are computed on and stored (the loop is unrolled by
+ * two, so the two register sets swap roles without copies), which keeps a period's loads in flight behind the arithmetic
+ * of the one before; the fold runs on the register copy (stride 1) and a lane stores x and v always, sd only where raised.
+ * The prefetch is unconditional -- behind the last period it re-reads that period's own rows, out of L2 -- because a
+ * conditional one ends in register copies that wait for the loads just issued; a scheduling barrier keeps it where it is.
+ * Bytes per point and due step, K = 1, f64 (a model, not a measurement): 4 of id + 72 of state gathers (36 in the f32
+ * library) + 24 read and 24 written of aprev; per period 80 read (x, v, sd) and 48 written, plus the raised sd.  8 periods:
+ * 124 + 8 x 128 = 1148.
+ */
+template <int K>
+__global__ void __launch_bounds__(256)
+hq_k_spec(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
+          const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
+          double dt2, int32_t nper, const double* __restrict__ coef, double* __restrict__ aprev, double* __restrict__ osc,
+          double* __restrict__ sd)
+{
+#pragma clang fp contract(off)
+    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= np) return;
+    int64_t row[K];
+    double wk[K];
+#pragma unroll
+    for (int c = 0; c < K; c++) {
+        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
+        if (K > 1) wk[c] = phi[(int64_t)c * np + p];
+    }
+    const double* w = K > 1 ? wk : nullptr;                      /* (a node: weight 1, hq_sample.h) */
+    double a0[3], a1[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) a0[a] = aprev[(int64_t)a * np + p];
+    double oa[HQ_SPEC_NOSC], sa[HQ_SPEC_NSD], ob[HQ_SPEC_NOSC], sb[HQ_SPEC_NSD];   /* two periods' state in registers */
+    const int64_t ostep = (int64_t)HQ_SPEC_NOSC * np, sstep = (int64_t)HQ_SPEC_NSD * np;
+    auto load = [np](const double* po, const double* ps, double* o, double* s) {
+#pragma unroll
+        for (int r = 0; r < HQ_SPEC_NOSC; r++) o[r] = po[(int64_t)r * np];
+#pragma unroll
+        for (int r = 0; r < HQ_SPEC_NSD; r++) s[r] = ps[(int64_t)r * np];
+    };
+    double* po = osc + p;
+    double* ps = sd + p;
+    load(po, ps, oa, sa);
+    double d[3] = { 0.0, 0.0, 0.0 };
+    hq_sample_disp(K, w, row, u1, d);
+    hq_sample_vel(K, w, row, u2, d);
+    hq_sample_acc(K, w, row, u2, u3, d);
+#pragma unroll
+    for (int a = 0; a < 3; a++) a1[a] = d[a] / dt2;
+    /* period j on the registers (o, s), the next period's loads into (on, sn) ahead of its arithmetic */
+    auto period = [&](int32_t j, double* o, double* s, double* on, double* sn) {
+        const bool more = j + 1 < nper;                          /* (the last period re-reads its own rows: no branch) */
+        load(po + (more ? ostep : 0), ps + (more ? sstep : 0), on, sn);
+        __builtin_amdgcn_sched_barrier(0);                       /* (the loads stay ahead of this period's arithmetic) */
+        double was[HQ_SPEC_NSD];
+#pragma unroll
+        for (int r = 0; r < HQ_SPEC_NSD; r++) was[r] = s[r];
+        hq_spec_fold(coef + (int64_t)HQ_SDOF_NCOEF * j, a0, a1, o, 1, s, 1);
+#pragma unroll
+        for (int r = 0; r < HQ_SPEC_NOSC; r++) po[(int64_t)r * np] = o[r];
+#pragma unroll
+        for (int r = 0; r < HQ_SPEC_NSD; r++)
+            if (s[r] != was[r]) ps[(int64_t)r * np] = s[r];
+        po += ostep; ps += sstep;
+    };
+    for (int32_t j = 0; j < nper; j += 2) {                      /* unrolled by two: the register sets swap roles */
+        period(j, oa, sa, ob, sb);
+        if (j + 1 < nper) period(j + 1, ob, sb, oa, sa);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) aprev[(int64_t)a * np + p] = a1[a];
 }
 
 /*
@@ -226,6 +309,18 @@ struct hq_ctx::hq_peak_tracker : hq_ctx::hq_output {
     int64_t nsamples = 0;         /* due steps folded or enqueued so far: accounted here, from `step` alone */
     double* d_pk = nullptr;       /* [nq][5][np] */
     int32_t* d_when = nullptr;    /* [nq][2][np] */
+};
+/* response-spectrum trackers (hq_spec_add): per point the last sample and, per period, three oscillators and their maxima,
+ * updated in place by hq_k_spec -- as a peak tracker, no ring, nothing pending, nothing for hq_run to count */
+struct hq_ctx::hq_spec_tracker : hq_ctx::hq_output {
+    hq_point_set pts;
+    int32_t nper = 0;
+    int64_t nsamples = 0;         /* due steps folded or enqueued so far */
+    std::vector<double> coef;     /* [nper][8], hq_sdof_coef at h = rate dt: what d_coef holds */
+    double* d_coef = nullptr;
+    double* d_aprev = nullptr;    /* [3][np] */
+    double* d_osc = nullptr;      /* [nper][2][3][np] */
+    double* d_sd = nullptr;       /* [nper][4][np] */
 };
 /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
  * pinned host memory.  A slot holds the fields one behind the other,
@@ -369,6 +464,35 @@ static void hq_peak_launch(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
                                                         c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
 }
 
+static void hq_output_free(hq_ctx::hq_spec_tracker& t)
+{
+    hq_points_free(&t.pts);
+    for (double* d : { t.d_coef, t.d_aprev, t.d_osc, t.d_sd }) if (d) hipFree(d);
+}
+
+/* the state of one spectrum tracker as it is before its first sample: at rest, aprev 0, sd 0 -- ON the compute stream, as
+ * hq_peak_zero; the caller waits */
+static hipError_t hq_spec_zero(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
+{
+    const size_t np = (size_t)t.pts.np, n = np * (size_t)t.nper;
+    if (np == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(t.d_aprev, 0, sizeof(double) * 3 * np, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t.d_osc, 0, sizeof(double) * HQ_SPEC_NOSC * n, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t.d_sd, 0, sizeof(double) * HQ_SPEC_NSD * n, c->stream);
+    return e;
+}
+
+/* head of a step, where hq_peak_launch sits and behind the same waits: one hq_k_spec launch per due tracker on the compute
+ * stream.  It reads d_u[spare] as u(t - 2 dt), as an acceleration peak tracker does: the caller holds the streams back. */
+static void hq_spec_launch(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
+{
+    t.nsamples++;
+    if (t.pts.np <= 0) return;
+    const auto k = t.pts.K == 1 ? hq_k_spec<1> : hq_k_spec<8>;
+    k<<<hq_blocks(t.pts.np, 256), 256, 0, c->stream>>>(t.pts.np, t.pts.d_ids, t.pts.d_phi, c->d_u[c->now], c->d_u[c->prev],
+                                                        c->d_u[c->spare], c->dt2, t.nper, t.d_coef, t.d_aprev, t.d_osc, t.d_sd);
+}
+
 static void hq_output_free(hq_ctx::hq_snapshot& sn)
 {
     if (sn.d_map) hipFree(sn.d_map);
@@ -405,7 +529,7 @@ static int hq_snapshot_launch(hq_ctx* c, hq_ctx::hq_snapshot& sn)
 
 /* The head of a step: every due output in solver_run's order (psolve.c:4277-4280: checkpoint / wavefield, then planes /
  * stations), then the trackers.  The launches that the step's other streams must stay behind (every snapshot, every recorder,
- * a tracker of accelerations: the comments above tell why) go first; ONE record of ev_output behind the last of them -- a
+ * a tracker of accelerations, a spectrum tracker: the comments above tell why) go first; ONE record of ev_output behind the last of them -- a
  * snapshot's own serves if nothing followed it -- holds the bricks' stream and the exchange chain's, on the patch variant,
  * where there is such a stream.  The trackers that need no hold follow that record: the streams never wait for them. */
 static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
@@ -418,6 +542,8 @@ static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
         if (hq_cadence_due(r.due, c->step)) { HQ_TRY(hq_record_launch(c, r)); if (r.pts.np > 0) { hold = true; recorded = false; } }
     for (auto& t : c->peaks)                     /* the trackers that read u(t - 2 dt) */
         if ((t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) { hq_peak_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
+    for (auto& t : c->specs)                     /* ... and the spectrum trackers, which all do */
+        if (hq_cadence_due(t.due, c->step)) { hq_spec_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
     if (hold && c->variant == HQ_VARIANT_PATCH && (hold_b || hold_c)) {
         if (!recorded) HQ_HIP(hipEventRecord(c->ev_output, c->stream));
         if (hold_b) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_output, 0));
@@ -436,7 +562,7 @@ static void hq_outputs_drop(hq_ctx* c, std::vector<T>& outs)
     outs.clear();
 }
 
-/* hq_record_clear, hq_peak_clear: every output of one kind goes, behind the steps enqueued so far */
+/* hq_record_clear, hq_peak_clear, hq_spec_clear: every output of one kind goes, behind the steps enqueued so far */
 template <typename T>
 static int hq_outputs_clear(hq_ctx* c, std::vector<T> hq_ctx::*outs)
 {
@@ -613,6 +739,121 @@ extern "C" int hq_peak_reset(hq_ctx* c, int32_t handle)
 }
 
 extern "C" int hq_peak_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::peaks); }
+
+/* ---- response-spectrum trackers: entry points (include/hq_solver.h) ---- */
+
+extern "C" int hq_spec_add(hq_ctx* c, const hq_spec_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const int32_t K = d->nodes_per_point;
+    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->nperiods < 1 || d->nperiods > HQ_SPEC_MAX_PERIODS || !d->periods ||
+        !(d->damping >= 0.0 && d->damping < 1.0) || (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
+        return hq_fail(HQ_ERR_ARG, "bad spectrum tracker description%s", "");
+    for (int32_t j = 0; j < d->nperiods; j++)                    /* finite and positive (x - x is NaN for an infinity) */
+        if (!(d->periods[j] > 0.0) || d->periods[j] - d->periods[j] != 0.0)
+            return hq_fail(HQ_ERR_ARG, "a period of a spectrum tracker is not finite and positive%s", "");
+    if (c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    hq_ctx::hq_spec_tracker t;
+    t.nper = d->nperiods; t.due = { d->rate, d->first_step };
+    t.coef.resize((size_t)HQ_SDOF_NCOEF * (size_t)t.nper);
+    for (int32_t j = 0; j < t.nper; j++)
+        hq_sdof_coef(d->periods[j], d->damping, (double)d->rate * c->dt, t.coef.data() + (size_t)HQ_SDOF_NCOEF * j);
+    const size_t np = (size_t)d->npoints, n = np * (size_t)t.nper;
+    const int64_t bytes0 = c->bytes;
+    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts, "hq_spec_add"));
+    int rc = hq_dev_alloc(c, &t.d_coef, t.coef.size());
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_aprev, 3 * np);
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_osc, HQ_SPEC_NOSC * n);
+    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_sd, HQ_SPEC_NSD * n);
+    hipError_t e = rc == HQ_OK ? hq_spec_zero(c, t) : hipSuccess;
+    if (rc == HQ_OK && e == hipSuccess)
+        e = hipMemcpyAsync(t.d_coef, t.coef.data(), sizeof(double) * t.coef.size(), hipMemcpyHostToDevice, c->stream);
+    if (rc == HQ_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);   /* (state and table are in place) */
+    if (rc != HQ_OK || e != hipSuccess) {
+        hq_output_free(t);
+        c->bytes = bytes0;
+        (void)hipGetLastError();
+        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_spec_add failed: %s", hipGetErrorString(e));
+    }
+    t.bytes = c->bytes - bytes0;
+    c->h2d_bytes += t.pts.h2d() + (int64_t)(sizeof(double) * t.coef.size());
+    t.id = c->spec_next_id++;
+    *handle = t.id;
+    c->specs.push_back(std::move(t));
+    return HQ_OK;
+}
+
+extern "C" int hq_spec_coefficients(hq_ctx* c, int32_t handle, double* coef)
+{
+    if (!c || !coef) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const hq_ctx::hq_spec_tracker* t = hq_output_find(c->specs, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
+    std::copy(t->coef.begin(), t->coef.end(), coef);
+    return HQ_OK;
+}
+
+/* the state crosses PCIe as the device keeps it ([nper][4][np], [nper][2][3][np], [3][np]); the caller's arrays are
+ * [np][nper][4], [np][nper][2][3], [np][3] -- hq_peak_transpose with the rows of a point counted across the periods */
+extern "C" int hq_spec_fetch(hq_ctx* c, int32_t handle, double* sd, double* osc, double* aprev, int64_t* nsamples)
+{
+    if (!c || !sd || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_spec_tracker* t = hq_output_find(c->specs, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->pts.np, nper = (size_t)t->nper;
+    *nsamples = t->nsamples;
+    if (np == 0) return HQ_OK;
+    std::vector<double> s(HQ_SPEC_NSD * nper * np), o(osc ? HQ_SPEC_NOSC * nper * np : 0), a(aprev ? 3 * np : 0);
+    HQ_HIP(hipMemcpyAsync(s.data(), t->d_sd, sizeof(double) * s.size(), hipMemcpyDeviceToHost, c->stream));
+    if (osc) HQ_HIP(hipMemcpyAsync(o.data(), t->d_osc, sizeof(double) * o.size(), hipMemcpyDeviceToHost, c->stream));
+    if (aprev) HQ_HIP(hipMemcpyAsync(a.data(), t->d_aprev, sizeof(double) * a.size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    hq_peak_transpose(np, nper * HQ_SPEC_NSD, true, s.data(), sd);
+    if (osc) hq_peak_transpose(np, nper * HQ_SPEC_NOSC, true, o.data(), osc);
+    if (aprev) hq_peak_transpose(np, (size_t)3, true, a.data(), aprev);
+    c->d2h_bytes += (int64_t)(sizeof(double) * (s.size() + o.size() + a.size()));
+    return HQ_OK;
+}
+
+extern "C" int hq_spec_load(hq_ctx* c, int32_t handle, const double* sd, const double* osc, const double* aprev, int64_t nsamples)
+{
+    if (!c || !sd || !osc || !aprev || nsamples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
+    hq_ctx::hq_spec_tracker* t = hq_output_find(c->specs, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->pts.np, nper = (size_t)t->nper;
+    t->nsamples = nsamples;
+    if (np == 0) return HQ_OK;
+    std::vector<double> s(HQ_SPEC_NSD * nper * np), o(HQ_SPEC_NOSC * nper * np), a(3 * np);
+    hq_peak_transpose(np, nper * HQ_SPEC_NSD, false, sd, s.data());
+    hq_peak_transpose(np, nper * HQ_SPEC_NOSC, false, osc, o.data());
+    hq_peak_transpose(np, (size_t)3, false, aprev, a.data());
+    HQ_HIP(hipMemcpyAsync(t->d_sd, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipMemcpyAsync(t->d_osc, o.data(), sizeof(double) * o.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipMemcpyAsync(t->d_aprev, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    c->h2d_bytes += (int64_t)(sizeof(double) * (s.size() + o.size() + a.size()));
+    return HQ_OK;
+}
+
+extern "C" int hq_spec_reset(hq_ctx* c, int32_t handle)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_spec_tracker* t = hq_output_find(c->specs, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    HQ_HIP(hq_spec_zero(c, *t));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    t->nsamples = 0;
+    return HQ_OK;
+}
+
+extern "C" int hq_spec_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::specs); }
 
 /* ---- field snapshots: entry points (include/hq_solver.h) ---- */
 

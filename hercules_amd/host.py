@@ -18,7 +18,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_forcefile_info", "hqh_forcefile_read", "hqh_forcefile_write",
            "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
-           "hqh_station_kinematics", "hqh_peak_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
+           "hqh_station_kinematics", "hqh_peak_fold", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
            "hqh_cvm_open", "hqh_cvm_close", "hqh_cvm_info", "hqh_cvm_query", "hqh_cvm_grid"]
 
@@ -773,6 +773,50 @@ def checkpoint_read(solver, path, rank=0, nranks=1):
     if rc != 0:
         raise capi.HqError("hqh_checkpoint_read failed: %d" % rc)
     return step.value
+
+
+def sdof_coef(periods, damping, h):
+    """hqh_sdof_coef per period: [nperiods, 8] = A11, A12, A21, A22, B11, B12, B21, B22 of the exact step h of the damped
+    oscillator under a piecewise-linear input -- the table Solver.spec_coefficients returns, bit for bit."""
+    periods = np.asarray(periods, np.float64).reshape(-1)
+    coef = np.zeros((len(periods), 8))
+    lib = load_library()
+    for j, t in enumerate(periods):
+        capi._check(lib.hqh_sdof_coef(ctypes.c_double(t), ctypes.c_double(damping), ctypes.c_double(h),
+                                      ctypes.c_void_p(coef[j].ctypes.data)))
+    return coef
+
+
+def spec_fold(coef, acc, sd=None, osc=None, aprev=None):
+    """hqh_spec_fold: acceleration samples acc [k, npoints, >= 3] -- the first three columns of the last axis count, which
+    may be a view such as record_fetch(...)[1][:, :, 6:9] -- folded with coef [nperiods, 8] into (sd [npoints, nperiods, 4],
+    osc [npoints, nperiods, 2, 3], aprev [npoints, 3]), the state Solver.spec_fetch returns.  None: a fresh state at rest;
+    given, they are folded into in place (float64, C-contiguous) -- two calls in sequence equal one on the concatenation.
+    Returns (sd, osc, aprev)."""
+    coef = np.ascontiguousarray(coef, np.float64)
+    if coef.ndim != 2 or coef.shape[1] != 8:
+        raise capi.HqError("spec_fold: coef %r is not [nperiods, 8]" % (coef.shape,))
+    nper = len(coef)
+    acc = np.asarray(acc, np.float64)
+    if acc.ndim != 3 or acc.shape[2] < 3:
+        raise capi.HqError("spec_fold: acc %r is not [k, npoints, >= 3]" % (acc.shape,))
+    k, npoints = acc.shape[:2]
+    item = acc.itemsize
+    stride = acc.strides[1] // item
+    regular = (acc.size == 0 or (acc.strides[2] == item and acc.strides[1] % item == 0 and stride >= 3 and
+                                 acc.strides[0] == acc.strides[1] * npoints))
+    if not regular:
+        acc = np.ascontiguousarray(acc[:, :, :3])
+        stride = 3
+    if sd is None:
+        sd, osc, aprev = np.zeros((npoints, nper, 4)), np.zeros((npoints, nper, 2, 3)), np.zeros((npoints, 3))
+    for a, shape in ((sd, (npoints, nper, 4)), (osc, (npoints, nper, 2, 3)), (aprev, (npoints, 3))):
+        if a is None or a.dtype != np.float64 or a.shape != shape or not a.flags.c_contiguous:
+            raise capi.HqError("spec_fold: sd / osc / aprev are not a state of %d points and %d periods" % (npoints, nper))
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)
+    capi._check(load_library().hqh_spec_fold(ctypes.c_int32(npoints), ctypes.c_int32(nper), ptr(coef), ctypes.c_int32(k),
+                                             ptr(acc), ctypes.c_int64(max(stride, 3)), ptr(sd), ptr(osc), ptr(aprev)))
+    return sd, osc, aprev
 
 
 def peak_fold(steps, samples, quantities, peaks=None, when=None):

@@ -302,6 +302,20 @@ HQ_API int hqh_station_kinematics(const double* phi, const double* tm1, const do
  * HQ_ERR_ARG for null pointers (where there is something to read), negative counts, quantities 0 or with unknown bits. */
 HQ_API int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps,
                          const double* samples, double* peaks, int32_t* when);
+/* The response-spectrum oscillator on the host (csrc/hq_sdof.h, the text hq_k_spec compiles).  hqh_sdof_coef: the eight
+ * coefficients {A11, A12, A21, A22, B11, B12, B21, B22} of the exact step h of x'' + 2 zeta omega x' + omega^2 x = -a_g(t),
+ * omega = 2 pi / period, for a piecewise-linear a_g -- a scaled Taylor series of the propagator, no libm: the numbers
+ * hq_spec_coefficients delivers, bit for bit.  HQ_ERR_ARG for a null pointer, a period or h that is not finite and positive,
+ * damping outside [0, 1).
+ * hqh_spec_fold: acceleration samples folded into the state hq_spec_fetch delivers.  acc holds nsamples x npoints rows of 3
+ * accelerations, sample-major, row r at acc + r * acc_stride (in doubles, >= 3): columns 6..8 of a derivs = 2 recorder's
+ * samples fold without a copy as (samples + 6, 9).  coef [nperiods][8]; sd [npoints][nperiods][4], osc
+ * [npoints][nperiods][2][3] (x then v) and aprev [npoints][3] are folded INTO: the caller starts them at 0, and two calls in
+ * sequence equal one call on the concatenation.  HQ_ERR_ARG for null pointers (where there is something to read), negative
+ * counts, a stride below 3. */
+HQ_API int hqh_sdof_coef(double period, double damping, double h, double* c);
+HQ_API int hqh_spec_fold(int32_t npoints, int32_t nperiods, const double* coef, int32_t nsamples, const double* acc,
+                         int64_t acc_stride, double* sd, double* osc, double* aprev);
 
 /*
  * Two-level layered box: the top nz_fine layers of elements of edge h over nz_coarse

@@ -545,6 +545,67 @@ HQ_API int hq_peak_reset(hq_ctx* ctx, int32_t handle);
 HQ_API int hq_peak_clear(hq_ctx* ctx);
 
 /*
+ * Response-spectrum trackers (additive under ABI 6): SD at a handful of periods per surface node or station -- what
+ * ShakeMap-style products and building codes are written in -- kept ON THE DEVICE.  A spectrum is a recursive filter plus a
+ * running maximum: a state of fixed size per point and period, a reduction over time in the sense a peak is.  The other
+ * route is a recorder at rate 1 with derivs = 2 and a filter over every sample on the host (hqh_spec_fold, hq_host.h).
+ * The oscillator is x'' + 2 zeta omega x' + omega^2 x = -a_g(t), omega = 2 pi / T, with a_g piecewise linear between the
+ * samples (Nigam & Jennings); its step is h = rate x dt and exact for that input (csrc/hq_sdof.h).  The eight
+ * coefficients of the step come from a scaled Taylor series of the 4 x 4 propagator in non-dimensional variables --
+ * additions, multiplications and divisions only, no libm, one result whatever compiler built the library -- because the
+ * textbook closed form cancels catastrophically at a simulation's time step (2e-5 relative at T = 10 s, h = 3e-4 s; the
+ * series holds 1e-14, tests/test_spectra_cpu.py).  hq_spec_coefficients delivers the table [nperiods][8] = {A11, A12,
+ * A21, A22, B11, B12, B21, B22} as the kernel reads it; it equals hqh_sdof_coef's bit for bit.
+ * Points, rate and first_step are a peak tracker's.  At the head of every step s >= first_step with s % rate == 0 one
+ * launch of hq_k_spec forms the acceleration sample hq_k_record takes at the point with derivs = 2 -- (u1 - 2 u2 + u3) /
+ * dt^2 on the state hq_gather3 documents, the recorder's column bit for bit -- and, per period, steps three oscillators
+ * (one per axis) from the point's previous sample to this one and folds |x| into the maxima.  The sample taken at the
+ * head of step s is the acceleration at time (s - 1) dt: u1 = u(s dt), u2 and u3 the two fields before it.  The state
+ * starts at rest with the previous sample 0, so the first due sample is the end of a ramp from 0 over h.  Per point:
+ *   sd[p][j][0..2]   = max |x_x|, |x_y|, |x_z| of period j
+ *   sd[p][j][3]      = max (x_x x_x + x_y x_y)      horizontal resultant, SQUARED, summed in this order: its root is
+ *                                                   RotD100 of SD
+ *   osc[p][j][0][0..2] = x, osc[p][j][1][0..2] = v  the oscillators as they stand
+ *   aprev[p][0..2]   = the last sample folded
+ * always double, in both libraries.  A value enters sd only if it is strictly greater: a NaN never enters sd, though a
+ * NaN sample does stay in x and v from then on, as in any linear filter.  The device multiplies nothing further: the
+ * caller forms PSV = omega SD and PSA = omega^2 SD (and takes the root of [3]), so the state equals hqh_spec_fold of a
+ * recorder's acceleration columns of the same run bit for bit.
+ * hq_spec_fetch waits for the enqueued work (as hq_peak_fetch does), copies the state out -- sd [np][nper][4]; osc
+ * [np][nper][2][3] and aprev [np][3], either of which may be NULL -- and leaves it in place; *nsamples counts the due steps
+ * folded so far.  It adds exactly the fetched bytes, 8 np (4 nper [+ 6 nper] [+ 3]), to hq_info.pcie_d2h_bytes; between
+ * fetches a tracker moves nothing.  hq_spec_load puts fetched values back (all three arrays required); hq_spec_reset
+ * puts the state at rest: zeros, nsamples 0.  hq_upload keeps trackers and their state; the due steps follow the new step
+ * number.  hq_spec_clear drops every spectrum tracker of the context and its memory (hq_destroy does, too); handles are
+ * not reused.  hq_record_clear, hq_snapshot_clear, hq_peak_clear and the hqh_solver_run* runners leave them alone, and no
+ * run call has anything to count for them.  The device memory counts in hq_info.device_bytes.  Every due step reads
+ * u(t - 2 dt), so it holds the bricks' and the exchange chain's streams back behind the launch, as a recorder's does.
+ * Errors: HQ_ERR_ARG for null pointers, npoints < 0, nodes_per_point not 1 or 8, rate < 1, nperiods outside 1 ..
+ * HQ_SPEC_MAX_PERIODS, a period that is not finite or not positive, damping outside [0, 1) or NaN, an id outside [0,
+ * nharbored), an unknown handle; HQ_ERR_STATE in the scatter variant, which keeps no u(t - 2 dt) (as hq_gather3);
+ * HQ_ERR_NOMEM if the device memory cannot be allocated -- nothing is kept then.  npoints == 0 is valid.
+ * A context without spectrum trackers enqueues exactly what it did before they existed.
+ */
+enum { HQ_SPEC_MAX_PERIODS = 32, HQ_SPEC_NVAL = 4 };
+typedef struct {
+    int32_t        npoints;
+    int32_t        nodes_per_point;  /* 8: ids [np][8] + phi [np][8]; 1: ids [np], phi ignored (may be NULL) */
+    const int32_t* ids;              /* local node ids, octor numbering */
+    const double*  phi;
+    int32_t        rate, first_step; /* a sample at the head of every step s >= first_step with s % rate == 0 */
+    int32_t        nperiods;         /* 1 .. HQ_SPEC_MAX_PERIODS */
+    int32_t        reserved;
+    const double*  periods;          /* [nperiods] seconds, finite, > 0 */
+    double         damping;          /* fraction of critical, 0 <= damping < 1 */
+} hq_spec_desc;
+HQ_API int hq_spec_add(hq_ctx* ctx, const hq_spec_desc* desc, int32_t* handle);
+HQ_API int hq_spec_coefficients(hq_ctx* ctx, int32_t handle, double* coef);
+HQ_API int hq_spec_fetch(hq_ctx* ctx, int32_t handle, double* sd, double* osc, double* aprev, int64_t* nsamples);
+HQ_API int hq_spec_load(hq_ctx* ctx, int32_t handle, const double* sd, const double* osc, const double* aprev, int64_t nsamples);
+HQ_API int hq_spec_reset(hq_ctx* ctx, int32_t handle);
+HQ_API int hq_spec_clear(hq_ctx* ctx);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
