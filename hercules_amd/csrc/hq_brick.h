@@ -135,14 +135,14 @@ struct hq_brick_host {
 struct hq_brick_plan {
     int64_t nb = 0;
     int32_t nunits = 0, nsame = 0, nrag = 0, nhet = 0, npacked = 0, nrhet = 0, nrpacked = 0;
-    hq_brick_unit* d_units = nullptr;
-    int32_t* d_tab = nullptr;
-    double* d_coef = nullptr;
-    float* d_coef32 = nullptr;
-    double* d_nt2 = nullptr;
+    hq_dbuf<hq_brick_unit> d_units;
+    hq_dbuf<int32_t> d_tab;
+    hq_dbuf<double> d_coef;
+    hq_dbuf<float> d_coef32;
+    hq_dbuf<double> d_nt2;
     hq_mat_const mat = { 0, 0, 0, 0, 0, 0 };  /* dt, bBase and the thresholds of the packed units (A and h ride in their records) */
-    int32_t* d_src_ptr = nullptr;            /* [nunits + 1] source entries per unit (hq_brick_set_source)        */
-    int32_t* d_src_ent = nullptr;            /* [n][2] = {node of the unit (plane * ny + y) * nx + x, loaded idx} */
+    hq_dbuf<int32_t> d_src_ptr;              /* [nunits + 1] source entries per unit (hq_brick_set_source)        */
+    hq_dbuf<int32_t> d_src_ent;              /* [n][2] = {node of the unit (plane * ny + y) * nx + x, loaded idx} */
     std::vector<int64_t> h_base;             /* units' first ids, ascending, and their launch slots: owner lookup */
     std::vector<int32_t> h_slot;
     std::vector<int64_t> h_size;
@@ -1373,12 +1373,10 @@ hq_k_brick_het(int32_t count, int32_t per_xcd, const hq_brick_unit* __restrict__
 
 static void hq_brick_free(hq_brick_plan* P)
 {
-    void* ptrs[] = { P->d_units, P->d_tab, P->d_coef, P->d_coef32, P->d_nt2, P->d_src_ptr, P->d_src_ent };
-    for (void* p : ptrs) if (p) hipFree(p);
-    *P = hq_brick_plan();
+    *P = hq_brick_plan();            /* (the device arrays go with their owners) */
 }
 
-static int hq_brick_upload(hq_brick_plan* P, const hq_brick_host& B, int64_t* bytes)
+static int hq_brick_upload(hq_brick_plan* P, const hq_brick_host& B, int64_t* ledger, hipStream_t st)
 {
     P->nb = B.nb;
     P->nunits = (int32_t)B.units.size();
@@ -1388,34 +1386,25 @@ static int hq_brick_upload(hq_brick_plan* P, const hq_brick_host& B, int64_t* by
     P->npacked = B.npacked;
     P->nrhet = B.nrhet;
     P->nrpacked = B.nrpacked;
-    if (P->nunits == 0) return 0;
+    if (P->nunits == 0) return HQ_OK;
     if (P->nhet + P->nrhet > 0) {
         /* (the double block of a packed unit is never read: only the blocks of the unpacked ones travel) */
-        if (P->nhet > P->npacked || P->nrhet > P->nrpacked) {
-            if (hipMalloc((void**)&P->d_coef, 8 * B.coef.size()) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-            *bytes += (int64_t)(8 * B.coef.size());
-            if (hipMemcpy(P->d_coef, B.coef.data(), 8 * B.coef.size(), hipMemcpyHostToDevice) != hipSuccess) { g_patch_err = "brick coefficient upload failed"; return -3; }
-        }
+        if (P->nhet > P->npacked || P->nrhet > P->nrpacked) HQ_TRY(P->d_coef.put(ledger, B.coef, st));
         if (P->npacked + P->nrpacked > 0) {
-            if (hipMalloc((void**)&P->d_coef32, 4 * B.coef32.size()) != hipSuccess || hipMalloc((void**)&P->d_nt2, 8 * B.nt2.size()) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-            *bytes += (int64_t)(4 * B.coef32.size() + 8 * B.nt2.size());
-            if (hipMemcpy(P->d_coef32, B.coef32.data(), 4 * B.coef32.size(), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(P->d_nt2, B.nt2.data(), 8 * B.nt2.size(), hipMemcpyHostToDevice) != hipSuccess) { g_patch_err = "brick coefficient upload failed"; return -3; }
+            HQ_TRY(P->d_coef32.put(ledger, B.coef32, st));
+            HQ_TRY(P->d_nt2.put(ledger, B.nt2, st));
         }
         static bool attr_set = false;            /* 80.7 KB of dynamic LDS per workgroup */
         if (!attr_set) {
             if (hipFuncSetAttribute((const void*)hq_k_brick_het<false>, hipFuncAttributeMaxDynamicSharedMemorySize, HQ_BH_LDS) != hipSuccess ||
                 hipFuncSetAttribute((const void*)hq_k_brick_het<true>, hipFuncAttributeMaxDynamicSharedMemorySize, HQ_BH_LDS) != hipSuccess ||
                 hipFuncSetAttribute((const void*)hq_k_brick_het<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, HQ_BH_LDS) != hipSuccess ||
-                hipFuncSetAttribute((const void*)hq_k_brick_het<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, HQ_BH_LDS) != hipSuccess) { g_patch_err = "hq_k_brick_het: LDS attribute"; return -3; }
+                hipFuncSetAttribute((const void*)hq_k_brick_het<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, HQ_BH_LDS) != hipSuccess) return hq_fail(HQ_ERR_DEVICE, "hq_k_brick_het: LDS attribute%s", "");
             attr_set = true;
         }
     }
-    if (hipMalloc((void**)&P->d_units, sizeof(hq_brick_unit) * B.units.size()) != hipSuccess ||
-        hipMalloc((void**)&P->d_tab, 4 * B.tab.size()) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-    *bytes += (int64_t)(sizeof(hq_brick_unit) * B.units.size() + 4 * B.tab.size());
-    if (hipMemcpy(P->d_units, B.units.data(), sizeof(hq_brick_unit) * B.units.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(P->d_tab, B.tab.data(), 4 * B.tab.size(), hipMemcpyHostToDevice) != hipSuccess) { g_patch_err = "brick table upload failed"; return -3; }
+    HQ_TRY(P->d_units.put(ledger, B.units, st));
+    HQ_TRY(P->d_tab.put(ledger, B.tab, st));
     /* owner lookup for hq_brick_set_source */
     std::vector<std::pair<int64_t, int32_t>> by_base;
     for (int32_t u = 0; u < P->nunits; u++) by_base.push_back({ B.units[(size_t)u].base, u });
@@ -1433,39 +1422,29 @@ static int hq_brick_upload(hq_brick_plan* P, const hq_brick_host& B, int64_t* by
         P->h_base.push_back(pr.first - top * nxy); P->h_slot.push_back(pr.second); P->h_size.push_back(size);
         P->h_first.push_back(pr.first);
     }
-    return 0;
+    return HQ_OK;
 }
 
 /* group the loaded nodes (device ids) that are brick nodes by their unit; the others are the patches' */
-static int hq_brick_set_source(hq_brick_plan* P, int32_t nloaded, const int32_t* loaded, int64_t* bytes)
+static int hq_brick_set_source(hq_brick_plan* P, int32_t nloaded, const int32_t* loaded, int64_t* ledger, hipStream_t st)
 {
-    if (P->d_src_ptr) { hipFree(P->d_src_ptr); P->d_src_ptr = nullptr; }
-    if (P->d_src_ent) { hipFree(P->d_src_ent); P->d_src_ent = nullptr; }
-    if (nloaded <= 0 || P->nunits == 0) return 0;
+    P->d_src_ptr.reset();
+    P->d_src_ent.reset();
+    if (nloaded <= 0 || P->nunits == 0) return HQ_OK;
     std::vector<std::array<int32_t, 3>> rec;
     for (int32_t i = 0; i < nloaded; i++) {
         if (loaded[i] >= P->nb) continue;
         const size_t k = (size_t)(std::upper_bound(P->h_base.begin(), P->h_base.end(), (int64_t)loaded[i]) - P->h_base.begin()) - 1;
         rec.push_back({ P->h_slot[k], (int32_t)(loaded[i] - P->h_first[k]), i });
     }
-    if (rec.empty()) return 0;
+    if (rec.empty()) return HQ_OK;
     std::sort(rec.begin(), rec.end());
     std::vector<int32_t> ptr((size_t)P->nunits + 1, 0), ent(rec.size() * 2);
     for (auto& r : rec) ptr[(size_t)r[0] + 1]++;
     for (int32_t u = 0; u < P->nunits; u++) ptr[(size_t)u + 1] += ptr[(size_t)u];
     for (size_t k = 0; k < rec.size(); k++) { ent[2 * k] = rec[k][1]; ent[2 * k + 1] = rec[k][2]; }
-    if (hipMalloc((void**)&P->d_src_ptr, 4 * ptr.size()) != hipSuccess) { P->d_src_ptr = nullptr; return -2; }
-    if (hipMalloc((void**)&P->d_src_ent, 4 * ent.size()) != hipSuccess) {
-        hipFree(P->d_src_ptr); P->d_src_ptr = nullptr; P->d_src_ent = nullptr;
-        return -2;
-    }
-    if (hipMemcpy(P->d_src_ptr, ptr.data(), 4 * ptr.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(P->d_src_ent, ent.data(), 4 * ent.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(P->d_src_ptr); hipFree(P->d_src_ent); P->d_src_ptr = nullptr; P->d_src_ent = nullptr;
-        return -3;
-    }
-    *bytes += (int64_t)(4 * ptr.size() + 4 * ent.size());
-    return 0;
+    HQ_TRY(P->d_src_ptr.put(ledger, ptr, st));
+    return P->d_src_ent.put(ledger, ent, st);
 }
 
 /* one step of all units: the HQ_BK_NTSAME units, then (a launch each) the units with per-node n_t rows and the HET units */

@@ -39,6 +39,7 @@
 
 #define HQ_SOLVER_IMPLEMENTATION 1
 #include "../../include/hq_solver.h"
+#include "hq_devmem.h"
 #include "hq_kernels.h"
 #include "hq_opts.h"
 #include "hq_cadence.h"
@@ -49,25 +50,7 @@
 #include "hq_patch.h"
 #include "hq_brick.h"
 
-/* ------------------------------------------------------------------------ */
-/* errors                                                                   */
-/* ------------------------------------------------------------------------ */
-
-static thread_local char g_err[512] = "";
-
-static int hq_fail(int code, const char* fmt, const char* a = "", const char* b = "")
-{
-    snprintf(g_err, sizeof g_err, fmt, a, b);
-    return code;
-}
-
-#define HQ_HIP(call)                                                                  \
-    do {                                                                              \
-        hipError_t e_ = (call);                                                       \
-        if (e_ != hipSuccess)                                                         \
-            return hq_fail(HQ_ERR_DEVICE, "%s: %s", #call, hipGetErrorString(e_));    \
-    } while (0)
-
+/* (hq_fail, HQ_HIP, HQ_TRY: hq_devmem.h) */
 extern "C" const char* hq_last_error(void) { return g_err; }
 
 /* ------------------------------------------------------------------------ */
@@ -134,24 +117,22 @@ struct hq_dev_messenger {
 
 struct hq_dev_schedule {
     std::vector<hq_dev_messenger> c, s;   /* c: owners of nodes I harbor; s: sharers of nodes I own */
-    int32_t* d_cmap = nullptr;   /* node ids, concatenated c-list mappings           */
-    int32_t* d_smap = nullptr;
-    int32_t* d_cmap_f = nullptr; /* the same entries as indices into the force table */
-    int32_t* d_smap_f = nullptr; /* (scatter: node ids again; patch: interface slots) */
-    double*  d_c_out = nullptr;  /* contribution send   [ctotal][3]                   */
-    double*  d_c_in = nullptr;   /* sharing      recv   [ctotal][3]                   */
-    double*  d_s_out = nullptr;  /* sharing      send   [stotal][3]                   */
+    hq_dbuf<int32_t> d_cmap;     /* node ids, concatenated c-list mappings           */
+    hq_dbuf<int32_t> d_smap;
+    int32_t* d_cmap_f = nullptr; /* the same entries as indices into the force table: views of d_cmap / d_smap (scatter: */
+    int32_t* d_smap_f = nullptr; /* node ids again) or of the slot tables below (patch: interface slots)                 */
+    hq_dbuf<int32_t> d_cslot, d_sslot;
+    hq_dbuf<double> d_c_out;     /* contribution send   [ctotal][3]                   */
+    hq_dbuf<double> d_s_out;     /* sharing      send   [stotal][3]                   */
+    double*  d_c_in = nullptr;   /* sharing      recv   [ctotal][3]: views of the two buffers below, or of the IPC arena */
     double*  d_s_in = nullptr;   /* contribution recv   [stotal][3]                   */
+    hq_dbuf<double> c_in_mem, s_in_mem;
     int32_t  ctotal = 0, stotal = 0;
     /* HQ_DEBUG_HALO: every record travels with the global identity of its node (psolve.c:5002-5007) */
-    int64_t* d_c_out_id = nullptr;
-    int64_t* d_c_in_id = nullptr;
-    int64_t* d_s_out_id = nullptr;
-    int64_t* d_s_in_id = nullptr;
+    hq_dbuf<int64_t> d_c_out_id, d_c_in_id, d_s_out_id, d_s_in_id;
     /* in-process transport (hq_group_link): where every record of the contribution / sharing send lands in its peer's
      * receive buffer -- the pack kernel writes there directly (one kernel per exchange, no copies) */
-    double** d_c_dst = nullptr;
-    double** d_s_dst = nullptr;
+    hq_dbuf<double*> d_c_dst, d_s_dst;
     /* host-staged transport (hq_comm_init_host): pinned mirrors of the four record buffers */
     double*  h_c_out = nullptr;
     double*  h_c_in = nullptr;
@@ -176,32 +157,28 @@ struct hq_ctx {
     double dt = 0, dt2 = 0;
     int64_t bytes = 0;
     int64_t h2d_bytes = 0, d2h_bytes = 0;    /* what crossed PCIe through the entry points since hq_create returned (hq_info) */
-    int32_t* d_gather_ids = nullptr;         /* hq_gather's scratch */
-    hq_real* d_gather_out = nullptr;
+    hq_dbuf<int32_t> d_gather_ids;           /* hq_gather's scratch (not counted in `bytes`) */
+    hq_dbuf<hq_real> d_gather_out;
     int32_t gather_cap = 0;
 
     /* element data, SoA */
     int32_t Epad = 0;
-    int32_t* d_lnid = nullptr;      /* [8][Epad] */
-    double* d_c1 = nullptr;
-    double* d_c2 = nullptr;
-    double* d_beta = nullptr;
+    hq_dbuf<int32_t> d_lnid;        /* [8][Epad] */
+    hq_dbuf<double> d_c1, d_c2, d_beta;
     /* node data */
     double* d_nt = nullptr;         /* [N][7]; behind bricks only the rows of the nodes nt_first .. N - 1 exist (d_nt_rows), */
-    double* d_nt_rows = nullptr;    /* d_nt = d_nt_rows - 7 nt_first: no kernel reads a brick node's 7-double row */
-    hq_real* d_u[3] = { nullptr, nullptr, nullptr };     /* the state in solver_float (psolve.h:60-64) */
+    hq_dbuf<double> d_nt_rows;      /* d_nt = d_nt_rows - 7 nt_first: no kernel reads a brick node's 7-double row */
+    hq_dbuf<hq_real> d_u[3];        /* the state in solver_float (psolve.h:60-64) */
     int now = 0, prev = 1, spare = 2;
-    double* d_force = nullptr;
+    hq_dbuf<double> d_force;
     /* source window */
     int32_t nloaded = 0, src_step0 = 0, src_nsteps = 0;
-    int32_t* d_loaded = nullptr;
-    double* d_F = nullptr;
+    hq_dbuf<int32_t> d_loaded;
+    hq_dbuf<double> d_F;
     std::vector<int32_t> h_loaded;  /* the loaded nodes (device numbering) of the window in place, and the */
     size_t F_capacity = 0;          /* doubles d_F holds: the next window of the same nodes reuses both    */
     /* hanging nodes */
-    int32_t* d_dn_id = nullptr;
-    int32_t* d_dn_ptr = nullptr;
-    int32_t* d_dn_anchor = nullptr;
+    hq_dbuf<int32_t> d_dn_id, d_dn_ptr, d_dn_anchor;
     /* halo */
     hq_dev_schedule an, dn;
     hq_nccl_comm comm = nullptr;
@@ -225,19 +202,19 @@ struct hq_ctx {
     int reserve_cus = 8;              /* CUs the interior launch leaves to the exchange chain (HQ_RESERVE_CUS) */
     /* patch variant: nodes on the partition interface */
     int32_t nI = 0, nOI = 0;
-    double* d_iforce = nullptr;       /* [nI][3] partial / summed force of interface nodes */
-    int32_t* d_oi_node = nullptr;     /* [nOI] interface nodes I own                        */
-    int32_t* d_oi_slot = nullptr;
-    int32_t* d_oi_ptr = nullptr;      /* [nOI+1] CSR: records of an.d_s_in to add, in       */
-    int32_t* d_oi_pos = nullptr;      /*         messenger order (fixed summation order)    */
-    int32_t* d_oi_fc = nullptr;       /* [nOI] first record | number of records << 24       */
+    hq_dbuf<double> d_iforce;         /* [nI][3] partial / summed force of interface nodes */
+    hq_dbuf<int32_t> d_oi_node;       /* [nOI] interface nodes I own                        */
+    hq_dbuf<int32_t> d_oi_slot;
+    hq_dbuf<int32_t> d_oi_ptr;        /* [nOI+1] CSR: records of an.d_s_in to add, in       */
+    hq_dbuf<int32_t> d_oi_pos;        /*         messenger order (fixed summation order)    */
+    hq_dbuf<int32_t> d_oi_fc;         /* [nOI] first record | number of records << 24       */
     /* compute_adjust DISTRIBUTION grouped by destination (hq_k_distribute): the shared hanging nodes of the patch
      * variant on the interface table (slots), all hanging nodes of the scatter variant on the force table (nodes) */
     int32_t  nSD = 0;                 /* destinations (anchors)                              */
-    int32_t* d_sd_dst = nullptr;      /* [nSD]                                               */
-    int32_t* d_sd_ptr = nullptr;      /* [nSD + 1]                                           */
-    int32_t* d_sd_src = nullptr;      /* [entries] hanging node (slot / id)                  */
-    int32_t* d_sd_deps = nullptr;     /* [entries] its number of anchors                     */
+    hq_dbuf<int32_t> d_sd_dst;        /* [nSD]                                               */
+    hq_dbuf<int32_t> d_sd_ptr;        /* [nSD + 1]                                           */
+    hq_dbuf<int32_t> d_sd_src;        /* [entries] hanging node (slot / id)                  */
+    hq_dbuf<int32_t> d_sd_deps;       /* [entries] its number of anchors                     */
     /* patch variant */
     hq_patch_plan plan;
     /* bricks (hq_brick.h): the device numbers the nodes its own way -- tile columns first -- and every entry point
@@ -248,8 +225,8 @@ struct hq_ctx {
     bool debug_halo = false;
     /* HQ_DEBUG_HALO over the IPC and the host-staged transport: exchanges counted on both sides (part of the check word) */
     unsigned long long dbg_send_epoch[4] = { 0, 0, 0, 0 }, dbg_recv_epoch[4] = { 0, 0, 0, 0 };
-    int64_t* d_gkey = nullptr;        /* [N] global identity of every harbored node          */
-    int32_t* d_halo_err = nullptr;    /* [4] records whose identity did not match; non-finite values seen by hq_check_finite;
+    hq_dbuf<int64_t> d_gkey;          /* [N] global identity of every harbored node          */
+    hq_dbuf<int32_t> d_halo_err;      /* [4] records whose identity did not match; non-finite values seen by hq_check_finite;
                                        * [2] IPC waits that timed out */
     /* device-side phase split (hq_options.phase_timing; every hq_run_timed batch): per step six events -- step start,
      * shell end, interior start / end, chain start / end -- in a ring of slots harvested when they are reused or asked for
@@ -281,18 +258,6 @@ struct hq_ctx {
     size_t ev_used = 0;
 };
 
-template <typename T>
-static int hq_dev_alloc(hq_ctx* c, T** p, size_t count)
-{
-    size_t bytes = sizeof(T) * (count ? count : 1);
-    hipError_t e = hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) return hq_fail(HQ_ERR_NOMEM, "hipMalloc(%s) failed: %s", "", hipGetErrorString(e));
-    c->bytes += (int64_t)bytes;
-    return HQ_OK;
-}
-
-#define HQ_TRY(x) do { int r_ = (x); if (r_ != HQ_OK) return r_; } while (0)
-
 /*
  * hq_comm_init_ipc: what a rank exports (one fixed-size blob, all-gathered by the caller's transport) and what it keeps.
  * Exchange x = 0 anchored-node contribution (received in an.d_s_in), 1 anchored-node sharing (an.d_c_in),
@@ -322,14 +287,14 @@ struct hq_ipc_state {
     hq_ipc_blob mine;
     std::vector<void*> opened;                       /* hipIpcOpenMemHandle results to close */
     unsigned long long* d_flags = nullptr;           /* in the arena */
-    double** d_dst[4] = { nullptr, nullptr, nullptr, nullptr };             /* where every send record of exchange x lands */
-    unsigned long long** d_sig[4] = { nullptr, nullptr, nullptr, nullptr }; /* the flags exchange x raises at its peers     */
-    int64_t** d_dst_id[4] = { nullptr, nullptr, nullptr, nullptr };         /* HQ_DEBUG_HALO: where every record's check word lands */
+    hq_dbuf<double*> d_dst[4];                       /* where every send record of exchange x lands */
+    hq_dbuf<unsigned long long*> d_sig[4];           /* the flags exchange x raises at its peers     */
+    hq_dbuf<int64_t*> d_dst_id[4];                   /* HQ_DEBUG_HALO: where every record's check word lands */
     int64_t* d_in_id[4] = { nullptr, nullptr, nullptr, nullptr };           /* ... and where this rank's arrive (in the arena)      */
     int32_t nsig[4] = { 0, 0, 0, 0 };
     unsigned long long wait_mask[4] = { 0, 0, 0, 0 };
     unsigned long long send_epoch[4] = { 0, 0, 0, 0 }, recv_epoch[4] = { 0, 0, 0, 0 };
-    uint32_t* d_done = nullptr;                      /* [4] last-block counters */
+    hq_dbuf<uint32_t> d_done;                        /* [4] last-block counters (not counted) */
     unsigned long long timeout_ticks = 2000000000ull; /* 20 s of the 100 MHz clock (HQ_IPC_TIMEOUT_MS) */
     unsigned long long delay_ticks = 0;              /* loopback only: flags raised this late (HQ_LOOPBACK_DELAY_US) */
 };
@@ -641,8 +606,8 @@ static inline unsigned hq_blocks(int64_t n, int bs) { return (unsigned)((n + bs 
 static int hq_build_schedule(hq_ctx* c, const hq_schedule* in, hq_dev_schedule* out)
 {
     auto load = [&](int32_t count, const hq_messenger* list, std::vector<hq_dev_messenger>& v,
-                    int32_t** d_map, double** d_out, double** d_in, int32_t* total, int64_t** d_out_id,
-                    int64_t** d_in_id) -> int {
+                    hq_dbuf<int32_t>& d_map, hq_dbuf<double>& d_out, hq_dbuf<double>& d_in, int32_t* total, hq_dbuf<int64_t>& d_out_id,
+                    hq_dbuf<int64_t>& d_in_id) -> int {
         std::vector<int32_t> map;
         for (int32_t i = 0; i < count; i++) {
             if (list[i].nodecount < 0 || (list[i].nodecount > 0 && !list[i].mapping))
@@ -659,21 +624,21 @@ static int hq_build_schedule(hq_ctx* c, const hq_schedule* in, hq_dev_schedule* 
         }
         *total = (int32_t)map.size();
         if (*total) {
-            HQ_TRY(hq_dev_alloc(c, d_map, map.size()));
-            HQ_TRY(hq_dev_alloc(c, d_out, map.size() * 3));
-            HQ_TRY(hq_dev_alloc(c, d_in, map.size() * 3));
-            HQ_HIP(hipMemcpy(*d_map, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
+            HQ_TRY(d_map.put(&c->bytes, map, c->stream));
+            HQ_TRY(d_out.alloc(&c->bytes, map.size() * 3));
+            HQ_TRY(d_in.alloc(&c->bytes, map.size() * 3));
             if (c->debug_halo) {
-                HQ_TRY(hq_dev_alloc(c, d_out_id, map.size()));
-                HQ_TRY(hq_dev_alloc(c, d_in_id, map.size()));
+                HQ_TRY(d_out_id.alloc(&c->bytes, map.size()));
+                HQ_TRY(d_in_id.alloc(&c->bytes, map.size()));
             }
         }
         return HQ_OK;
     };
-    HQ_TRY(load(in->c_count, in->first_c, out->c, &out->d_cmap, &out->d_c_out, &out->d_c_in, &out->ctotal,
-                &out->d_c_out_id, &out->d_c_in_id));
-    HQ_TRY(load(in->s_count, in->first_s, out->s, &out->d_smap, &out->d_s_out, &out->d_s_in, &out->stotal,
-                &out->d_s_out_id, &out->d_s_in_id));
+    HQ_TRY(load(in->c_count, in->first_c, out->c, out->d_cmap, out->d_c_out, out->c_in_mem, &out->ctotal,
+                out->d_c_out_id, out->d_c_in_id));
+    HQ_TRY(load(in->s_count, in->first_s, out->s, out->d_smap, out->d_s_out, out->s_in_mem, &out->stotal,
+                out->d_s_out_id, out->d_s_in_id));
+    out->d_c_in = out->c_in_mem; out->d_s_in = out->s_in_mem;
     out->d_cmap_f = out->d_cmap;
     out->d_smap_f = out->d_smap;
     return HQ_OK;
@@ -1400,12 +1365,8 @@ static int hq_build_distribution(hq_ctx* c, const std::vector<int32_t>& sd)
         src.push_back(sd[3 * i]); deps.push_back(sd[3 * i + 2]);
     }
     ptr.push_back((int32_t)src.size());
-    auto up = [&](const std::vector<int32_t>& v, int32_t** p) -> int {
-        HQ_TRY(hq_dev_alloc(c, p, v.size()));
-        HQ_HIP(hipMemcpy(*p, v.data(), 4 * v.size(), hipMemcpyHostToDevice));
-        return HQ_OK;
-    };
-    HQ_TRY(up(dst, &c->d_sd_dst)); HQ_TRY(up(ptr, &c->d_sd_ptr)); HQ_TRY(up(src, &c->d_sd_src)); HQ_TRY(up(deps, &c->d_sd_deps));
+    HQ_TRY(c->d_sd_dst.put(&c->bytes, dst, c->stream)); HQ_TRY(c->d_sd_ptr.put(&c->bytes, ptr, c->stream));
+    HQ_TRY(c->d_sd_src.put(&c->bytes, src, c->stream)); HQ_TRY(c->d_sd_deps.put(&c->bytes, deps, c->stream));
     c->nSD = (int32_t)dst.size();
     return HQ_OK;
 }
@@ -1455,18 +1416,21 @@ static int hq_setup_interface(hq_ctx* c, const hq_desc* d)
         if (slot[n] >= 0 && !nonowned[n]) { oin.push_back(n); ois.push_back(slot[n]); }
     c->nI = nI;
     c->nOI = (int32_t)oin.size();
-    HQ_TRY(hq_dev_alloc(c, &c->d_iforce, (size_t)nI * 3));
-    HQ_HIP(hipMemset(c->d_iforce, 0, sizeof(double) * 3 * (size_t)nI));
-    auto upload = [&](const std::vector<int32_t>& v, int32_t** dst) -> int {
-        if (v.empty()) return HQ_OK;
-        HQ_TRY(hq_dev_alloc(c, dst, v.size()));
-        HQ_HIP(hipMemcpy(*dst, v.data(), 4 * v.size(), hipMemcpyHostToDevice));
+    HQ_TRY(c->d_iforce.alloc(&c->bytes, (size_t)nI * 3));
+    HQ_TRY(c->d_iforce.fill(0, c->stream));
+    auto upload = [&](const std::vector<int32_t>& v, hq_dbuf<int32_t>& dst) -> int {
+        return v.empty() ? HQ_OK : dst.put(&c->bytes, v, c->stream);
+    };
+    /* the schedules' entries as interface slots: memory of their own, and the force-table views point there */
+    auto slots = [&](const std::vector<int32_t>& v, hq_dbuf<int32_t>& mem, int32_t** view) -> int {
+        HQ_TRY(upload(v, mem));
+        if (mem) *view = mem;
         return HQ_OK;
     };
-    HQ_TRY(upload(an_cs, &c->an.d_cmap_f));
-    HQ_TRY(upload(an_ss, &c->an.d_smap_f));
-    HQ_TRY(upload(dn_cs, &c->dn.d_cmap_f));
-    HQ_TRY(upload(dn_ss, &c->dn.d_smap_f));
+    HQ_TRY(slots(an_cs, c->an.d_cslot, &c->an.d_cmap_f));
+    HQ_TRY(slots(an_ss, c->an.d_sslot, &c->an.d_smap_f));
+    HQ_TRY(slots(dn_cs, c->dn.d_cslot, &c->dn.d_cmap_f));
+    HQ_TRY(slots(dn_ss, c->dn.d_sslot, &c->dn.d_smap_f));
     HQ_TRY(hq_build_distribution(c, sd));
     if (c->nOI) {
         /* records of the anchored-node contribution receive buffer per owned interface node,
@@ -1485,14 +1449,13 @@ static int hq_setup_interface(hq_ctx* c, const hq_desc* d)
             fc[(size_t)i] = cnt ? (int32_t)(((uint32_t)cnt << 24) | (uint32_t)pos[(size_t)ptr[(size_t)i]]) : 0;
         }
         if (pos.empty()) pos.push_back(0);
-        HQ_TRY(upload(fc, &c->d_oi_fc));
-        HQ_TRY(upload(oin, &c->d_oi_node));
-        HQ_TRY(upload(ois, &c->d_oi_slot));
-        HQ_TRY(upload(ptr, &c->d_oi_ptr));
-        HQ_TRY(upload(pos, &c->d_oi_pos));
+        HQ_TRY(upload(fc, c->d_oi_fc));
+        HQ_TRY(upload(oin, c->d_oi_node));
+        HQ_TRY(upload(ois, c->d_oi_slot));
+        HQ_TRY(upload(ptr, c->d_oi_ptr));
+        HQ_TRY(upload(pos, c->d_oi_pos));
     }
-    if (hq_patch_set_interface(c->opts, &c->plan, slot.data(), (int64_t)c->N, &c->bytes) != 0)
-        return hq_fail(HQ_ERR_NOMEM, "interface tables: %s", hq_patch_error());
+    HQ_TRY(hq_patch_set_interface(c->opts, &c->plan, slot.data(), (int64_t)c->N, &c->bytes, c->stream));
     if (!hq_set(c->opts.no_overlap)) {
         /* the exchange chain is short and latency-bound: let its kernels (and RCCL's) get CUs ahead
          * of the thousands of interior patch workgroups queued on the compute stream */
@@ -1533,10 +1496,7 @@ static int hq_field_to_device(hq_ctx* c, const hq_real* host, hq_real* dev)
 {
     const size_t bytes = sizeof(hq_real) * 3 * (size_t)c->N;
     c->h2d_bytes += (int64_t)bytes;
-    if (c->perm.empty()) {
-        HQ_HIP(hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice));
-        return HQ_OK;
-    }
+    if (c->perm.empty()) return hq_copy_wait(dev, host, bytes, hipMemcpyHostToDevice, c->stream);
     std::vector<hq_real> tmp;
     try { tmp.resize(3 * (size_t)c->N); } catch (...) { return hq_fail(HQ_ERR_NOMEM, "out of host memory%s", ""); }
     const int32_t* pm = c->perm.data();
@@ -1545,21 +1505,17 @@ static int hq_field_to_device(hq_ctx* c, const hq_real* host, hq_real* dev)
         const int64_t q = pm[n];
         tmp[(size_t)(3 * q)] = host[3 * n]; tmp[(size_t)(3 * q + 1)] = host[3 * n + 1]; tmp[(size_t)(3 * q + 2)] = host[3 * n + 2];
     }
-    HQ_HIP(hipMemcpy(dev, tmp.data(), bytes, hipMemcpyHostToDevice));
-    return HQ_OK;
+    return hq_copy_wait(dev, tmp.data(), bytes, hipMemcpyHostToDevice, c->stream);
 }
 
 static int hq_field_to_host(hq_ctx* c, const hq_real* dev, hq_real* host)
 {
     const size_t bytes = sizeof(hq_real) * 3 * (size_t)c->N;
     c->d2h_bytes += (int64_t)bytes;
-    if (c->perm.empty()) {
-        HQ_HIP(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
-        return HQ_OK;
-    }
+    if (c->perm.empty()) return hq_copy_wait(host, dev, bytes, hipMemcpyDeviceToHost, c->stream);
     std::vector<hq_real> tmp;
     try { tmp.resize(3 * (size_t)c->N); } catch (...) { return hq_fail(HQ_ERR_NOMEM, "out of host memory%s", ""); }
-    HQ_HIP(hipMemcpy(tmp.data(), dev, bytes, hipMemcpyDeviceToHost));
+    HQ_TRY(hq_copy_wait(tmp.data(), dev, bytes, hipMemcpyDeviceToHost, c->stream));
     const int32_t* pm = c->perm.data();
 #pragma omp parallel for schedule(static) if (c->N > 262144)     /* small fields: a parallel region costs more than the loop */
     for (int64_t n = 0; n < (int64_t)c->N; n++) {
@@ -1666,18 +1622,15 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
     size_t n3 = (size_t)c->N * 3;
     int nbuf = (variant == HQ_VARIANT_PATCH) ? 3 : 2;
     for (int b = 0; b < nbuf; b++) {
-        if ((rc = hq_dev_alloc(c, &c->d_u[b], n3)) != HQ_OK) return bail(rc);
-        if (hipMemset(c->d_u[b], 0, sizeof(hq_real) * n3) != hipSuccess) return bail(hq_fail(HQ_ERR_DEVICE, "memset%s", ""));
+        if ((rc = c->d_u[b].alloc(&c->bytes, n3)) != HQ_OK || (rc = c->d_u[b].fill(0, c->stream)) != HQ_OK) return bail(rc);
     }
     {
         /* brick nodes are updated from the 3-double rows (plan.d_nt3) or the unit's record: their 7-double rows stay on
          * the host (189 M-element basin: 10.5 GB less to upload and to hold) */
         const int64_t nt_first = (variant == HQ_VARIANT_PATCH) ? BH.nb : 0;
         const size_t rows = (size_t)std::max<int64_t>(c->N - nt_first, 1);
-        if ((rc = hq_dev_alloc(c, &c->d_nt_rows, rows * 7)) != HQ_OK) return bail(rc);
-        if (c->N > nt_first &&
-            hipMemcpy(c->d_nt_rows, ntab + 7 * nt_first, sizeof(double) * 7 * (size_t)(c->N - nt_first), hipMemcpyHostToDevice) != hipSuccess)
-            return bail(hq_fail(HQ_ERR_DEVICE, "nTable upload failed%s", ""));
+        if ((rc = c->d_nt_rows.alloc(&c->bytes, rows * 7)) != HQ_OK) return bail(rc);
+        if (c->N > nt_first && (rc = c->d_nt_rows.upload(ntab + 7 * nt_first, 7 * (size_t)(c->N - nt_first), c->stream)) != HQ_OK) return bail(rc);
         c->d_nt = c->d_nt_rows - 7 * nt_first;
     }
     lap("state buffers, n_t rows");
@@ -1687,17 +1640,13 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
 
     if (c->ldnnum) {
         int32_t na = d->dn_ptr[c->ldnnum];
-        if ((rc = hq_dev_alloc(c, &c->d_dn_id, (size_t)c->ldnnum)) != HQ_OK) return bail(rc);
-        if ((rc = hq_dev_alloc(c, &c->d_dn_ptr, (size_t)c->ldnnum + 1)) != HQ_OK) return bail(rc);
-        if ((rc = hq_dev_alloc(c, &c->d_dn_anchor, (size_t)na)) != HQ_OK) return bail(rc);
-        if (hipMemcpy(c->d_dn_id, d->dn_ldnid, sizeof(int32_t) * c->ldnnum, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_dn_ptr, d->dn_ptr, sizeof(int32_t) * (c->ldnnum + 1), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_dn_anchor, d->dn_lanid, sizeof(int32_t) * na, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(hq_fail(HQ_ERR_DEVICE, "dangling-node table upload failed%s", ""));
+        if ((rc = c->d_dn_id.put(&c->bytes, d->dn_ldnid, (size_t)c->ldnnum, c->stream)) != HQ_OK ||
+            (rc = c->d_dn_ptr.put(&c->bytes, d->dn_ptr, (size_t)c->ldnnum + 1, c->stream)) != HQ_OK ||
+            (rc = c->d_dn_anchor.put(&c->bytes, d->dn_lanid, (size_t)na, c->stream)) != HQ_OK)
+            return bail(rc);
     }
 
-    if ((rc = hq_dev_alloc(c, &c->d_halo_err, 4)) != HQ_OK) return bail(rc);
-    if (hipMemset(c->d_halo_err, 0, 4 * sizeof(int32_t)) != hipSuccess) return bail(hq_fail(HQ_ERR_DEVICE, "memset%s", ""));
+    if ((rc = c->d_halo_err.alloc(&c->bytes, 4)) != HQ_OK || (rc = c->d_halo_err.fill(0, c->stream)) != HQ_OK) return bail(rc);
     if (hq_set(opts.debug_halo) && c->nranks > 1) {
         /* the reference's -DDEBUG exchange: every halo record carries the global id of its node and the
          * receiver checks it (psolve.c:5002-5007, 5058-5069).  Identity = node_t.gnid where the caller
@@ -1714,28 +1663,21 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
             }
             key[(size_t)n] = (int64_t)h;
         }
-        if ((rc = hq_dev_alloc(c, &c->d_gkey, (size_t)c->N)) != HQ_OK) return bail(rc);
-        if (hipMemcpy(c->d_gkey, key.data(), sizeof(int64_t) * (size_t)c->N, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(hq_fail(HQ_ERR_DEVICE, "node identity upload failed%s", ""));
+        if ((rc = c->d_gkey.put(&c->bytes, key, c->stream)) != HQ_OK) return bail(rc);
         c->debug_halo = true;
     }
 
     if (variant == HQ_VARIANT_SCATTER) {
-        if ((rc = hq_dev_alloc(c, &c->d_force, n3)) != HQ_OK) return bail(rc);
-        if (hipMemset(c->d_force, 0, sizeof(double) * n3) != hipSuccess) return bail(hq_fail(HQ_ERR_DEVICE, "memset%s", ""));
+        if ((rc = c->d_force.alloc(&c->bytes, n3)) != HQ_OK || (rc = c->d_force.fill(0, c->stream)) != HQ_OK) return bail(rc);
         c->Epad = (c->E + 63) & ~63;
         std::vector<int32_t> soa((size_t)8 * c->Epad, 0);
         for (int64_t e = 0; e < c->E; e++)
             for (int n = 0; n < 8; n++) soa[(size_t)n * c->Epad + e] = d->lnid[8 * e + n];
-        if ((rc = hq_dev_alloc(c, &c->d_lnid, soa.size())) != HQ_OK) return bail(rc);
-        if ((rc = hq_dev_alloc(c, &c->d_c1, (size_t)c->E)) != HQ_OK) return bail(rc);
-        if ((rc = hq_dev_alloc(c, &c->d_c2, (size_t)c->E)) != HQ_OK) return bail(rc);
-        if ((rc = hq_dev_alloc(c, &c->d_beta, (size_t)c->E)) != HQ_OK) return bail(rc);
-        if (hipMemcpy(c->d_lnid, soa.data(), sizeof(int32_t) * soa.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_c1, prep.c1.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_c2, prep.c2.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->d_beta, prep.beta.data(), sizeof(double) * c->E, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(hq_fail(HQ_ERR_DEVICE, "element table upload failed%s", ""));
+        if ((rc = c->d_lnid.put(&c->bytes, soa, c->stream)) != HQ_OK ||
+            (rc = c->d_c1.put(&c->bytes, prep.c1.data(), (size_t)c->E, c->stream)) != HQ_OK ||
+            (rc = c->d_c2.put(&c->bytes, prep.c2.data(), (size_t)c->E, c->stream)) != HQ_OK ||
+            (rc = c->d_beta.put(&c->bytes, prep.beta.data(), (size_t)c->E, c->stream)) != HQ_OK)
+            return bail(rc);
         if ((rc = hq_build_schedule(c, &d->an_sched, &c->an)) != HQ_OK) return bail(rc);
         if ((rc = hq_build_schedule(c, &d->dn_sched, &c->dn)) != HQ_OK) return bail(rc);
         if (c->ldnnum) {
@@ -1747,18 +1689,14 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
             if ((rc = hq_build_distribution(c, sd)) != HQ_OK) return bail(rc);
         }
     } else {
-        int64_t pb = 0;
         c->plan.ragged_default = true;
         rc = hq_patch_build(opts, &c->plan, c->E, c->N, d->lnid, d->node_xyz, prep.c1.data(), prep.c2.data(), prep.beta.data(), ntab,
-                            prep.dn, prep.seed0.data(), &pb, BH.nb);
+                            prep.dn, prep.seed0.data(), &c->bytes, c->stream, BH.nb);
         lap("patch plan");
-        if (rc == 0 && BH.nb > 0) rc = hq_brick_upload(&c->bricks, BH, &pb);
+        if (rc == HQ_OK && BH.nb > 0) rc = hq_brick_upload(&c->bricks, BH, &c->bytes, c->stream);
         c->bricks.mat = { 0.0, 0.0, d->deltaT, d->mat_bbase, d->mat_threshold_damping, d->mat_threshold_vpvs };
         lap("brick upload");
-        if (rc != 0)
-            return bail(hq_fail(rc == -1 ? HQ_ERR_ARG : (rc == -2 ? HQ_ERR_NOMEM : HQ_ERR_DEVICE), "patch plan: %s",
-                                hq_patch_error()));
-        c->bytes += pb;
+        if (rc != HQ_OK) return bail(rc);
         /* one persistent workgroup per CU, the same number on every XCD (workgroups are dealt to the XCDs round-robin) */
         c->plan.grid_cus = std::max(8, prop.multiProcessorCount & ~7);
         if ((rc = hq_build_schedule(c, &d->an_sched, &c->an)) != HQ_OK) return bail(rc);
@@ -1783,43 +1721,18 @@ extern "C" int hq_destroy(hq_ctx* c)
     if (c->comm && g_rccl.handle) g_rccl.CommDestroy(c->comm);
     if (c->ipc) {
         hq_ipc_state* I = c->ipc;
-        for (int x = 0; x < 4; x++) {                /* the receive buffers live in the arena */
-            hq_dev_schedule* sc = x < 2 ? &c->an : &c->dn;
-            if (x & 1) sc->d_c_in = nullptr; else sc->d_s_in = nullptr;
-            if (I->d_dst[x]) hipFree(I->d_dst[x]);
-            if (I->d_sig[x]) hipFree(I->d_sig[x]);
-            if (I->d_dst_id[x]) hipFree(I->d_dst_id[x]);
-        }
         for (void* p : I->opened) hipIpcCloseMemHandle(p);
-        if (I->d_done) hipFree(I->d_done);
         if (I->arena) hipFree(I->arena);
         delete I;
         c->ipc = nullptr;
     }
-    void* ptrs[] = { c->d_gather_ids, c->d_gather_out, c->d_lnid, c->d_c1, c->d_c2, c->d_beta, c->d_nt_rows, c->d_u[0], c->d_u[1], c->d_u[2],
-                     c->d_force, c->d_loaded, c->d_F, c->d_dn_id, c->d_dn_ptr, c->d_dn_anchor,
-                     c->an.d_cmap, c->an.d_smap, c->an.d_c_out, c->an.d_c_in, c->an.d_s_out, c->an.d_s_in,
-                     c->dn.d_cmap, c->dn.d_smap, c->dn.d_c_out, c->dn.d_c_in, c->dn.d_s_out, c->dn.d_s_in,
-                     c->d_iforce, c->d_oi_node, c->d_oi_slot, c->d_oi_ptr, c->d_oi_pos, c->d_oi_fc, c->d_sd_dst, c->d_sd_ptr, c->d_sd_src, c->d_sd_deps,
-                     c->d_gkey, c->d_halo_err, c->an.d_c_out_id, c->an.d_c_in_id, c->an.d_s_out_id, c->an.d_s_in_id,
-                     c->dn.d_c_out_id, c->dn.d_c_in_id, c->dn.d_s_out_id, c->dn.d_s_in_id };
-    for (void* p : ptrs) if (p) hipFree(p);
-    hq_outputs_drop(c, c->recs);
-    hq_outputs_drop(c, c->peaks);
-    hq_outputs_drop(c, c->specs);
-    hq_outputs_drop(c, c->snaps);
+    hq_outputs_drop(c->snaps);
     if (c->sstream) hipStreamDestroy(c->sstream);
-    if (c->an.d_cmap_f && c->an.d_cmap_f != c->an.d_cmap) hipFree(c->an.d_cmap_f);
-    if (c->an.d_smap_f && c->an.d_smap_f != c->an.d_smap) hipFree(c->an.d_smap_f);
-    if (c->dn.d_cmap_f && c->dn.d_cmap_f != c->dn.d_cmap) hipFree(c->dn.d_cmap_f);
-    if (c->dn.d_smap_f && c->dn.d_smap_f != c->dn.d_smap) hipFree(c->dn.d_smap_f);
     for (hq_dev_schedule* sc : { &c->an, &c->dn }) {
         for (double* hp : { sc->h_c_out, sc->h_c_in, sc->h_s_out, sc->h_s_in })
             if (hp) hipHostFree(hp);
         for (int64_t* hp : { sc->h_c_out_id, sc->h_c_in_id, sc->h_s_out_id, sc->h_s_in_id })
             if (hp) hipHostFree(hp);
-        if (sc->d_c_dst) hipFree(sc->d_c_dst);
-        if (sc->d_s_dst) hipFree(sc->d_s_dst);
     }
     if (c->ev_sent) hipEventDestroy(c->ev_sent);
     if (c->ev_output) hipEventDestroy(c->ev_output);
@@ -1844,7 +1757,7 @@ extern "C" int hq_destroy(hq_ctx* c)
     for (hipEvent_t e : c->ev) hipEventDestroy(e);
     for (int k = 0; k < 2; k++) if (c->ev_span[k]) hipEventDestroy(c->ev_span[k]);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                        /* the device arrays go with their owners (hq_devmem.h) */
     return HQ_OK;
 }
 
@@ -1967,19 +1880,15 @@ extern "C" int hq_comm_selftest(hq_ctx* c, int32_t count)
     hipStream_t xs = c->overlap ? c->cstream : c->stream;
     std::vector<double> h((size_t)count), back((size_t)count, 0.0);
     for (int32_t i = 0; i < count; i++) h[i] = 1.0 + 0.5 * i;
-    double *d_out = nullptr, *d_in = nullptr;
-    HQ_HIP(hipMalloc((void**)&d_out, sizeof(double) * count));
-    HQ_HIP(hipMalloc((void**)&d_in, sizeof(double) * count));
-    HQ_HIP(hipMemcpyAsync(d_out, h.data(), sizeof(double) * count, hipMemcpyHostToDevice, xs));
-    HQ_HIP(hipMemsetAsync(d_in, 0, sizeof(double) * count, xs));
+    hq_dbuf<double> d_out, d_in;                     /* not counted: gone when this returns, however it returns */
+    HQ_TRY(d_out.put(nullptr, h, xs));
+    HQ_TRY(d_in.alloc(nullptr, (size_t)count));
+    HQ_TRY(d_in.fill(0, xs));
     HQ_NCCL(g_rccl.GroupStart());
     HQ_NCCL(g_rccl.Recv(d_in, (size_t)count, HQ_NCCL_DOUBLE, c->rank, c->comm, xs));
     HQ_NCCL(g_rccl.Send(d_out, (size_t)count, HQ_NCCL_DOUBLE, c->rank, c->comm, xs));
     HQ_NCCL(g_rccl.GroupEnd());
-    HQ_HIP(hipMemcpyAsync(back.data(), d_in, sizeof(double) * count, hipMemcpyDeviceToHost, xs));
-    HQ_HIP(hipStreamSynchronize(xs));
-    hipFree(d_out);
-    hipFree(d_in);
+    HQ_TRY(hq_copy_wait(back.data(), d_in, sizeof(double) * count, hipMemcpyDeviceToHost, xs));
     for (int32_t i = 0; i < count; i++)
         if (back[i] != h[i]) return hq_fail(HQ_ERR_COMM, "self send/recv through RCCL returned other data than was sent%s", "");
     return HQ_OK;
@@ -2012,6 +1921,12 @@ static double** hq_ipc_inbuf(hq_ctx* c, int x)
 {
     hq_dev_schedule* s = x < 2 ? &c->an : &c->dn;
     return (x & 1) ? &s->d_c_in : &s->d_s_in;
+}
+
+static hq_dbuf<double>& hq_ipc_inbuf_mem(hq_ctx* c, int x)
+{
+    hq_dev_schedule* s = x < 2 ? &c->an : &c->dn;
+    return (x & 1) ? s->c_in_mem : s->s_in_mem;
 }
 
 static int32_t hq_ipc_total(hq_ctx* c, int x, bool sending)
@@ -2055,8 +1970,7 @@ static int hq_ipc_prepare(hq_ctx* c)
         }
     I->arena_bytes = off;
     /* everything that can fail comes before the schedules' receive buffers are touched (round-4 advisor) */
-    if (hipMalloc((void**)&I->d_done, 4 * sizeof(uint32_t)) != hipSuccess || hipMemset(I->d_done, 0, 4 * sizeof(uint32_t)) != hipSuccess) {
-        if (I->d_done) hipFree(I->d_done);
+    if (I->d_done.alloc(nullptr, 4) != HQ_OK || I->d_done.fill(0, c->stream) != HQ_OK) {
         delete I;
         return hq_fail(HQ_ERR_NOMEM, "hipMalloc failed%s", "");
     }
@@ -2080,7 +1994,6 @@ static int hq_ipc_prepare(hq_ctx* c)
         (void)hipGetLastError();
         if (I->arena) { hipFree(I->arena); I->arena = nullptr; }
         if (attempt == last_kind) {
-            hipFree(I->d_done);
             delete I;
             return hq_fail(HQ_ERR_DEVICE, "IPC transport: cannot allocate / export the receive arena: %s", hipGetErrorString(e));
         }
@@ -2092,13 +2005,13 @@ static int hq_ipc_prepare(hq_ctx* c)
     if (hipDeviceGetPCIBusId(B.busid, (int)sizeof(B.busid), c->device) != hipSuccess) B.busid[0] = 0;
     /* (zeroed BEFORE the blob leaves this rank: a peer raises flags in here as soon as it steps, and a hipMemset on the null
      *  stream is finished only when the device says so) */
-    if (hipMemset(I->arena, 0, I->arena_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { hipFree(I->arena); hipFree(I->d_done); delete I; return hq_fail(HQ_ERR_DEVICE, "memset%s", ""); }
+    if (hipMemset(I->arena, 0, I->arena_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { hipFree(I->arena); delete I; return hq_fail(HQ_ERR_DEVICE, "memset%s", ""); }
     c->bytes += (int64_t)I->arena_bytes;
     I->d_flags = (unsigned long long*)I->arena;
     for (int x = 0; x < 4; x++) {
-        double** pin = hq_ipc_inbuf(c, x);
-        if (*pin) { hipFree(*pin); *pin = nullptr; }
-        if (hq_ipc_total(c, x, false)) *pin = (double*)((char*)I->arena + B.buf_off[x]);
+        double** pin = hq_ipc_inbuf(c, x);           /* the receive buffer moves into the arena: its own memory goes */
+        hq_ipc_inbuf_mem(c, x).reset();
+        *pin = hq_ipc_total(c, x, false) ? (double*)((char*)I->arena + B.buf_off[x]) : nullptr;
         std::vector<hq_dev_messenger>& rcv = hq_ipc_list(c, x, false);
         B.nrecv[x] = (int32_t)rcv.size();
         for (size_t j = 0; j < rcv.size(); j++) {
@@ -2196,14 +2109,9 @@ static int hq_ipc_connect(hq_ctx* c, const char* blobs)
         }
         I->nsig[x] = (int32_t)sig.size();
         if (total) {
-            HQ_TRY(hq_dev_alloc(c, &I->d_dst[x], (size_t)total));
-            HQ_HIP(hipMemcpy(I->d_dst[x], dst.data(), sizeof(double*) * (size_t)total, hipMemcpyHostToDevice));
-            HQ_TRY(hq_dev_alloc(c, &I->d_sig[x], sig.size()));
-            if (!sig.empty()) HQ_HIP(hipMemcpy(I->d_sig[x], sig.data(), sizeof(void*) * sig.size(), hipMemcpyHostToDevice));
-            if (c->debug_halo) {
-                HQ_TRY(hq_dev_alloc(c, &I->d_dst_id[x], (size_t)total));
-                HQ_HIP(hipMemcpy(I->d_dst_id[x], dst_id.data(), sizeof(int64_t*) * (size_t)total, hipMemcpyHostToDevice));
-            }
+            HQ_TRY(I->d_dst[x].put(&c->bytes, dst, c->stream));
+            HQ_TRY(I->d_sig[x].put(&c->bytes, sig, c->stream));
+            if (c->debug_halo) HQ_TRY(I->d_dst_id[x].put(&c->bytes, dst_id, c->stream));
         }
     }
     I->ready = true;
@@ -2220,9 +2128,7 @@ extern "C" int hq_comm_init_ipc(hq_ctx* c, const void* blobs)
     if (!c->ipc) return hq_fail(HQ_ERR_STATE, "hq_comm_init_ipc needs the blobs of hq_comm_ipc_export (this rank's among them)%s", "");
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
     HQ_HIP(hipSetDevice(c->device));
-    HQ_TRY(hq_ipc_connect(c, (const char*)blobs));
-    HQ_HIP(hipDeviceSynchronize());              /* the destination / flag tables are in place before a step reads them */
-    return HQ_OK;
+    return hq_ipc_connect(c, (const char*)blobs);    /* (the destination / flag tables are in place when it returns) */
 }
 
 /* the same with the number of blobs the caller holds: a short all-gather is refused instead of read out of bounds */
@@ -2237,9 +2143,7 @@ extern "C" int hq_comm_init_loopback(hq_ctx* c)
     if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     HQ_TRY(hq_ipc_prepare(c));
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
-    HQ_TRY(hq_ipc_connect(c, nullptr));
-    HQ_HIP(hipDeviceSynchronize());
-    return HQ_OK;
+    return hq_ipc_connect(c, nullptr);
 }
 
 extern "C" int hq_group_link(hq_ctx** ctxs, int32_t n)
@@ -2307,21 +2211,15 @@ extern "C" int hq_group_link(hq_ctx** ctxs, int32_t n)
             }
         }
     }
-    std::vector<double**> uploaded;
-    auto undo = [&]() { for (double** p : uploaded) hipFree(p); };
-    for (auto& T : tables) {
-        double** d = nullptr;
-        hipSetDevice(T.c->device);
-        if (hipMalloc((void**)&d, sizeof(double*) * T.dst.size()) != hipSuccess ||
-            hipMemcpy(d, T.dst.data(), sizeof(double*) * T.dst.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            if (d) hipFree(d);
-            undo();
+    std::vector<hq_dbuf<double*>> uploaded(tables.size());   /* each on its member's device and compute stream, in its ledger */
+    for (size_t k = 0; k < tables.size(); k++) {
+        hq_ctx* tc = tables[k].c;
+        hipSetDevice(tc->device);
+        if (uploaded[k].put(&tc->bytes, tables[k].dst, tc->stream) != HQ_OK)
             return hq_fail(HQ_ERR_NOMEM, "hq_group_link: destination tables%s", "");
-        }
-        uploaded.push_back(d);
     }
     std::vector<hq_ctx*>* g = new (std::nothrow) std::vector<hq_ctx*>(ctxs, ctxs + n);
-    if (!g) { undo(); return hq_fail(HQ_ERR_NOMEM, "out of host memory%s", ""); }
+    if (!g) return hq_fail(HQ_ERR_NOMEM, "out of host memory%s", "");
     /* publish.  Partitions that share ONE GPU gain nothing from a second stream -- the other partitions' patches fill
      * the device anyway -- and pay for its events: the 64M box in 8 in-process partitions steps in 2.54 ms on one
      * stream per partition against 3.28 ms with the chain on a second one (round 2; HQ_OVERLAP=1 forces it, which is
@@ -2330,11 +2228,7 @@ extern "C" int hq_group_link(hq_ctx** ctxs, int32_t n)
     for (int32_t i = 0; i < n; i++) { ctxs[i]->group = g; ctxs[i]->overlap = ov && ctxs[i]->can_overlap; }
     for (size_t k = 0; k < tables.size(); k++) {
         hq_dev_schedule* s = tables[k].which ? &tables[k].c->dn : &tables[k].c->an;
-        (tables[k].contribution ? s->d_c_dst : s->d_s_dst) = uploaded[k];
-        tables[k].c->bytes += (int64_t)(sizeof(double*) * tables[k].dst.size());
-    }
-    for (int32_t i = 0; i < n; i++) {            /* the tables are in place on every member's device before a step reads them */
-        if (hipSetDevice(ctxs[i]->device) == hipSuccess) (void)hipDeviceSynchronize();
+        (tables[k].contribution ? s->d_c_dst : s->d_s_dst) = std::move(uploaded[k]);
     }
     return HQ_OK;
 }
@@ -2382,30 +2276,26 @@ extern "C" int hq_set_source(hq_ctx* c, int32_t nloaded, const int32_t* loaded, 
                             (size_t)nloaded * 3 * (size_t)nsteps <= c->F_capacity;
     if (same_nodes) {
         c->src_step0 = step0; c->src_nsteps = nsteps;
-        HQ_HIP(hipMemcpy(c->d_F, F, sizeof(double) * 3 * nloaded * (size_t)nsteps, hipMemcpyHostToDevice));
-        HQ_HIP(hipStreamSynchronize(nullptr));
+        HQ_TRY(c->d_F.upload(F, 3 * (size_t)nloaded * (size_t)nsteps, c->stream));
         c->h2d_bytes += 24 * (int64_t)nloaded * nsteps;
         return HQ_OK;
     }
-    if (c->d_loaded) { hipFree(c->d_loaded); c->d_loaded = nullptr; }
-    if (c->d_F) { hipFree(c->d_F); c->d_F = nullptr; }
-    c->nloaded = nloaded; c->src_step0 = step0; c->src_nsteps = nsteps;
-    c->h_loaded.clear(); c->F_capacity = 0;
+    c->d_loaded.reset();
+    c->d_F.reset();
+    c->nloaded = 0; c->src_step0 = step0; c->src_nsteps = nsteps;   /* no source until every table is in place: a failure */
+    c->h_loaded.clear(); c->F_capacity = 0;                         /* below leaves the context stepping without one      */
     if (nloaded && nsteps) {
-        HQ_TRY(hq_dev_alloc(c, &c->d_loaded, (size_t)nloaded));
-        HQ_TRY(hq_dev_alloc(c, &c->d_F, (size_t)nloaded * 3 * nsteps));
-        HQ_HIP(hipMemcpy(c->d_loaded, loaded, sizeof(int32_t) * nloaded, hipMemcpyHostToDevice));
-        HQ_HIP(hipMemcpy(c->d_F, F, sizeof(double) * 3 * nloaded * (size_t)nsteps, hipMemcpyHostToDevice));
+        HQ_TRY(c->d_loaded.put(&c->bytes, loaded, (size_t)nloaded, c->stream));
+        HQ_TRY(c->d_F.put(&c->bytes, F, (size_t)nloaded * 3 * (size_t)nsteps, c->stream));
         c->h2d_bytes += 4 * (int64_t)nloaded + 24 * (int64_t)nloaded * nsteps;
         c->h_loaded.assign(loaded, loaded + nloaded);
         c->F_capacity = (size_t)nloaded * 3 * (size_t)nsteps;
     }
     if (c->variant == HQ_VARIANT_PATCH) {
-        int r = hq_patch_set_source(&c->plan, (nloaded && nsteps) ? nloaded : 0, loaded, &c->bytes);
-        if (r == 0) r = hq_brick_set_source(&c->bricks, (nloaded && nsteps) ? nloaded : 0, loaded, &c->bytes);
-        if (r != 0) return hq_fail(HQ_ERR_NOMEM, "source table allocation failed%s", "");
+        HQ_TRY(hq_patch_set_source(&c->plan, (nloaded && nsteps) ? nloaded : 0, loaded, &c->bytes, c->stream));
+        HQ_TRY(hq_brick_set_source(&c->bricks, (nloaded && nsteps) ? nloaded : 0, loaded, &c->bytes, c->stream));
     }
-    HQ_HIP(hipStreamSynchronize(nullptr));       /* the tables went through the null stream; the steps read them on other streams */
+    c->nloaded = nloaded;
     return HQ_OK;
 }
 
@@ -2430,7 +2320,7 @@ extern "C" int hq_sync(hq_ctx* c)
     hq_clock_harvest_all(c, true);
     if (c->ipc) {
         int32_t late = 0;
-        HQ_HIP(hipMemcpy(&late, c->d_halo_err + 2, sizeof late, hipMemcpyDeviceToHost));
+        HQ_TRY(hq_copy_wait(&late, c->d_halo_err + 2, sizeof late, hipMemcpyDeviceToHost, c->stream));
         if (late) {
             char n[32];
             snprintf(n, sizeof n, "%d", late);
@@ -2441,7 +2331,7 @@ extern "C" int hq_sync(hq_ctx* c)
     }
     if (c->debug_halo) {
         int32_t bad = 0;
-        HQ_HIP(hipMemcpy(&bad, c->d_halo_err, sizeof bad, hipMemcpyDeviceToHost));
+        HQ_TRY(hq_copy_wait(&bad, c->d_halo_err, sizeof bad, hipMemcpyDeviceToHost, c->stream));
         if (bad) {
             char n[32];
             snprintf(n, sizeof n, "%d", bad);
@@ -2557,15 +2447,10 @@ static int hq_gather_impl(hq_ctx* c, int32_t n, const int32_t* lnid, hq_real* o1
     /* scratch kept with the context: a host that prints stations every few steps (psolve.c:6679-6790) must not pay a
      * hipMalloc / hipFree pair per call */
     if (n > c->gather_cap) {
-        if (c->d_gather_ids) { hipFree(c->d_gather_ids); c->d_gather_ids = nullptr; }
-        if (c->d_gather_out) { hipFree(c->d_gather_out); c->d_gather_out = nullptr; }
         c->gather_cap = 0;
         const int32_t cap = std::max(n, 1024);
-        HQ_HIP(hipMalloc((void**)&c->d_gather_ids, sizeof(int32_t) * (size_t)cap));
-        if (hipMalloc((void**)&c->d_gather_out, sizeof(hq_real) * 9 * (size_t)cap) != hipSuccess) {
-            hipFree(c->d_gather_ids); c->d_gather_ids = nullptr;
-            return hq_fail(HQ_ERR_NOMEM, "hipMalloc failed%s", "");
-        }
+        HQ_TRY(c->d_gather_ids.alloc(nullptr, (size_t)cap));
+        HQ_TRY(c->d_gather_out.alloc(nullptr, 9 * (size_t)cap));
         c->gather_cap = cap;
     }
     int32_t* d_ids = c->d_gather_ids;
@@ -2620,7 +2505,6 @@ extern "C" int hq_upload(hq_ctx* c, const hq_real* tm1, const hq_real* tm2, int3
         HQ_HIP(hipMemsetAsync(c->d_u[c->spare], 0, bytes, c->stream));
         HQ_HIP(hipStreamSynchronize(c->stream));
     }
-    HQ_HIP(hipStreamSynchronize(nullptr));       /* (the copies above went through the null stream: nothing of them may be in flight) */
     c->step = step;
     return HQ_OK;
 }
@@ -2654,6 +2538,5 @@ extern "C" int hq_download_force(hq_ctx* c, double* force)
     if (c->variant != HQ_VARIANT_SCATTER) return hq_fail(HQ_ERR_STATE, "no force array in the patch variant%s", "");
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
-    HQ_HIP(hipMemcpy(force, c->d_force, sizeof(double) * 3 * (size_t)c->N, hipMemcpyDeviceToHost));
-    return HQ_OK;
+    return hq_copy_wait(force, c->d_force, sizeof(double) * 3 * (size_t)c->N, hipMemcpyDeviceToHost, c->stream);
 }

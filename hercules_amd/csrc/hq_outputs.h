@@ -279,7 +279,6 @@ struct hq_ctx::hq_output {
     hq_cadence due = { 1, 0 };
     hq_step_ring ring = { nullptr, 0, 0, 0 };
     std::vector<int32_t> steps;   /* [capacity] the ring's storage: a move keeps the buffer, and so ring.steps */
-    int64_t bytes = 0;            /* device memory of this output (part of `bytes`) */
     void open(int32_t rate, int64_t first_step, int32_t capacity)
     {
         due = { rate, first_step };
@@ -291,15 +290,15 @@ struct hq_ctx::hq_output {
  * them in whole lines */
 struct hq_point_set {
     int32_t np = 0, K = 8;
-    int32_t* d_ids = nullptr;     /* [K][np] device numbering */
-    double* d_phi = nullptr;      /* [8][np]; NULL for K = 1 */
+    hq_dbuf<int32_t> d_ids;       /* [K][np] device numbering */
+    hq_dbuf<double> d_phi;        /* [8][np]; NULL for K = 1 */
     int64_t h2d() const { return (K == 8 ? 12 : 4) * (int64_t)K * np; }   /* bytes the upload carried: 4 per id, 8 per weight */
 };
 /* sample recorders (hq_record_add): rings in device memory */
 struct hq_ctx::hq_recorder : hq_ctx::hq_output {
     hq_point_set pts;
     int32_t derivs = 0;
-    double* d_ring = nullptr;     /* [capacity][np][3 (1 + derivs)] */
+    hq_dbuf<double> d_ring;       /* [capacity][np][3 (1 + derivs)] */
 };
 /* peak-motion trackers (hq_peak_add): a running state per point updated in place by hq_k_peak -- no ring, no pending
  * samples, nothing for hq_run to count */
@@ -307,8 +306,8 @@ struct hq_ctx::hq_peak_tracker : hq_ctx::hq_output {
     hq_point_set pts;
     int32_t quantities = 0, nq = 0;
     int64_t nsamples = 0;         /* due steps folded or enqueued so far: accounted here, from `step` alone */
-    double* d_pk = nullptr;       /* [nq][5][np] */
-    int32_t* d_when = nullptr;    /* [nq][2][np] */
+    hq_dbuf<double> d_pk;         /* [nq][5][np] */
+    hq_dbuf<int32_t> d_when;      /* [nq][2][np] */
 };
 /* response-spectrum trackers (hq_spec_add): per point the last sample and, per period, three oscillators and their maxima,
  * updated in place by hq_k_spec -- as a peak tracker, no ring, nothing pending, nothing for hq_run to count */
@@ -317,10 +316,10 @@ struct hq_ctx::hq_spec_tracker : hq_ctx::hq_output {
     int32_t nper = 0;
     int64_t nsamples = 0;         /* due steps folded or enqueued so far */
     std::vector<double> coef;     /* [nper][8], hq_sdof_coef at h = rate dt: what d_coef holds */
-    double* d_coef = nullptr;
-    double* d_aprev = nullptr;    /* [3][np] */
-    double* d_osc = nullptr;      /* [nper][2][3][np] */
-    double* d_sd = nullptr;       /* [nper][4][np] */
+    hq_dbuf<double> d_coef;
+    hq_dbuf<double> d_aprev;      /* [3][np] */
+    hq_dbuf<double> d_osc;        /* [nper][2][3][np] */
+    hq_dbuf<double> d_sd;         /* [nper][4][np] */
 };
 /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
  * pinned host memory.  A slot holds the fields one behind the other,
@@ -329,8 +328,8 @@ struct hq_ctx::hq_spec_tracker : hq_ctx::hq_output {
  * recorded on the compute stream and waited for by sstream, which copies the slot and records the slot's done event */
 struct hq_ctx::hq_snapshot : hq_ctx::hq_output {
     int32_t first = 0, count = 0, fields = 0;
-    int32_t* d_map = nullptr;     /* [count] device id of node first + i; NULL on contexts without a renumbering */
-    char* d_stage = nullptr;      /* [slots][slot_bytes] */
+    hq_dbuf<int32_t> d_map;       /* [count] device id of node first + i; NULL on contexts without a renumbering */
+    hq_dbuf<char> d_stage;        /* [slots][slot_bytes] */
     char* h_stage = nullptr;      /* the same, pinned host memory */
     size_t off[3] = { 0, 0, 0 };  /* tm1, tm2, vel inside a slot */
     size_t slot_bytes = 0;
@@ -366,17 +365,9 @@ static T* hq_output_find(std::vector<T>& outs, int32_t handle)
     return nullptr;
 }
 
-static void hq_points_free(hq_point_set* ps)
-{
-    if (ps->d_ids) hipFree(ps->d_ids);
-    if (ps->d_phi) hipFree(ps->d_phi);
-    ps->d_ids = nullptr; ps->d_phi = nullptr;
-}
-
 /* the tables of np points from the caller's [np][K] ids and [np][8] weights (K = 8 only): every id checked, device numbering,
- * transposed to [K][np], uploaded ON the compute stream and waited for -- the steps read the tables on other streams, the host
- * tables go out of scope, hq_upload tells what a null-stream operation cost.  A failure leaves nothing allocated; h2d() the caller counts. */
-static int hq_points_build(hq_ctx* c, int32_t np, int32_t K, const int32_t* ids_in, const double* phi_in, hq_point_set* ps, const char* who)
+ * transposed to [K][np], uploaded ON the compute stream and waited for (hq_devmem.h).  h2d() the caller counts. */
+static int hq_points_build(hq_ctx* c, int32_t np, int32_t K, const int32_t* ids_in, const double* phi_in, hq_point_set* ps)
 {
     for (int64_t i = 0; i < (int64_t)K * np; i++)
         if (ids_in[i] < 0 || ids_in[i] >= c->N) return hq_fail(HQ_ERR_ARG, "node id out of range%s", "");
@@ -389,29 +380,9 @@ static int hq_points_build(hq_ctx* c, int32_t np, int32_t K, const int32_t* ids_
             if (K == 8) phi[(size_t)k * np + p] = phi_in[8 * (size_t)p + k];
         }
     ps->np = np; ps->K = K;
-    const int64_t bytes0 = c->bytes;
-    int rc = hq_dev_alloc(c, &ps->d_ids, ids.size());
-    if (rc == HQ_OK && K == 8) rc = hq_dev_alloc(c, &ps->d_phi, phi.size());
-    hipError_t e = hipSuccess;
-    if (rc == HQ_OK && np > 0) {
-        e = hipMemcpyAsync(ps->d_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && K == 8)
-            e = hipMemcpyAsync(ps->d_phi, phi.data(), sizeof(double) * phi.size(), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (rc != HQ_OK || e != hipSuccess) {
-        hq_points_free(ps);
-        c->bytes = bytes0;
-        (void)hipGetLastError();
-        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "%s failed: %s", who, hipGetErrorString(e));
-    }
+    HQ_TRY(ps->d_ids.put(&c->bytes, ids, c->stream));
+    if (K == 8) HQ_TRY(ps->d_phi.put(&c->bytes, phi, c->stream));
     return HQ_OK;
-}
-
-static void hq_output_free(hq_ctx::hq_recorder& r)
-{
-    hq_points_free(&r.pts);
-    if (r.d_ring) hipFree(r.d_ring);
 }
 
 /* head of a step: one hq_k_record launch per due recorder on the compute stream, behind the waits phase 0 has already
@@ -430,22 +401,12 @@ static int hq_record_launch(hq_ctx* c, hq_ctx::hq_recorder& r)
     return HQ_OK;
 }
 
-static void hq_output_free(hq_ctx::hq_peak_tracker& t)
+/* the state of one tracker as it is before its first sample: peaks 0, `when` -1 (every byte 0xff) -- on the compute stream,
+ * in place when this returns */
+static int hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
 {
-    hq_points_free(&t.pts);
-    if (t.d_pk) hipFree(t.d_pk);
-    if (t.d_when) hipFree(t.d_when);
-}
-
-/* the state of one tracker as it is before its first sample: peaks 0, `when` -1 (every byte 0xff) -- ON the compute stream
- * (hq_upload tells what a null-stream memset cost); the caller waits */
-static hipError_t hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
-{
-    const size_t n = (size_t)t.nq * (size_t)t.pts.np;
-    if (n == 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(t.d_pk, 0, sizeof(double) * HQ_PEAK_NVAL * n, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t.d_when, 0xff, sizeof(int32_t) * HQ_PEAK_NWHEN * n, c->stream);
-    return e;
+    HQ_TRY(t.d_pk.fill(0, c->stream));
+    return t.d_when.fill(0xff, c->stream);
 }
 
 /* head of a step, where hq_record_launch sits and behind the same waits: one hq_k_peak launch per due tracker on the
@@ -464,22 +425,12 @@ static void hq_peak_launch(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
                                                         c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
 }
 
-static void hq_output_free(hq_ctx::hq_spec_tracker& t)
+/* the state of one spectrum tracker as it is before its first sample: at rest, aprev 0, sd 0 -- as hq_peak_zero */
+static int hq_spec_zero(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
 {
-    hq_points_free(&t.pts);
-    for (double* d : { t.d_coef, t.d_aprev, t.d_osc, t.d_sd }) if (d) hipFree(d);
-}
-
-/* the state of one spectrum tracker as it is before its first sample: at rest, aprev 0, sd 0 -- ON the compute stream, as
- * hq_peak_zero; the caller waits */
-static hipError_t hq_spec_zero(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
-{
-    const size_t np = (size_t)t.pts.np, n = np * (size_t)t.nper;
-    if (np == 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(t.d_aprev, 0, sizeof(double) * 3 * np, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t.d_osc, 0, sizeof(double) * HQ_SPEC_NOSC * n, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t.d_sd, 0, sizeof(double) * HQ_SPEC_NSD * n, c->stream);
-    return e;
+    HQ_TRY(t.d_aprev.fill(0, c->stream));
+    HQ_TRY(t.d_osc.fill(0, c->stream));
+    return t.d_sd.fill(0, c->stream);
 }
 
 /* head of a step, where hq_peak_launch sits and behind the same waits: one hq_k_spec launch per due tracker on the compute
@@ -493,10 +444,9 @@ static void hq_spec_launch(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
                                                         c->d_u[c->spare], c->dt2, t.nper, t.d_coef, t.d_aprev, t.d_osc, t.d_sd);
 }
 
+/* what of a snapshot is not device memory: the pinned mirror and the slots' events */
 static void hq_output_free(hq_ctx::hq_snapshot& sn)
 {
-    if (sn.d_map) hipFree(sn.d_map);
-    if (sn.d_stage) hipFree(sn.d_stage);
     if (sn.h_stage) hipHostFree(sn.h_stage);
     for (hipEvent_t e : sn.done) if (e) hipEventDestroy(e);
 }
@@ -554,12 +504,11 @@ static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
     return HQ_OK;
 }
 
-/* free every output of one kind (the caller has waited for every stream that serves them) */
-template <typename T>
-static void hq_outputs_drop(hq_ctx* c, std::vector<T>& outs)
+/* every snapshot goes (the caller has waited for every stream that serves them); the other kinds are device memory only */
+static void hq_outputs_drop(std::vector<hq_ctx::hq_snapshot>& snaps)
 {
-    for (auto& o : outs) { hq_output_free(o); c->bytes -= o.bytes; }
-    outs.clear();
+    for (auto& sn : snaps) hq_output_free(sn);
+    snaps.clear();
 }
 
 /* hq_record_clear, hq_peak_clear, hq_spec_clear: every output of one kind goes, behind the steps enqueued so far */
@@ -570,7 +519,7 @@ static int hq_outputs_clear(hq_ctx* c, std::vector<T> hq_ctx::*outs)
     if ((c->*outs).empty()) return HQ_OK;
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
-    hq_outputs_drop(c, c->*outs);
+    (c->*outs).clear();
     return HQ_OK;
 }
 
@@ -587,11 +536,8 @@ extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* hand
     HQ_HIP(hipSetDevice(c->device));
     hq_ctx::hq_recorder r;
     r.derivs = d->derivs;
-    const int64_t bytes0 = c->bytes;
-    HQ_TRY(hq_points_build(c, d->npoints, 8, d->ids, d->phi, &r.pts, "hq_record_add"));
-    const int rc = hq_dev_alloc(c, &r.d_ring, (size_t)d->capacity * (size_t)d->npoints * 3 * (size_t)(1 + d->derivs));
-    if (rc != HQ_OK) { hq_output_free(r); c->bytes = bytes0; return rc; }
-    r.bytes = c->bytes - bytes0;
+    HQ_TRY(hq_points_build(c, d->npoints, 8, d->ids, d->phi, &r.pts));
+    HQ_TRY(r.d_ring.alloc(&c->bytes, (size_t)d->capacity * (size_t)d->npoints * 3 * (size_t)(1 + d->derivs)));
     c->h2d_bytes += r.pts.h2d();
     r.open(d->rate, INT32_MIN, d->capacity);                     /* every multiple of the rate, wherever `step` is set to */
     r.id = c->rec_next_id++;
@@ -624,9 +570,9 @@ extern "C" int hq_record_fetch(hq_ctx* c, int32_t handle, int32_t max_samples, d
     const size_t row = (size_t)r->pts.np * 3 * (size_t)(1 + r->derivs);          /* doubles per sample */
     const int32_t first = std::min(n, r->ring.capacity - head);              /* up to the ring's end, then from its start */
     if (row > 0) {
-        HQ_HIP(hipMemcpy(out, r->d_ring + (size_t)head * row, sizeof(double) * row * (size_t)first, hipMemcpyDeviceToHost));
+        HQ_TRY(hq_copy_wait(out, r->d_ring + (size_t)head * row, sizeof(double) * row * (size_t)first, hipMemcpyDeviceToHost, c->stream));
         if (n > first)
-            HQ_HIP(hipMemcpy(out + (size_t)first * row, r->d_ring, sizeof(double) * row * (size_t)(n - first), hipMemcpyDeviceToHost));
+            HQ_TRY(hq_copy_wait(out + (size_t)first * row, r->d_ring, sizeof(double) * row * (size_t)(n - first), hipMemcpyDeviceToHost, c->stream));
     }
     for (int32_t k = 0; k < n; k++) steps[k] = r->steps[(size_t)hq_step_ring_slot_at(&r->ring, k)];
     c->d2h_bytes += 8 * (int64_t)row * n;
@@ -653,19 +599,10 @@ extern "C" int hq_peak_add(hq_ctx* c, const hq_peak_desc* d, int32_t* handle)
     hq_ctx::hq_peak_tracker t;
     t.quantities = d->quantities; t.nq = hq_peak_nq(d->quantities); t.due = { d->rate, d->first_step };
     const size_t n = (size_t)t.nq * (size_t)d->npoints;
-    const int64_t bytes0 = c->bytes;
-    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts, "hq_peak_add"));
-    int rc = hq_dev_alloc(c, &t.d_pk, HQ_PEAK_NVAL * n);
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_when, HQ_PEAK_NWHEN * n);
-    hipError_t e = rc == HQ_OK ? hq_peak_zero(c, t) : hipSuccess;
-    if (rc == HQ_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);   /* (the state is in place) */
-    if (rc != HQ_OK || e != hipSuccess) {
-        hq_output_free(t);
-        c->bytes = bytes0;
-        (void)hipGetLastError();
-        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_peak_add failed: %s", hipGetErrorString(e));
-    }
-    t.bytes = c->bytes - bytes0;
+    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts));
+    HQ_TRY(t.d_pk.alloc(&c->bytes, HQ_PEAK_NVAL * n));
+    HQ_TRY(t.d_when.alloc(&c->bytes, HQ_PEAK_NWHEN * n));
+    HQ_TRY(hq_peak_zero(c, t));
     c->h2d_bytes += t.pts.h2d();
     t.id = c->peak_next_id++;
     *handle = t.id;
@@ -732,8 +669,7 @@ extern "C" int hq_peak_reset(hq_ctx* c, int32_t handle)
     if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
-    HQ_HIP(hq_peak_zero(c, *t));
-    HQ_HIP(hipStreamSynchronize(c->stream));
+    HQ_TRY(hq_peak_zero(c, *t));
     t->nsamples = 0;
     return HQ_OK;
 }
@@ -761,23 +697,12 @@ extern "C" int hq_spec_add(hq_ctx* c, const hq_spec_desc* d, int32_t* handle)
     for (int32_t j = 0; j < t.nper; j++)
         hq_sdof_coef(d->periods[j], d->damping, (double)d->rate * c->dt, t.coef.data() + (size_t)HQ_SDOF_NCOEF * j);
     const size_t np = (size_t)d->npoints, n = np * (size_t)t.nper;
-    const int64_t bytes0 = c->bytes;
-    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts, "hq_spec_add"));
-    int rc = hq_dev_alloc(c, &t.d_coef, t.coef.size());
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_aprev, 3 * np);
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_osc, HQ_SPEC_NOSC * n);
-    if (rc == HQ_OK) rc = hq_dev_alloc(c, &t.d_sd, HQ_SPEC_NSD * n);
-    hipError_t e = rc == HQ_OK ? hq_spec_zero(c, t) : hipSuccess;
-    if (rc == HQ_OK && e == hipSuccess)
-        e = hipMemcpyAsync(t.d_coef, t.coef.data(), sizeof(double) * t.coef.size(), hipMemcpyHostToDevice, c->stream);
-    if (rc == HQ_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);   /* (state and table are in place) */
-    if (rc != HQ_OK || e != hipSuccess) {
-        hq_output_free(t);
-        c->bytes = bytes0;
-        (void)hipGetLastError();
-        return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_spec_add failed: %s", hipGetErrorString(e));
-    }
-    t.bytes = c->bytes - bytes0;
+    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts));
+    HQ_TRY(t.d_coef.put(&c->bytes, t.coef, c->stream));
+    HQ_TRY(t.d_aprev.alloc(&c->bytes, 3 * np));
+    HQ_TRY(t.d_osc.alloc(&c->bytes, HQ_SPEC_NOSC * n));
+    HQ_TRY(t.d_sd.alloc(&c->bytes, HQ_SPEC_NSD * n));
+    HQ_TRY(hq_spec_zero(c, t));
     c->h2d_bytes += t.pts.h2d() + (int64_t)(sizeof(double) * t.coef.size());
     t.id = c->spec_next_id++;
     *handle = t.id;
@@ -847,8 +772,7 @@ extern "C" int hq_spec_reset(hq_ctx* c, int32_t handle)
     if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
-    HQ_HIP(hq_spec_zero(c, *t));
-    HQ_HIP(hipStreamSynchronize(c->stream));
+    HQ_TRY(hq_spec_zero(c, *t));
     t->nsamples = 0;
     return HQ_OK;
 }
@@ -874,10 +798,10 @@ extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* ha
     sn.off[1] = at; if (d->fields & HQ_SNAP_TM2) at += pad(sizeof(hq_real) * n3);
     sn.off[2] = at; if (d->fields & HQ_SNAP_VEL) at += pad(sizeof(double) * n3);
     sn.slot_bytes = at;
-    const int64_t bytes0 = c->bytes;
     const bool had_stream = c->sstream != nullptr;
-    int rc = hq_dev_alloc(c, &sn.d_stage, sn.slot_bytes * (size_t)d->slots);
-    if (rc == HQ_OK && !c->perm.empty()) rc = hq_dev_alloc(c, &sn.d_map, (size_t)d->count);
+    int rc = sn.d_stage.alloc(&c->bytes, sn.slot_bytes * (size_t)d->slots);
+    if (rc == HQ_OK && !c->perm.empty())                         /* perm[first .. first + count): the caller's id -> the device's */
+        rc = sn.d_map.put(&c->bytes, c->perm.data() + d->first, (size_t)d->count, c->stream);
     if (rc == HQ_OK && hipHostMalloc((void**)&sn.h_stage, sn.slot_bytes * (size_t)d->slots, hipHostMallocDefault) != hipSuccess) {
         sn.h_stage = nullptr;
         rc = hq_fail(HQ_ERR_NOMEM, "hipHostMalloc failed for the snapshot's pinned buffers%s", "");
@@ -887,18 +811,12 @@ extern "C" int hq_snapshot_add(hq_ctx* c, const hq_snapshot_desc* d, int32_t* ha
     sn.done.assign((size_t)d->slots, nullptr);
     for (int32_t k = 0; k < d->slots && rc == HQ_OK && e == hipSuccess; k++)
         e = hipEventCreateWithFlags(&sn.done[(size_t)k], hipEventDisableTiming);
-    if (rc == HQ_OK && e == hipSuccess && sn.d_map) {            /* perm[first .. first + count): the caller's id -> the device's */
-        e = hipMemcpy(sn.d_map, c->perm.data() + d->first, sizeof(int32_t) * (size_t)d->count, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  /* the steps read the map on other streams */
-    }
-    if (rc != HQ_OK || e != hipSuccess) {
+    if (rc != HQ_OK || e != hipSuccess) {                        /* (the device memory unwinds by scope) */
         hq_output_free(sn);
         if (!had_stream && c->sstream) { hipStreamDestroy(c->sstream); c->sstream = nullptr; }
-        c->bytes = bytes0;
         (void)hipGetLastError();
         return rc != HQ_OK ? rc : hq_fail(HQ_ERR_DEVICE, "hq_snapshot_add failed: %s", hipGetErrorString(e));
     }
-    sn.bytes = c->bytes - bytes0;
     if (sn.d_map) c->h2d_bytes += 4 * (int64_t)d->count;
     sn.open(d->rate, d->first_step, d->slots);
     sn.id = c->snap_next_id++;
@@ -964,7 +882,7 @@ extern "C" int hq_snapshot_clear(hq_ctx* c)
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
     HQ_HIP(hipStreamSynchronize(c->sstream));
-    hq_outputs_drop(c, c->snaps);
+    hq_outputs_drop(c->snaps);
     hipStreamDestroy(c->sstream); c->sstream = nullptr;   /* (the copy stream goes with the snapshots: here and in hq_destroy) */
     return HQ_OK;
 }

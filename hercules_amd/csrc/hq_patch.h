@@ -114,39 +114,37 @@ struct hq_patch_plan {
     int64_t nhalo = 0;
     int32_t hstride = 0;             /* ints between consecutive patches' halo id lists */
     int32_t ndistinct = 0, nuniform = 0;
-    hq_patch_desc* d_desc = nullptr;
-    uint4*   d_pidx = nullptr;
-    double*  d_pc1 = nullptr;
-    double*  d_pc2 = nullptr;
-    double*  d_pbeta = nullptr;
-    int32_t* d_halo = nullptr;
-    double*  d_nt3 = nullptr;        /* [N][3] {mass_simple, mass2_minusaM, mass_minusaM} for ISO patches */
+    hq_dbuf<hq_patch_desc> d_desc;
+    hq_dbuf<uint4>   d_pidx;
+    hq_dbuf<double>  d_pc1, d_pc2, d_pbeta;
+    hq_dbuf<int32_t> d_halo;
+    hq_dbuf<double>  d_nt3;          /* [N][3] {mass_simple, mass2_minusaM, mass_minusaM} for ISO patches */
     /* source entries grouped by patch (built by hq_patch_set_source) */
-    int32_t* d_src_ptr = nullptr;    /* [npatches + 1]                    */
-    int32_t* d_src_ent = nullptr;    /* [n][2] = {local node, loaded idx} */
+    hq_dbuf<int32_t> d_src_ptr;      /* [npatches + 1]                    */
+    hq_dbuf<int32_t> d_src_ent;      /* [n][2] = {local node, loaded idx} */
     /* partition-interface nodes grouped by owning patch (hq_patch_set_interface) */
-    int32_t* d_if_ptr = nullptr;     /* [npatches + 1]                    */
-    int32_t* d_if_ent = nullptr;     /* [n][2] = {local node, slot}       */
-    int32_t* d_order = nullptr;      /* patch ids: the nb interface patches first, then the rest */
-    int32_t* d_tickets = nullptr;    /* per XCD, HQ_TICKET_STRIDE ints apart: {next slot of hq_k_patch_pers' work queue, workgroups done} */
-    uint16_t* d_lat_row = nullptr;   /* [1024] LDS row of thread t's local node in a lattice patch             */
+    hq_dbuf<int32_t> d_if_ptr;       /* [npatches + 1]                    */
+    hq_dbuf<int32_t> d_if_ent;       /* [n][2] = {local node, slot}       */
+    hq_dbuf<int32_t> d_order;        /* patch ids: the nb interface patches first, then the rest */
+    hq_dbuf<int32_t> d_tickets;      /* per XCD, HQ_TICKET_STRIDE ints apart: {next slot of hq_k_patch_pers' work queue, workgroups done} */
+    hq_dbuf<uint16_t> d_lat_row;     /* [1024] LDS row of thread t's local node in a lattice patch             */
     int32_t  ne = 0, ns = 0, nr = 0; /* d_order = nb interface patches | ne other element-form patches | nr stencil patches with
                                       * interface nodes | ns other stencil patches */
     bool     ragged_default = false; /* set by the caller before hq_patch_build: what hq_options.patch_ragged = -1 means */
     int32_t  ns_rg = 0;              /* of the ns: ragged patches of <= 512 nodes, between the full lattices and the big ones */
     int32_t  nr_big = 0, ns_big = 0; /* of the nr / ns: patches of more than 512 owned nodes, at the end of their part */
     int32_t  nragged = 0, nstencil = 0;  /* STENCIL patches (nr + ns entries: two for a patch of more than 512 nodes), RAGGED ones among them */
-    uint32_t* d_rg_tab = nullptr;    /* tables of the stencil patches (hq_ragged_match), one per patch shape      */
+    hq_dbuf<uint32_t> d_rg_tab;      /* tables of the stencil patches (hq_ragged_match), one per patch shape      */
 #ifdef HQ_ST_TIMING
     bool timing_armed = false; unsigned long long* d_timing = nullptr;
 #endif
-    struct hq_st_desc* d_st_desc = nullptr;   /* [nr + ns] the stencil patches' records in launch order (hq_k_stencil_entries) */
-    int2*    d_st_halo = nullptr;    /* [nr + ns][512] (halo node, its LDS word) in launch order                        */
-    double*  d_pcoef = nullptr;      /* [P][4] c1, c2, beta of a stencil patch (beside the descriptor: no second hop)  */
-    int64_t* d_rg_off = nullptr;     /* [P] offset of a patch's table in d_rg_tab                                  */
-    double*  d_E1 = nullptr;         /* [576] element matrix blocks for (c1, c2) = (1, 0) ...                      */
-    double*  d_E2 = nullptr;         /* ... and (0, 1)                                                              */
-    int32_t* d_if_slot = nullptr;    /* [N] interface slot of a node or -1 (ragged patches on a partition)          */
+    hq_dbuf<struct hq_st_desc> d_st_desc;     /* [nr + ns] the stencil patches' records in launch order (hq_k_stencil_entries) */
+    hq_dbuf<int2> d_st_halo;         /* [nr + ns][512] (halo node, its LDS word) in launch order                        */
+    hq_dbuf<double> d_pcoef;         /* [P][4] c1, c2, beta of a stencil patch (beside the descriptor: no second hop)  */
+    hq_dbuf<int64_t> d_rg_off;       /* [P] offset of a patch's table in d_rg_tab                                  */
+    hq_dbuf<double> d_E1;            /* [576] element matrix blocks for (c1, c2) = (1, 0) ...                      */
+    hq_dbuf<double> d_E2;            /* ... and (0, 1)                                                              */
+    hq_dbuf<int32_t> d_if_slot;      /* [N] interface slot of a node or -1 (ragged patches on a partition)          */
     std::vector<int32_t> h_flags;    /* host copy of the patches' flags (hq_patch_set_interface edits them)     */
     int32_t  nlattice = 0;           /* lattice patches                                                        */
     int32_t  nrows = 0;              /* rows of hq_k_patch_pers' LDS image                                     */
@@ -156,8 +154,8 @@ struct hq_patch_plan {
     int32_t  pipe = 6;               /* hq_options.patch_pipe at plan time, or what hq_patch_build chose         */
     std::vector<char> patch_lat;     /* host copy of the lattice flags                                         */
     int32_t  nb = 0;
-    int32_t* d_ds_ptr = nullptr;     /* hanging-node force distribution (compute_adjust) per patch */
-    int32_t* d_ds_ent = nullptr;
+    hq_dbuf<int32_t> d_ds_ptr;       /* hanging-node force distribution (compute_adjust) per patch */
+    hq_dbuf<int32_t> d_ds_ent;
     int32_t  max_nown = 0, max_nhalo = 0, max_npairs = 0;
     int32_t  step_nl = 0;            /* rows of hq_k_patch_step's LDS image: max over patches of owned + halo nodes */
     std::vector<int32_t> h_halo;     /* host copies kept only for meshes with hanging nodes */
@@ -2103,11 +2101,7 @@ static void hq_patch_free(hq_patch_plan* P)
 #ifdef HQ_PATCH_PROFILING
     if (P->npatches) hq_patch_report_stamps(P);
 #endif
-    void* ptrs[] = { P->d_desc, P->d_pidx, P->d_pc1, P->d_pc2, P->d_pbeta, P->d_halo, P->d_src_ptr, P->d_src_ent,
-                     P->d_if_ptr, P->d_if_ent, P->d_order, P->d_nt3, P->d_ds_ptr, P->d_ds_ent, P->d_tickets, P->d_lat_row,
-                     P->d_rg_tab, P->d_rg_off, P->d_E1, P->d_E2, P->d_if_slot, P->d_pcoef, P->d_st_desc, P->d_st_halo };
-    for (void* p : ptrs) if (p) hipFree(p);
-    *P = hq_patch_plan();
+    *P = hq_patch_plan();            /* (the device arrays go with their owners) */
 }
 
 /*
@@ -2115,7 +2109,7 @@ static void hq_patch_free(hq_patch_plan* P)
  * nr stencil patches that own interface nodes | ns other stencil patches], each part in Z-order.
  * if_ptr (or null): CSR of the interface entries.
  */
-static int hq_patch_build_order(hq_patch_plan* P, const int32_t* if_ptr, int64_t* bytes)
+static int hq_patch_build_order(hq_patch_plan* P, const int32_t* if_ptr, int64_t* ledger, hipStream_t stream)
 {
     const int32_t np = P->npatches;
     std::vector<int32_t> order;
@@ -2147,35 +2141,31 @@ static int hq_patch_build_order(hq_patch_plan* P, const int32_t* if_ptr, int64_t
         P->nragged += (P->h_flags[p] & HQ_PATCH_RAGGED) != 0;
         P->nstencil += (P->h_flags[p] & HQ_PATCH_STENCIL) != 0;
     }
-    if (P->nb == 0 && P->ns == 0 && P->nr == 0) return 0;          /* identity order: no table */
-    if (!P->d_order) {
-        if (hipMalloc((void**)&P->d_order, 4 * (size_t)(np ? np : 1)) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-        *bytes += (int64_t)(4 * (size_t)np);
-    }
-    hipMemcpy(P->d_order, order.data(), 4 * order.size(), hipMemcpyHostToDevice);
+    if (P->nb == 0 && P->ns == 0 && P->nr == 0) return HQ_OK;      /* identity order: no table */
+    if (!P->d_order) HQ_TRY(P->d_order.alloc(ledger, (size_t)np));
+    HQ_TRY(P->d_order.upload(order.data(), order.size(), stream));
     if (P->nr + P->ns > 0) {                             /* the stencil part's records and halo entries in launch order */
         const size_t n = (size_t)(P->nr + P->ns);
         if (!P->d_st_desc) {
-            if (hipMalloc((void**)&P->d_st_desc, sizeof(hq_st_desc) * n) != hipSuccess ||
-                hipMalloc((void**)&P->d_st_halo, sizeof(int2) * HQ_ST_HSTRIDE * n) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-            *bytes += (int64_t)((sizeof(hq_st_desc) + sizeof(int2) * HQ_ST_HSTRIDE) * n);
+            HQ_TRY(P->d_st_desc.alloc(ledger, n));
+            HQ_TRY(P->d_st_halo.alloc(ledger, HQ_ST_HSTRIDE * n));
         }
-        hq_k_stencil_entries<<<(unsigned)n, HQ_ST_HSTRIDE>>>((int32_t)n, P->d_order + P->nb + P->ne, P->d_desc, P->d_pcoef,
-                                                             P->d_rg_off, P->d_rg_tab, P->d_halo, P->hstride, P->d_st_desc,
-                                                             P->d_st_halo);
-        if (hipDeviceSynchronize() != hipSuccess) { g_patch_err = "building the stencil entries failed"; return -3; }
+        hq_k_stencil_entries<<<(unsigned)n, HQ_ST_HSTRIDE, 0, stream>>>((int32_t)n, P->d_order + P->nb + P->ne, P->d_desc, P->d_pcoef,
+                                                                    P->d_rg_off, P->d_rg_tab, P->d_halo, P->hstride, P->d_st_desc,
+                                                                    P->d_st_halo);
+        if (hipStreamSynchronize(stream) != hipSuccess) return hq_fail(HQ_ERR_DEVICE, "building the stencil entries failed%s", "");
     }
 #ifdef HQ_ST_TIMING
     if (!P->timing_armed) hq_st_timing_report(P);
 #endif
-    return 0;
+    return HQ_OK;
 }
 
 static bool hq_patch_uses_pers(const hq_patch_plan* P);
 
 static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int64_t N, const int32_t* lnid, const int32_t* xyz,
                           const double* c1, const double* c2, const double* beta, const double* ntab,
-                          const hq_dangling& dn, const char* seed0, int64_t* bytes, int64_t n0 = 0)
+                          const hq_dangling& dn, const char* seed0, int64_t* ledger, hipStream_t st, int64_t n0 = 0)
 {
     hq_patch_host H;
     const bool plap_on = o.verbose > 1;
@@ -2202,7 +2192,8 @@ static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int6
     want_lattice = want_lattice && pers_fits(std::max(P->cfg.nlmax, HQ_LAT_ROWS), 0);
     std::vector<int32_t> cand;                       /* the shell's elements: found once, used by every plan below */
     for (;;) {
-        if (hq_patch_plan_host(o, P->cfg, E, N, lnid, xyz, dn, want_lattice, &H, n0, &cand) != 0) return -1 /* HQ_ERR_ARG */;
+        if (hq_patch_plan_host(o, P->cfg, E, N, lnid, xyz, dn, want_lattice, &H, n0, &cand) != 0)
+            return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
         /* behind bricks the patches are the shell of the mesh -- a few thousand, 15 per CU on the 64M box: the
          * persistent kernels' prologue and work queue cost more than they save there, and one workgroup per patch
          * (hq_k_patch_step, two per CU) fills the device at once: 64M box 1.104 -> 1.060 ms per step, 8M box
@@ -2334,49 +2325,30 @@ static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int6
     P->npairs = (int64_t)H.pelem.size();
     P->nhalo = (int64_t)H.halo.size();
     P->hstride = H.hstride;
-    std::vector<double> v((size_t)P->npairs);
-    size_t np = (size_t)P->npairs ? (size_t)P->npairs : 1, nh = H.halo.size() ? H.halo.size() : 1;
-#define HQ_PA(ptr, bytes_)                                                                   \
-    if (hipMalloc((void**)&(ptr), (bytes_)) != hipSuccess) { g_patch_err = "hipMalloc failed"; hq_patch_free(P); return -2; } \
-    *bytes += (int64_t)(bytes_);
-    HQ_PA(P->d_desc, sizeof(hq_patch_desc) * H.desc.size())
-    HQ_PA(P->d_pidx, 16 * np)
-    HQ_PA(P->d_pc1, 8 * np)
-    HQ_PA(P->d_pc2, 8 * np)
-    HQ_PA(P->d_pbeta, 8 * np)
-    HQ_PA(P->d_halo, 4 * nh)
-    HQ_PA(P->d_nt3, 8 * nt3.size())
-    HQ_PA(P->d_tickets, 4 * 8 * HQ_TICKET_STRIDE)
-    hipMemset(P->d_tickets, 0, 4 * 8 * HQ_TICKET_STRIDE);
-    if (P->nlattice) {
-        HQ_PA(P->d_lat_row, sizeof(uint16_t) * 1024)
-        hipMemcpy(P->d_lat_row, hq_lattice().row_of_local, sizeof(uint16_t) * 1024, hipMemcpyHostToDevice);
-    }
+    /* every table on the compute stream and waited for: a failure unwinds by scope (hq_patch_free by the caller) */
+    HQ_TRY(P->d_desc.put(ledger, H.desc, st));
+    HQ_TRY(P->d_pidx.put(ledger, (const uint4*)H.pidx.data(), (size_t)P->npairs, st));   /* eight 16-bit local ids per pair */
+    HQ_TRY(P->d_halo.put(ledger, H.halo, st));
+    HQ_TRY(P->d_nt3.put(ledger, nt3, st));
+    HQ_TRY(P->d_tickets.alloc(ledger, 8 * HQ_TICKET_STRIDE));
+    HQ_TRY(P->d_tickets.fill(0, st));
+    if (P->nlattice) HQ_TRY(P->d_lat_row.put(ledger, hq_lattice().row_of_local, 1024, st));
     if (!rg_tab.empty()) {
-        HQ_PA(P->d_rg_tab, sizeof(uint32_t) * rg_tab.size())
-        HQ_PA(P->d_rg_off, sizeof(int64_t) * rg_off.size())
-        {
-            std::vector<double> pco(4 * H.desc.size(), 0.0);
-            for (size_t q = 0; q < H.desc.size(); q++)
-                if (H.desc[q].flags & HQ_PATCH_STENCIL) {
-                    const int32_t e0 = H.pelem[(size_t)H.desc[q].pair_off];
-                    pco[4 * q] = c1[e0]; pco[4 * q + 1] = c2[e0]; pco[4 * q + 2] = beta[e0];
-                }
-            HQ_PA(P->d_pcoef, sizeof(double) * pco.size())
-            hipMemcpy(P->d_pcoef, pco.data(), sizeof(double) * pco.size(), hipMemcpyHostToDevice);
-        }
-        HQ_PA(P->d_E1, sizeof(double) * 576)
-        HQ_PA(P->d_E2, sizeof(double) * 576)
-        hipMemcpy(P->d_rg_tab, rg_tab.data(), sizeof(uint32_t) * rg_tab.size(), hipMemcpyHostToDevice);
-        hipMemcpy(P->d_rg_off, rg_off.data(), sizeof(int64_t) * rg_off.size(), hipMemcpyHostToDevice);
-        hipMemcpy(P->d_E1, hq_stencil().E1, sizeof(double) * 576, hipMemcpyHostToDevice);
-        hipMemcpy(P->d_E2, hq_stencil().E2, sizeof(double) * 576, hipMemcpyHostToDevice);
+        std::vector<double> pco(4 * H.desc.size(), 0.0);
+        for (size_t q = 0; q < H.desc.size(); q++)
+            if (H.desc[q].flags & HQ_PATCH_STENCIL) {
+                const int32_t e0 = H.pelem[(size_t)H.desc[q].pair_off];
+                pco[4 * q] = c1[e0]; pco[4 * q + 1] = c2[e0]; pco[4 * q + 2] = beta[e0];
+            }
+        HQ_TRY(P->d_pcoef.put(ledger, pco, st));
+        HQ_TRY(P->d_rg_tab.put(ledger, rg_tab, st));
+        HQ_TRY(P->d_rg_off.put(ledger, rg_off, st));
+        HQ_TRY(P->d_E1.put(ledger, hq_stencil().E1, 576, st));
+        HQ_TRY(P->d_E2.put(ledger, hq_stencil().E2, 576, st));
     }
     if (dn.n > 0) {
-        HQ_PA(P->d_ds_ptr, 4 * H.ds_ptr.size())
-        HQ_PA(P->d_ds_ent, 4 * (H.ds_ent.size() ? H.ds_ent.size() : 1))
-        hipMemcpy(P->d_ds_ptr, H.ds_ptr.data(), 4 * H.ds_ptr.size(), hipMemcpyHostToDevice);
-        hipMemcpy(P->d_ds_ent, H.ds_ent.data(), 4 * H.ds_ent.size(), hipMemcpyHostToDevice);
+        HQ_TRY(P->d_ds_ptr.put(ledger, H.ds_ptr, st));
+        HQ_TRY(P->d_ds_ent.put(ledger, H.ds_ent, st));
         P->h_halo = H.halo;
         P->h_halo_off.resize(H.desc.size());
         P->h_nvirt.resize(H.desc.size());
@@ -2385,16 +2357,12 @@ static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int6
             P->h_nvirt[p] = H.desc[p].nacc - H.desc[p].nown;
         }
     }
-#undef HQ_PA
-    hipMemcpy(P->d_nt3, nt3.data(), 8 * nt3.size(), hipMemcpyHostToDevice);
-    hipMemcpy(P->d_desc, H.desc.data(), sizeof(hq_patch_desc) * H.desc.size(), hipMemcpyHostToDevice);
-    hipMemcpy(P->d_pidx, H.pidx.data(), 16 * (size_t)P->npairs, hipMemcpyHostToDevice);
-    hipMemcpy(P->d_halo, H.halo.data(), 4 * H.halo.size(), hipMemcpyHostToDevice);
     const double* src[3] = { c1, c2, beta };
-    double* dst[3] = { P->d_pc1, P->d_pc2, P->d_pbeta };
+    hq_dbuf<double>* dst[3] = { &P->d_pc1, &P->d_pc2, &P->d_pbeta };
+    std::vector<double> v((size_t)P->npairs);
     for (int k = 0; k < 3; k++) {
         for (int64_t q = 0; q < P->npairs; q++) v[(size_t)q] = src[k][H.pelem[(size_t)q]];
-        hipMemcpy(dst[k], v.data(), 8 * (size_t)P->npairs, hipMemcpyHostToDevice);
+        HQ_TRY(dst[k]->put(ledger, v, st));
     }
     for (auto& D : H.desc) {
         P->max_nown = std::max(P->max_nown, D.nown);
@@ -2404,17 +2372,18 @@ static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int6
     P->patch_base.resize(H.desc.size());
     P->patch_nown.resize(H.desc.size());
     for (size_t p = 0; p < H.desc.size(); p++) { P->patch_base[p] = H.desc[p].base; P->patch_nown[p] = H.desc[p].nown; }
-    if (hq_patch_build_order(P, nullptr, bytes) != 0) return -2;
+    HQ_TRY(hq_patch_build_order(P, nullptr, ledger, st));
     plap("uploads");
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    HQ_HIP(hipGetLastError());
+    return HQ_OK;
 }
 
 /* group the loaded nodes (Global.theNodesLoadedList, psolve.c:5917-5918) by owning patch */
-static int hq_patch_set_source(hq_patch_plan* P, int32_t nloaded, const int32_t* loaded, int64_t* bytes)
+static int hq_patch_set_source(hq_patch_plan* P, int32_t nloaded, const int32_t* loaded, int64_t* ledger, hipStream_t st)
 {
-    if (P->d_src_ptr) { hipFree(P->d_src_ptr); P->d_src_ptr = nullptr; }
-    if (P->d_src_ent) { hipFree(P->d_src_ent); P->d_src_ent = nullptr; }
-    if (nloaded <= 0) return 0;
+    P->d_src_ptr.reset();
+    P->d_src_ent.reset();
+    if (nloaded <= 0) return HQ_OK;
     /* (patch, local accumulator, loaded index): the owning patch, plus every patch that keeps a
      * "virtual" accumulator of a loaded hanging node (its force is distributed to their anchors) */
     std::vector<std::array<int32_t, 3>> rec;
@@ -2436,16 +2405,12 @@ static int hq_patch_set_source(hq_patch_plan* P, int32_t nloaded, const int32_t*
     for (auto& r : rec) ptr[r[0] + 1]++;
     for (int32_t p = 0; p < P->npatches; p++) ptr[p + 1] += ptr[p];
     for (size_t k = 0; k < rec.size(); k++) { ent[2 * k] = rec[k][1]; ent[2 * k + 1] = rec[k][2]; }
-    if (hipMalloc((void**)&P->d_src_ptr, 4 * ptr.size()) != hipSuccess) return -2;
-    if (hipMalloc((void**)&P->d_src_ent, 4 * ent.size()) != hipSuccess) return -2;
-    *bytes += (int64_t)(4 * ptr.size() + 4 * ent.size());
-    hipMemcpy(P->d_src_ptr, ptr.data(), 4 * ptr.size(), hipMemcpyHostToDevice);
-    hipMemcpy(P->d_src_ent, ent.data(), 4 * ent.size(), hipMemcpyHostToDevice);
-    return 0;
+    HQ_TRY(P->d_src_ptr.put(ledger, ptr, st));
+    return P->d_src_ent.put(ledger, ent, st);
 }
 
 /* slot[n] >= 0 for nodes on the partition interface */
-static int hq_patch_set_interface(const hq_options& o, hq_patch_plan* P, const int32_t* slot, int64_t nnodes, int64_t* bytes)
+static int hq_patch_set_interface(const hq_options& o, hq_patch_plan* P, const int32_t* slot, int64_t nnodes, int64_t* ledger, hipStream_t st)
 {
     std::vector<int32_t> ptr((size_t)P->npatches + 1, 0), ent;
     for (int32_t p = 0; p < P->npatches; p++) {
@@ -2455,7 +2420,7 @@ static int hq_patch_set_interface(const hq_options& o, hq_patch_plan* P, const i
         }
         ptr[p + 1] = (int32_t)(ent.size() / 2);
     }
-    if (ent.empty()) return 0;
+    if (ent.empty()) return HQ_OK;
     /* launch order: patches owning interface nodes first, so their partial forces can travel while the rest of
      * the partition is still being computed; they hand partial forces on, so they take the element form */
     bool any_st_if = false;
@@ -2465,19 +2430,11 @@ static int hq_patch_set_interface(const hq_options& o, hq_patch_plan* P, const i
             P->h_flags[p] |= HQ_PATCH_RAGGED;                /* hands partial forces on: launched ahead of the exchange */
             any_st_if = true;
         }
-    if (P->d_if_slot) { hipFree(P->d_if_slot); P->d_if_slot = nullptr; }
-    if (any_st_if) {
-        if (hipMalloc((void**)&P->d_if_slot, 4 * (size_t)nnodes) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-        *bytes += (int64_t)(4 * (size_t)nnodes);
-        hipMemcpy(P->d_if_slot, slot, 4 * (size_t)nnodes, hipMemcpyHostToDevice);
-    }
-    if (hq_patch_build_order(P, ptr.data(), bytes) != 0) return -2;
-    if (hipMalloc((void**)&P->d_if_ptr, 4 * ptr.size()) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-    if (hipMalloc((void**)&P->d_if_ent, 4 * ent.size()) != hipSuccess) { g_patch_err = "hipMalloc failed"; return -2; }
-    *bytes += (int64_t)(4 * ptr.size() + 4 * ent.size());
-    hipMemcpy(P->d_if_ptr, ptr.data(), 4 * ptr.size(), hipMemcpyHostToDevice);
-    hipMemcpy(P->d_if_ent, ent.data(), 4 * ent.size(), hipMemcpyHostToDevice);
-    return 0;
+    P->d_if_slot.reset();
+    if (any_st_if) HQ_TRY(P->d_if_slot.put(ledger, slot, (size_t)nnodes, st));
+    HQ_TRY(hq_patch_build_order(P, ptr.data(), ledger, st));
+    HQ_TRY(P->d_if_ptr.put(ledger, ptr, st));
+    return P->d_if_ent.put(ledger, ent, st);
 }
 
 #ifdef HQ_PATCH_PROFILING

@@ -341,7 +341,8 @@ def test_every_rank_loads_all_its_harbored_nodes(kind, variant, overlap):
 @pytest.mark.parametrize("mesh,options", [("box32x32x16", None), ("two_level", {"no_bricks": 1})], ids=["bricks", "patches-only"])
 def test_source_windows_same_nodes_rebuilds_subsets_and_the_empty_list(mesh, options):
     """hq_set_source(ids, F, step0) stage by stage, the oracle stepped along on the same state with each stage's table
-    zero-padded to the whole run (its rows are indexed by the absolute step)."""
+    zero-padded to the whole run (its rows are indexed by the absolute step).  hq_info.device_bytes follows the tables: a
+    repeated call leaves it unchanged, a subset reports less, the empty list gives back all a source ever took."""
     p = _mesh(mesh)
     N, dt = p["N"], p["dt"]
     total = 40
@@ -366,6 +367,7 @@ def test_source_windows_same_nodes_rebuilds_subsets_and_the_empty_list(mesh, opt
         assert e1 < TOL_RUN and e2 < TOL_RUN, (what, e1, e2)
 
     try:
+        bytes0 = s.info()["device_bytes"]
         # 1. a window that opens at step 2: the steps before it apply nothing
         F = rows(3, 100)
         s.set_source(every, F, step0=2)
@@ -389,15 +391,25 @@ def test_source_windows_same_nodes_rebuilds_subsets_and_the_empty_list(mesh, opt
         perm = np.random.default_rng(5).permutation(N)
         F = rows(3, 400)
         s.set_source(every[perm], F[:, perm], step0=17)
+        bytes5 = s.info()["device_bytes"]
+        s.set_source(every[perm], F[:, perm], step0=17)      # the same call again: nothing more is held
+        assert s.info()["device_bytes"] == bytes5 > bytes0
         advance(4, every, F, 17, "permuted list")
         # 6. a proper subset
         sub = every[::3]
         F = rows(3, 500)[:, sub]
         s.set_source(sub, F, step0=22)
+        bytes6 = s.info()["device_bytes"]
+        assert bytes0 < bytes6 < bytes5
+        s.set_source(sub[::-1], F[:, ::-1], step0=22)        # other ids: every table is rebuilt, the old ones are given back
+        assert s.info()["device_bytes"] == bytes6
+        s.set_source(sub, F, step0=22)
+        assert s.info()["device_bytes"] == bytes6
         advance(5, sub, F, 22, "subset")
         # 7. the empty list: the run goes on unforced
         s.set_source(np.zeros(0, np.int32), np.zeros((0, 0, 3)))
         advance(3, np.zeros(0, np.int32), np.zeros((0, 0, 3)), 0, "empty list")
+        assert s.info()["device_bytes"] == bytes0
         assert s.check_finite() == 0
     finally:
         s.close()
