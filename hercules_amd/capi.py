@@ -626,7 +626,8 @@ def stencil_plan_check(desc):
 
 
 BRICK_PLAN_REPORT = ("brick_nodes", "columns", "units", "units_one_nt_row", "het_units", "neighbours_checked",
-                     "patch_nodes", "faults", "ragged_units", "ragged_nodes", "ragged_het_units", "ragged_het_nodes", "packed_units")
+                     "patch_nodes", "faults", "ragged_units", "ragged_nodes", "ragged_het_units", "ragged_het_nodes", "packed_units",
+                     "min_unit_nx", "min_unit_ny", "min_unit_np", "ragged_min_plane_nodes", "units_one_plane_both_faces")
 
 
 def brick_plan_check(desc):

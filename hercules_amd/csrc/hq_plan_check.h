@@ -232,13 +232,16 @@ extern "C" int hq_stencil_plan_check(const hq_desc* d, int64_t report[6])
  * the unit, an entry of the unit's ring table or of its first / last plane's id list.
  * report = {brick nodes, tile columns, units, units with one n_t row, levels, neighbours checked, patch nodes, faults,
  *           ragged units (HQ_BK_RAGGED), the nodes they own, ragged HET units, the nodes they own,
- *           HET units in the packed form (HQ_BK_PACKED), ragged ones included}
+ *           HET units in the packed form (HQ_BK_PACKED), ragged ones included,
+ *           the smallest nx, ny and np of any unit, the fewest nodes a ragged unit (of either kernel) owns in one of its
+ *           planes (0: no ragged unit), units of ONE plane that carry both z faces}
  */
-static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[13])
+#define HQ_BRICK_REPORT_N 18
+static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[HQ_BRICK_REPORT_N])
 {
     hq_options opts;                                  /* host-only diagnostic: the library defaults, the environment where HQ_ALLOW_ENV=1 */
     hq_options_resolve(&opts, nullptr);
-    for (int k = 0; k < 13; k++) report[k] = 0;
+    for (int k = 0; k < HQ_BRICK_REPORT_N; k++) report[k] = 0;
     if (!d || !d->node_xyz || !d->eTable || !d->nTable)
         return hq_fail(HQ_ERR_ARG, "inconsistent mesh description (node_xyz is needed)%s", "");
     hq_prep prep;
@@ -449,10 +452,20 @@ static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[13])
     report[0] = B.nb; report[1] = B.ncolumns; report[2] = (int64_t)B.units.size(); report[3] = nsame;
     report[4] = B.nhet + B.nrhet; report[5] = nchecked; report[6] = N - B.nb; report[7] = bad;
     report[8] = B.nrag; report[10] = B.nrhet; report[12] = B.npacked + B.nrpacked;
+    report[13] = report[14] = report[15] = INT64_MAX;
     for (const hq_brick_unit& U : B.units) {
+        report[13] = std::min<int64_t>(report[13], U.nx); report[14] = std::min<int64_t>(report[14], U.ny);
+        report[15] = std::min<int64_t>(report[15], U.np);
+        report[17] += U.np == 1 && (U.flags & HQ_BK_TOPFACE) && (U.flags & HQ_BK_BOTFACE);
         if (!(U.flags & HQ_BK_RAGGED)) continue;
+        const int64_t nxy = (int64_t)U.nx * U.ny;
         const int32_t* pl = B.tab.data() + U.tab + (int64_t)(U.np + 2) * (2 * (U.nx + 2) + 2 * U.ny);
-        for (int64_t i = (int64_t)U.nx * U.ny; i < (int64_t)U.nx * U.ny * (U.np + 1); i++) report[(U.flags & HQ_BK_HET) ? 11 : 9] += pl[i] >= 0;
+        for (int64_t k = 1; k <= U.np; k++) {            /* (planes 0 and np + 1 of the table are the caps: never owned) */
+            int64_t own = 0;
+            for (int64_t i = k * nxy; i < (k + 1) * nxy; i++) own += pl[i] >= 0;
+            report[(U.flags & HQ_BK_HET) ? 11 : 9] += own;
+            report[16] = report[16] ? std::min(report[16], own) : own;
+        }
     }
     if (bad) return hq_fail(HQ_ERR_STATE, "brick plan self-check failed%s", "");
     return HQ_OK;
@@ -460,13 +473,13 @@ static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[13])
 
 extern "C" int hq_brick_plan_check(const hq_desc* d, int64_t report[8]) { return hq_brick_plan_check_n(d, report, 8); }
 
-/* the same with a longer report (entries 8 .. 12 above); n = entries the caller has, those past 13 are zeroed */
+/* the same with a longer report (entries 8 .. 17 above); n = entries the caller has, those past 18 are zeroed */
 extern "C" int hq_brick_plan_check_n(const hq_desc* d, int64_t* report, int32_t n)
 {
-    int64_t r13[13];
+    int64_t r[HQ_BRICK_REPORT_N];
     if (!report || n < 8) return hq_fail(HQ_ERR_ARG, "hq_brick_plan_check_n: a report of at least 8 entries%s", "");
-    const int rc = hq_brick_plan_check_impl(d, r13);
-    for (int k = 0; k < n; k++) report[k] = k < 13 ? r13[k] : 0;
+    const int rc = hq_brick_plan_check_impl(d, r);
+    for (int k = 0; k < n; k++) report[k] = k < HQ_BRICK_REPORT_N ? r[k] : 0;
     return rc;
 }
 

@@ -657,7 +657,10 @@ HQ_API int hq_stencil_plan_check(const hq_desc* desc, int64_t report[6]);
 HQ_API int hq_brick_plan_check(const hq_desc* desc, int64_t report[8]);
 /* ... with report[8] = units that own only part of their tile (ragged, one n_t row), report[9] = the nodes those own,
  * report[10] / [11] = the same for the ragged units of the per-element kernel, report[12] = the per-element units kept in
- * the packed form (desc->edata given and every coefficient reproduced bit for bit), ragged ones included; n >= 8 entries */
+ * the packed form (desc->edata given and every coefficient reproduced bit for bit), ragged ones included,
+ * report[13] / [14] / [15] = the smallest nx, ny and np (planes) of any unit, report[16] = the fewest nodes a ragged unit
+ * of either kernel owns in one of its planes (0: there is no ragged unit), report[17] = units of ONE plane that carry
+ * both z faces; n >= 8 entries, those past the last one named here are zeroed */
 HQ_API int hq_brick_plan_check_n(const hq_desc* desc, int64_t* report, int32_t n);
 
 /*

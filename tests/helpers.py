@@ -1,6 +1,7 @@
 """Shared set-up of the reference's examples/simple case (C1) from the golden
 fixtures: mesh in octor order, eTable/nTable from the oracle's solver_init."""
 import os
+import re
 
 import numpy as np
 
@@ -269,7 +270,10 @@ def source_mesh(name, damping="rayleigh"):
     tests/test_sources_oracle_cpu.py for the oracle's side and the planner's counters), built once: the smallest ones
     the suite reaches each kernel with.  -> dict(lnid, etable, ntable, dt, dangling, N, node_xyz[, box | edata, material])
     het70x20x12 (box70x20x12's geometry) and c5_gradient_branch (c5_gradient's) carry branch_materials per element,
-    labels included, with the tables of the damping kind (rayleigh, mass, none) at step_mesh's time step."""
+    labels included, with the tables of the damping kind (rayleigh, mass, none) at step_mesh's time step; the edge...,
+    hetedge... and two...s.. boxes of edge_mesh() as they are."""
+    if is_edge_mesh(name):
+        return edge_mesh(name, damping)
     if name in ("het70x20x12", "c5_gradient_branch"):
         if (name, damping) not in _SOURCE_MESHES:
             _SOURCE_MESHES[(name, damping)] = _branch_mesh(name, damping)
@@ -466,6 +470,59 @@ def _branch_mesh(name, damping):
                 labels=labels, damping=damping, raw_edata=raw)
 
 
+# ---------------------------------------------------------------------------------------------
+# boxes whose extents leave the brick planner degenerate units (tests/test_brick_edges_cpu.py, tests/test_gpu_brick_edges.py)
+# ---------------------------------------------------------------------------------------------
+_EDGE_NAME = re.compile(r"^(edge|hetedge|two)(\d+)x(\d+)x(\d+)(?:s(\d+))?$")
+_EDGE_SEEDS = {"hetedge65x9x8": 7101, "hetedge64x9x36": 7102, "hetedge3x9x8": 7103}
+_EDGE_MESHES = {}
+
+
+def is_edge_mesh(name):
+    return _EDGE_NAME.match(name) is not None
+
+
+def edge_mesh(name, damping="rayleigh"):
+    """A box of nx x ny x nz elements (h = 62.5) named for the footprints its interior leaves on the planner's tile grid --
+    (nx - 1) mod 64 == 1 gives a column ONE node wide, (ny - 1) mod 8 == 1 a row one node deep, (nz - 1) mod cz == 1 a unit
+    of one plane; 62 and 7 for the per-element kernel's tiles:
+      edgeAxBxC      one material (hq_k_brick), like uniform_box
+      hetedgeAxBxC   branch_materials per element (hq_k_brick_het), like het70x20x12; edata / material for the packed form
+      twoAxBxCsS     the soft material in the element columns i < S, the hard one beyond (two_material_leaves' recipe):
+                     the tile that straddles i = S is ragged, the nodes of the plane x = S are per-element ones
+    dt at a quarter of the stiffest element's CFL square (the step meshes' rule), tables of the damping kind (edge / two:
+    rayleigh).  Built once.  -> dict like step_mesh's, with shape, node_ijk, elem_ijk."""
+    key = (name, damping)
+    if key in _EDGE_MESHES:
+        return _EDGE_MESHES[key]
+    m = _EDGE_NAME.match(name)
+    family, (nx, ny, nz), split = m.group(1), [int(v) for v in m.group(2, 3, 4)], m.group(5)
+    assert (family == "two") == (split is not None), name
+    h, freq = 62.5, 5.0
+    elem_ijk, lnid, node_ijk = ho.uniform_mesh(nx, ny, nz)
+    face, N = ho.face_bits(elem_ijk, nx, ny, nz), len(node_ijk)
+    xyz = (np.asarray(node_ijk, np.int64) * (1 << 20)).astype(np.int32)
+    common = dict(lnid=lnid, dangling=None, N=N, E=len(lnid), shape=(nx, ny, nz), node_xyz=xyz, node_ijk=np.asarray(node_ijk),
+                  elem_ijk=np.asarray(elem_ijk), damping=damping)
+    if family == "hetedge":
+        edata, et, nt, dt, labels, material, raw = _branch_tables(lnid, h, face, N, _EDGE_SEEDS[name], damping, freq)
+        p = dict(common, etable=et, ntable=nt, dt=dt, edata=edata, material=material, labels=labels, raw_edata=raw)
+    else:
+        assert damping == "rayleigh"
+        edata = np.empty((len(lnid), 4), np.float32)
+        edata[:] = (h, 6000.0, 3464.0, 2700.0)
+        if split is not None:
+            assert 0 < int(split) < nx
+            edata[np.asarray(elem_ijk)[:, 0] < int(split)] = (h, 3000.0, 1732.0, 2200.0)
+        dt = _quarter_cfl_dt(edata)
+        raw = edata.copy()
+        et, nt = ho.solver_init(lnid, edata, face, N, dt, freq)
+        assert np.array_equal(edata, raw)                          # plain materials: solver_init rewrites nothing
+        p = dict(common, etable=et, ntable=nt, dt=dt, edata=edata, material=(ho.setab(freq, ho.DAMP_RAYLEIGH)[1], 0.05, 3.0))
+    _EDGE_MESHES[key] = p
+    return p
+
+
 _STEP_MESHES = {}
 
 
@@ -476,7 +533,9 @@ def step_mesh(name, damping="rayleigh"):
     if key in _STEP_MESHES:
         return _STEP_MESHES[key]
     kind = ho.DAMPING_BY_NAME[damping]
-    if name in ("het70x20x12", "c5_gradient_branch"):
+    if is_edge_mesh(name):
+        p = edge_mesh(name, damping)
+    elif name in ("het70x20x12", "c5_gradient_branch"):
         p = source_mesh(name, damping)
     elif name in ("box32x32x16", "box70x20x12", "box32"):
         assert damping == "rayleigh"

@@ -223,7 +223,12 @@ def _worst(err, scale, mask):
 
 @pytest.mark.parametrize("case,phase", PARAMS, ids=["%s-%s" % kp for kp in PARAMS])
 def test_one_step_from_rest_with_every_node_loaded(case, phase):
-    c = CASES[case]
+    one_step_from_rest(case, CASES[case], phase)
+
+
+def one_step_from_rest(case, c, phase):
+    """A. for one case (a _case(...) on a tests/helpers.source_mesh): shared with tests/test_gpu_brick_edges.py, whose
+    meshes put the same criterion on degenerate brick units."""
     p = _mesh(c["mesh"])
     f32 = c["precision"] == "f32"
     loaded, F, ref = _reference(c["mesh"], phase, c["precision"])

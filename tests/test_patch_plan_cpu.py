@@ -356,13 +356,19 @@ def test_the_two_brick_reports_agree():
     assert list(r8) == list(r12)[:8] and r12[8] > 0 and r12[9] > 0
     b = host.Box(16, 16, 16, 10.0, 2e-4, 50.0)
     d = _desc_of(b)
-    r16 = (ctypes.c_int64 * 16)(*([-7] * 16))
-    capi._check(lib.hq_brick_plan_check_n(ctypes.byref(d), r16, ctypes.c_int32(16)))
+    nrep = len(capi.BRICK_PLAN_REPORT)
+    r13, r22 = (ctypes.c_int64 * 13)(*([-7] * 13)), (ctypes.c_int64 * (nrep + 4))(*([-7] * (nrep + 4)))
+    capi._check(lib.hq_brick_plan_check_n(ctypes.byref(d), r13, ctypes.c_int32(13)))
+    capi._check(lib.hq_brick_plan_check_n(ctypes.byref(d), r22, ctypes.c_int32(nrep + 4)))
     b.close()
-    rep = dict(zip(capi.BRICK_PLAN_REPORT, list(r16)))
+    rep = dict(zip(capi.BRICK_PLAN_REPORT, list(r22)))
     assert rep["brick_nodes"] > 0 and rep["faults"] == 0
     assert rep["ragged_units"] == rep["ragged_nodes"] == rep["ragged_het_units"] == rep["ragged_het_nodes"] == 0
-    assert list(r16)[12:] == [0, 0, 0, 0]
+    # a caller of the thirteen-entry report gets what it always got; the entries past the last named one are zeroed
+    assert list(r13) == list(r22)[:13] and r22[12] == 0 and list(r22)[nrep:] == [0, 0, 0, 0]
+    # the unit extents (15 x 8 and 15 x 7 footprints on this box), no ragged unit, no one-plane unit with both faces
+    assert (rep["min_unit_nx"], rep["min_unit_ny"]) == (15, 7) and rep["min_unit_np"] >= 1
+    assert rep["ragged_min_plane_nodes"] == 0 and rep["units_one_plane_both_faces"] == 0
 
 
 def test_plan_check_needs_no_element_or_node_tables():

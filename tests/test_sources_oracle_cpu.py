@@ -21,7 +21,13 @@ def _two_level():
     return H.source_mesh("two_level")
 
 
-@pytest.mark.parametrize("mesh", [_uniform, _two_level], ids=["uniform", "two_level"])
+def _edge(name):
+    return lambda: H.source_mesh(name)
+
+
+# (edge66x10x2, hetedge65x9x8: the degenerate-footprint meshes tests/test_gpu_brick_edges.py loads on every node)
+@pytest.mark.parametrize("mesh", [_uniform, _two_level, _edge("edge66x10x2"), _edge("hetedge65x9x8")],
+                         ids=["uniform", "two_level", "edge66x10x2", "hetedge65x9x8"])
 def test_a_plain_loaded_node_is_its_force_over_its_mass_bit_for_bit(mesh):
     """Every node loaded (hanging ones too, where there are any): at every node that is neither hanging nor an anchor --
     dashpot faces included, their n_t rows differ per axis but column 0 is the divisor -- u(1) == F * dt^2 / n_t[n][0],
