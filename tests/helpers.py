@@ -311,13 +311,17 @@ def source_mesh(name, damping="rayleigh"):
     return p
 
 
-def solver_desc(p, pack=False):
+def solver_desc(p, pack=False, precision="f64"):
     """hq_desc (capi._Desc) of a source_mesh() for the host-only plan checks (capi.brick_plan_check, plan_check,
     stencil_plan_check); the arrays it points to are kept alive on the returned object.  pack: with p's edata and
-    material (hq_desc.edata / mat_*), as a context that may pack its per-element units gets them."""
+    material (hq_desc.edata / mat_*), as a context that may pack its per-element units gets them.  precision "f32": the
+    n_t rows rounded to float and widened again, as the float library's planners see them (hq_prepare.h)."""
     import ctypes
     from hercules_amd import capi
     d = capi._Desc()
+    if precision == "f32":
+        assert "box" not in p
+        p = dict(p, ntable=np.ascontiguousarray(p["ntable"], np.float32).astype(np.float64))
     if "box" in p:
         fill = p["box"]._lib.hqh_octbox_desc if hasattr(p["box"], "gid") else p["box"]._lib.hqh_box_desc
         assert fill(p["box"]._h, ctypes.byref(d)) == 0

@@ -10,7 +10,11 @@ whose plans, cases, fields, reference and bound are the ones used here).
    B_oracle, printed, at most 64 (tests/test_gpu_step_terms.bound_factor); no value is fixed in advance.
 3. The criterion sees a wrong ring or exchange value where these meshes put one: u1 of the single node of the 1 x 1
    column's middle plane (of one node of the 62 x 1 row) scaled by 1 + 1e-9 exceeds the device bound at that node and its
-   26 neighbours, and nowhere else."""
+   26 neighbours, and nowhere else.
+4. The float cases: their plans on n_t rows rounded to float are the pinned ones, except that per-element units pack only
+   without damping; and the criterion of a float state (tests/test_gpu_step_terms.rounded_step: one step = float32(double
+   step)) is met by the rounded double oracle on every mesh and damping kind of those cases, undetermined components
+   printed and under the cap (1 of 30 261 on edge130x10x6, 1 of 72 150 on hetedge64x9x36, 0 elsewhere)."""
 import numpy as np
 import pytest
 
@@ -129,6 +133,39 @@ def test_float_oracle_step_against_the_extended_reference(mesh, damping):
     assert nt.dtype == u1.dtype == G.oracle_step(p, nt, u1, u2).dtype == np.float32
     print("\n[brick-edges] B_oracle (float, of 2^-24 T) %-16s %-8s %.2f" % (mesh, damping, b))
     assert np.isfinite(b) and b <= 64.0
+
+
+@pytest.mark.parametrize("mesh,damping", MESHES_F32, ids=["%s-%s" % m for m in MESHES_F32])
+def test_rounded_double_step_meets_the_float_criterion(mesh, damping):
+    """The float cases' criterion (tests/test_gpu_step_terms.rounded_step: one step = float32(double step)) is satisfiable
+    on these meshes and fields: the double oracle on the widened float rows, rounded once, has no mismatch and stays under
+    the cap of undetermined components."""
+    p = H.step_mesh(mesh, damping)
+    nt, u1, u2, ref, T, _ = G.reference(mesh, damping, "f32")
+    B = G.bound_factor(mesh, damping)
+    got = G.float_model(p, nt, u1, u2)
+    r = G.rounded_step(got, ref, T, B, None)
+    print("\n[brick-edges] float32(double oracle) %-16s %-8s mismatches %d, undetermined %d of %d (cap %d)"
+          % (mesh, damping, r["mismatches"], r["undetermined"], r["plain"], int(G.UNDETERMINED_CAP * r["plain"])))
+    G.assert_rounded_step("%s-%s" % (mesh, damping), r, "float32(double oracle)")
+    assert G.additive_bound_trips(got, ref, T, B, None) == 0
+
+
+F32_CASES = [k for k, c in E.CASES.items() if c["precision"] == "f32"]
+
+
+@pytest.mark.parametrize("case", F32_CASES, ids=F32_CASES)
+def test_the_float_rows_leave_the_pinned_plan(case):
+    """The n_t rows are rounded to float before the planner sees them; NTSAME and packing read them.  The plan of a float
+    case is the pinned one, except that per-element units pack only where the rows are undamped (G.float_rows_pack)."""
+    c = E.CASES[case]
+    rep = E.plan_report(c["plan"], c["damping"], "f32")
+    want = dict(zip(_KEYS, PINNED[c["plan"]]))
+    if not G.float_rows_pack(c["damping"]):
+        want["packed_units"] = 0
+    assert rep["faults"] == 0 and {k: rep[k] for k in _KEYS} == want, (rep, want)
+    if case.endswith("-packed-none"):
+        assert rep["packed_units"] == rep["het_units"] > 0       # the packed form of the float build is what these two run
 
 
 def _node_at(p, X, Y, Z):

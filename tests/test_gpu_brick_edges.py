@@ -22,7 +22,14 @@ Every case: the context's counters equal the host-only plan check's for the same
 step these nodes; the numbers themselves are pinned in tests/test_brick_edges_cpu.py), one step against
 tests/helpers.extended_step per node and component with the bound of tests/test_gpu_step_terms.py
     |got - ref| <= B 2^-53 T,   B = 16 max(B_oracle, 4) = 64      (float state: + 2^-24 |ref|)
-over ALL nodes, nothing non-finite, the old field handed back bit for bit.  Then every node loaded from rest
+over ALL nodes, nothing non-finite, the old field handed back bit for bit.  A float state is also held to
+tests/test_gpu_step_terms.rounded_step: got == float32(double step) bit for bit, undetermined components at most 1 in
+10 000 -- 16 f32 cases, one or more for every footprint class above: cz = 2 (also by component and with per-node rows), both
+faces in one unit, 2 x 8 / 2 x 1, the 12-node brick, the two full tiles, five units per column, the per-element kernel
+unpacked on all three het meshes (float n_t rows under Rayleigh damping do not pack: the plan compared with hq_info is the
+host-only one of the FLOAT rows) and <PACKED> without damping on hetedge65x9x8 and hetedge64x9x36, all three ragged
+boundaries.  Measured: 0 mismatches, 0 components off float32(ref), undetermined 1 of 30 261 (edge130x10x6) and 1 of
+72 150 (hetedge64x9x36, rayleigh), 0 elsewhere.  Then every node loaded from rest
 (tests/test_gpu_sources.py's criterion, unchanged) and six steps against the oracle at the suite's 1e-9.
 
 Footprint classes (footprint_classes below): a node's tile extent by arithmetic on its lattice position, "z face" for its
@@ -30,7 +37,7 @@ nodes on a z face plane (brick nodes where the faces ride: the uniform plans wit
 elsewhere the patches step them), "shell" for the x / y faces (always the patches').
 
 Worst |got - ref| / (2^-53 T) per kernel family and footprint class on an MI355X (the bound is 64; no case failed, no
-kernel or planner change was needed; 52 cases in 6.9 s, the slowest 0.8 s):
+kernel or planner change was needed; 65 cases in 7.8 s with the float twins, 52 in 6.9 s before them, the slowest 0.8 s):
   hq_k_brick (one n_t row; cz = default, 2, 3, 5, auto 8; faces riding)
       64 x 8 1.90 - 2.03 (z face 1.54 - 1.81)   1 x 8 1.10 - 1.80 (z face 0.80 - 1.08)   64 x 1 1.32 - 1.86 (z face 1.33 - 1.56)
       1 x 1 0.34 - 1.49 (z face 0.33 - 0.53)    2 x 8 1.60 (1.29)   2 x 1 1.18 (0.42)   2 x 2 x 1 plane 0.94 (both faces 1.03)
@@ -96,14 +103,15 @@ PLANS = dict(UNIFORM_PLANS, **HET_PLANS, **RAGGED_PLANS)
 
 
 @functools.lru_cache(maxsize=None)
-def plan_report(plan, damping="rayleigh"):
-    """capi.brick_plan_check of a plan (host only), its options through the environment for the length of the call."""
+def plan_report(plan, damping="rayleigh", precision="f64"):
+    """capi.brick_plan_check of a plan (host only), its options through the environment for the length of the call.
+    precision "f32": on the n_t rows rounded to float, as the float library's planner gets them."""
     pl = PLANS[plan]
     env = {"HQ_" + k.upper(): str(v) for k, v in pl["options"].items()}
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        return capi.brick_plan_check(H.solver_desc(H.step_mesh(pl["mesh"], damping), pack=pl["pack"]))
+        return capi.brick_plan_check(H.solver_desc(H.step_mesh(pl["mesh"], damping), pack=pl["pack"], precision=precision))
     finally:
         for k, v in old.items():
             if v is None:
@@ -191,6 +199,17 @@ for _k in ("edge66x10x8-cz2", "hetedge65x9x8-nopack", "two70x10x8s68"):
 for _k in HET_PLANS:
     for _d in ("mass", "none"):
         CASES["%s-%s" % (_k, _d)] = _case(_k, _d)
+# float twins of the footprint classes the three f32 cases above do not reach: per-node rows, both z faces in one unit,
+# 2 x 8 / 2 x 1 / 2 x 2, two full tiles beside the 1-wide column, five units per column, 1 x 7 / 1 x 1 / 2 x 7 of the
+# per-element kernel, the other two ragged boundaries.  Float n_t rows pack only without damping (G.float_rows_pack): the
+# packed form on degenerate footprints has its float cases there; assert_runs_the_checked_plan compares hq_info with the
+# host-only plan of the FLOAT rows, tests/test_brick_edges_cpu.py pins what that plan is
+for _k in ("edge66x10x8-pernode-cz2", "edge66x10x2", "edge3x10x8", "edge3x3x2", "edge130x10x6", "edge66x10x36",
+           "hetedge64x9x36-nopack", "hetedge3x9x8-nopack", "two70x10x8s37", "two66x10x8s64"):
+    CASES["f32-" + _k] = _case(_k, precision="f32")
+CASES["f32-edge66x10x8-cz2-bycomp"] = _case("edge66x10x8-cz2", precision="f32", brick_by_component=1)
+for _k in ("hetedge65x9x8-packed", "hetedge64x9x36-packed"):
+    CASES["f32-%s-none" % _k] = _case(_k, "none", precision="f32")
 
 
 def make(c, p, nt, u1=None, u2=None):
@@ -202,7 +221,7 @@ def make(c, p, nt, u1=None, u2=None):
 
 def assert_runs_the_checked_plan(s, c):
     """The context's counters are the host-only plan check's for the same options, and its options are the case's."""
-    rep, info, o = plan_report(c["plan"], c["damping"]), s.info(), s.options()
+    rep, info, o = plan_report(c["plan"], c["damping"], c["precision"]), s.info(), s.options()
     assert rep["faults"] == 0 and info["variant"] == G.PATCH
     for r, i in INFO_OF_REPORT:
         assert rep[r] == info[i], (c, r, rep[r], i, info[i])
@@ -223,6 +242,7 @@ def test_one_step_on_degenerate_footprints(case):
     s = make(c, p, nt, u1, u2)
     try:
         rep = assert_runs_the_checked_plan(s, c)
+        family = G.family_of(s)
         s.run(1)
         got, old = s.download()
         nonfinite = s.check_finite()
@@ -240,6 +260,11 @@ def test_one_step_on_degenerate_footprints(case):
     print("[brick-edges]     |got - ref| / (%s2^-53 T) by footprint: " % ("2^-24 |ref| + " if f32 else "")
           + " | ".join("%s %.3g" % (k, v[0]) for k, v in by.items()))
     assert w[0] <= 1.0, (w, footprint(mesh, w[1]), got[w[1]], np.asarray(ref[w[1]], np.float64), G.branch_of(p, w[1]))
+    if f32:                                                        # one step of the float library is float32(double step)
+        r = G.rounded_step(got, ref, T, B, None)
+        print("[brick-edges]     float32(double step): mismatches %d, undetermined %d of %d, got != float32(ref) inside the band %d"
+              % (r["mismatches"], r["undetermined"], r["plain"], r["off_centre"]))
+        G.assert_rounded_step(case, r, family, (footprint(mesh, r["first"][0]), G.branch_of(p, r["first"][0])) if r["first"] else None)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -35,7 +35,17 @@ single-rank step on the assembled tables), pinned below 64 by tests/test_partiti
     box 32x16x16        2 and 8 ranks: 1.48 (float 1.64)    box 32x32x16 2 ranks 1.63    box 32x32x32 8 ranks 1.76
 (all below 4, so B = 64 everywhere.)  The factor 16 of tests/test_gpu_step_terms.py carries over: the interface sum adds
 at most (sharers) additions -- 4 here -- of terms that T already counts, so nothing is widened.
-precision="f32": bound 2^-24 |ref| + B 2^-53 T, at hanging nodes test_gpu_step_terms.float_rounding.
+precision="f32": bound 2^-24 |ref| + B 2^-53 T, at hanging nodes test_gpu_step_terms.float_rounding -- and beside it
+test_gpu_step_terms.rounded_step: one step of the float library is float32(double step) bit for bit (undetermined
+components, whose band straddles a float rounding boundary, at most 1 in 10 000), for every copy on every rank:
+hq_k_interface_update rounds once, and a hanging node whose anchors live elsewhere still equals the rounded double mean of
+the anchors' stored values as that rank holds them.  It is evaluated on the first copy of every global node; every other
+copy equals it bit for bit (asserted first).  Float twins: c5_gradient_branch on 8 (patch_seed, patch_step, patch_pers in
+the w form and with patch_wform = 0, scatter), two_level on 5, het70x20x12 on 3 (Rayleigh: float n_t rows do not pack --
+test_gpu_step_terms.float_rows_pack -- so hq_info must say brick_units_packed == 0, with and without brick_no_pack; no
+damping: hq_k_brick_het<PACKED> on a float state), the brick box on 2, the stencil boxes without bricks on 2 and 8, and
+the IPC case between processes.  Measured on an MI355X: 0 mismatches and 0 components off float32(ref) in all 13;
+undetermined 0 except the stencil boxes (1 of 55 539 and 2 of 107 811, the reference side's own counts).
 
 Every case also asserts, per rank: check_finite() == 0; every copy of a global node equals the first one seen bit for bit;
 the downloaded old field equals u1[gid] bit for bit; hq_info.transport (4 = linked in one process, 2 = IPC, 3 = host-staged)
@@ -58,8 +68,9 @@ update of hq_k_interface_update do not depend on how the records travel.
     hq_k_brick on the box, 2 ranks 1.72 | 1.12, 8 ranks 1.72 | 1.21 (overlap, brick_by_component, no_fused_share alike)
     hq_k_patch_stencil on the boxes without bricks: 2 ranks 1.73 | 1.05, 8 ranks 1.84 | 1.37
     float state: 0.992 (c5_gradient_branch on 8), 0.975 (two_level), 0.992 (box), 0.995 (IPC between processes) of the f32 bound
-50 cases in 25 s on the device; the slowest are the four between processes (3.4 - 3.8 s: five processes start), of the
-others the first of a problem (2.0 s with its reference), then 0.2 - 0.7 s each."""
+59 cases in 26 s on the device (50 in 25 s before the nine float twins, which take 0.1 - 0.7 s each); the slowest are the
+four between processes (2.6 - 3.9 s: five processes start), of the others the first of a problem (2.1 s with its
+reference), then 0.2 - 0.7 s each."""
 import numpy as np
 import pytest
 
@@ -140,6 +151,17 @@ CASES.update({
     "f32-c5-8": _oct(C5, 8, 1, precision="f32", route=NOBRICKS),
     "f32-two_level-5": _oct("two_level", 5, 1, precision="f32", route=NOBRICKS),
     "f32-box-2": _box(2, 1, precision="f32"),
+    # float twins of the forms above that had none (the criterion: ST.rounded_step on every copy of every rank)
+    "f32-het-3": _oct("het70x20x12", 3, 1, pack=True, precision="f32", route=("het",)),
+    "f32-het-3-none": _oct("het70x20x12", 3, 1, "none", pack=True, precision="f32", route=("het",)),
+    "f32-het-3-no_pack": _oct("het70x20x12", 3, 1, options={"brick_no_pack": 1}, pack=True, precision="f32", route=("het",)),
+    "f32-box-2-stencil-ov0": _box(2, 0, {"no_bricks": 1}, precision="f32"),
+    "f32-box-8-stencil-ov1": _box(8, 1, {"no_bricks": 1}, precision="f32"),
+    "f32-c5-8-scatter": _oct(C5, 8, 1, variant=SCATTER, precision="f32", route=("scatter",)),
+    "f32-c5-8-patch_step": _oct(C5, 8, 1, options={"patch_pipe": 0}, precision="f32", route=NOBRICKS + (("kernel", "hq_k_patch_step"),)),
+    "f32-c5-8-patch_pers": _oct(C5, 8, 1, options={"patch_pipe": 4}, precision="f32", route=NOBRICKS + (("kernel", "hq_k_patch_pers"),)),
+    "f32-c5-8-patch_pers-u1u2": _oct(C5, 8, 1, options={"patch_pipe": 4, "patch_wform": 0}, precision="f32",
+                                     route=NOBRICKS + (("kernel", "hq_k_patch_pers"),)),
 })
 
 # ranks in processes of their own (tests/_hq_rank_worker.py, kind "step"): c5_gradient_branch on 5 ranks
@@ -172,8 +194,9 @@ def check_route(c, solvers, q):
                 assert info["brick_nodes"] > 0 and info["brick_units_het"] == 0 and kernel == "hq_k_brick", (r, kernel, info)
             elif tag == "box_stencil":
                 assert info["brick_nodes"] == 0 and info["stencil_patches"] > 0 and info["ragged_patches"] > 0, (r, info)
-            elif tag == "het":
-                assert info["brick_units_packed"] == (0 if c["options"].get("brick_no_pack") else info["brick_units_het"]), (r, info)
+            elif tag == "het":                                   # (float n_t rows pack only without damping: ST.float_rows_pack)
+                packs = not c["options"].get("brick_no_pack") and (c["precision"] == "f64" or ST.float_rows_pack(c["damping"]))
+                assert info["brick_units_packed"] == (info["brick_units_het"] if packs else 0), (r, info)
             elif tag == "ragged":                                # what the counters report: partitions this small need not have bricks
                 assert info["brick_units_het"] >= info["brick_units_ragged_het"], (r, info)
                 assert (info["brick_units_packed"] > 0) == (bool(c["pack"]) and info["brick_units_het"] > 0), (r, info)
@@ -236,8 +259,9 @@ def node_kinds(q):
     return out
 
 
-def check_fields(name, q, fields, olds, B):
-    """The bound, the copies and the old field for every rank's download; prints the [partition-step] line."""
+def check_fields(name, q, fields, olds, B, family=None):
+    """The bound, the copies and the old field for every rank's download; prints the [partition-step] line.  A float
+    state: also ST.rounded_step, one step = float32(double step), for every copy (family: the kernels, for its message)."""
     f32 = q["precision"] == "f32"
     bits = np.int32 if f32 else np.int64
     kinds = node_kinds(q)
@@ -266,6 +290,18 @@ def check_fields(name, q, fields, olds, B):
              "  ".join("%s %.2f" % kv for kv in by_kind.items())))
     assert have.all()
     assert top[0] <= 1.0, top
+    if f32:
+        # every copy equals `first` bit for bit (asserted above): what holds for it holds for every copy on every rank, a
+        # hanging node's anchors included -- the values that rank holds are these
+        r = ST.rounded_step(first, q["ref"], q["T"], B, q["dangling"])
+        print("[partition-step] %-28s float32(double step): mismatches %d, undetermined %d of %d, got != float32(ref) inside the band %d"
+              % (name, r["mismatches"], r["undetermined"], r["plain"], r["off_centre"]))
+        where = None
+        if r["first"]:
+            n = r["first"][0]
+            where = dict(ranks={rk: str(kinds[rk][int(np.nonzero(g == n)[0][0])]) for rk, g in enumerate(q["gid"]) if (g == n).any()},
+                         branch_of=ST.branch_of(dict(lnid=q["lnid"], labels=q["labels"]), n) if q.get("labels") is not None else None)
+        ST.assert_rounded_step(name, r, family, where)
 
 
 @pytest.mark.parametrize("case", list(CASES), ids=list(CASES))
@@ -277,14 +313,16 @@ def test_one_step_from_independent_fields_on_partitions(case):
     solvers, boxes = make_solvers(c, q)
     try:
         capi.group_link(solvers)
-        check_route(c, solvers, q)
+        infos = check_route(c, solvers, q)
+        family = (sorted({s.dominant_kernel() for s in solvers}),) + tuple(
+            "%s=%d" % (k, sum(i[k] for i in infos)) for k in ("brick_units", "brick_units_het", "brick_units_packed", "npatches", "stencil_patches"))
         capi.group_run(solvers, 1)
         got = [s.download() for s in solvers]
         nonfinite = [s.check_finite() for s in solvers]
     finally:
         close_all(solvers, boxes)
     assert nonfinite == [0] * c["nranks"], nonfinite
-    check_fields(case, q, [g[0] for g in got], [g[1] for g in got], B)
+    check_fields(case, q, [g[0] for g in got], [g[1] for g in got], B, family)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -320,4 +358,4 @@ def test_one_step_from_independent_fields_between_processes(case, tmp_path):
         assert np.array_equal(z["gid"], q["gid"][r])
         assert int(z["transport"]) == (2 if c["transport"] == "ipc" else 3) and int(z["nonfinite"]) == 0, r
         assert str(z["kernel"]).startswith("hq_k_patch") and int(z["brick_nodes"]) == 0, (r, str(z["kernel"]))
-    check_fields("processes-" + case, q, [z["tm1"] for z in out], [z["tm2"] for z in out], B)
+    check_fields("processes-" + case, q, [z["tm1"] for z in out], [z["tm2"] for z in out], B, sorted({str(z["kernel"]) for z in out}))

@@ -25,13 +25,35 @@ intermediates up to 8 times the size of a term; packed units add their documente
 of one float ulp in zeta is 6e-8 of the damping share -- tests/test_step_terms_cpu.py shows that, a capped element given
 its uncapped lambda and 1e-9 in one m1 tripping this bound at the nodes concerned only.
 precision="f32": float32 n_t rows and fields, ref from the widened floats, bound 2^-24 |ref| + B 2^-53 T (the library
-rounds the state once).
+rounds the state once).  At a hanging node the float term is (deps + 1) 2^-24 mean|ref(anchors)| instead (float_rounding
+below); measured there 0.38 x 2^-24 mean|ref(anchors)|, 31 times 2^-24 of its own value.
 
+The float library per node (rounded_step below).  That additive bound is nearly all rounding of the state: every c1 of
+het70x20x12 off by 1e-9 passes it (tests/test_step_terms_cpu.py).  But the float library rounds the state ONCE and every
+sum inside a kernel is double, so what it must return is float32(double step), and that is held to the bit.  Every f64
+key has an "f32-" twin (the same mesh, options, damping and CHECKS entry on float32 rows and fields) under
+    lo = float32(ref - B 2^-53 T), hi = float32(ref + B 2^-53 T)      (round to nearest from np.longdouble; B as above)
+    plain node, lo == hi    got == lo bit for bit (int32 views)
+    plain node, lo != hi    "undetermined": got is one of the floats in [lo, hi]; at most 1 component in 10 000 per case
+                            (UNDETERMINED_CAP: a condition on the inputs, which the reference side meets without a device)
+    hanging node            got == float32(sum over its anchors, in list order, of float64(got[anchor]) / deps) bit for bit,
+                            from the library's OWN anchors: the text of hq_k_adjust_assign; the double sum is exact
+                            (asserted), so its order cannot matter, and the anchors are plain nodes
+with the additive bound still asserted beside it.  A form that does not exist in the float build: a per-element unit packs
+only if its n_t rows come back out of the two doubles {m0, m0 - m1} to 1e-15; rows rounded to float do so only without
+damping (m1 = m0, m2 = 2 m0), so the "het-packed" and "het-ragged-packed" twins under Rayleigh and mass damping assert
+from hq_info that hq_k_brick_het runs them UNPACKED (brick_units_packed == 0 with the same per-element units:
+float_rows_pack, float_twin) and the twins without damping run hq_k_brick_het<PACKED> on a float state.
+Measured on an MI355X, every f32 case (47 here, 16 in tests/test_gpu_brick_edges.py, 13 in tests/test_gpu_partition_step.py):
+    mismatches 0; got != float32(ref) inside the band 0 -- every component of every kernel form is the correctly rounded
+    reference itself;  undetermined 0 of 3 294 - 107 811 plain components per case here
+(hq_k_brick default / brick_cz = 5 / by component / per-node rows on both boxes; hq_k_patch_stencil subsets, full lattices,
+element lattice rows, patch_no_uniform; hq_k_brick_het unpacked on het70x20x12 and ragged c5_gradient_branch under all three
+dampings, <PACKED> without damping; hq_k_patch_step, hq_k_patch_pers in the w form and with patch_wform = 0, hq_k_patch_seed
+with patch_no_iso / _ntsame / _dedup / _lattice on het70x20x12 and two_level; scatter on both).
 
-At a hanging node the float term is (deps + 1) 2^-24 mean|ref(anchors)| instead: its value is the float mean of its anchors'
-stored values (float_rounding below); measured there 0.38 x 2^-24 mean|ref(anchors)|, 31 times 2^-24 of its own value.
-
-Worst |got - ref| / (2^-53 T) per kernel family on an MI355X (the bound is 64; 49 cases in 6.3 s, the slowest 1.1 s):
+Worst |got - ref| / (2^-53 T) per kernel family on an MI355X (the bound is 64; 93 cases in 7.4 s of which the f32 ones
+take 2.7 s, the slowest 1.1 s; 49 cases took 6.3 s before the f32 twins):
     hq_k_brick (default, brick_cz = 5, by component, per-node rows), both boxes          2.0 - 2.1
     hq_k_patch_stencil (subsets / full lattices), element lattice rows, patch_no_uniform  1.8 - 2.4
     hq_k_brick_het unpacked: het70x20x12 3.5 / 3.8 / 3.7 (rayleigh / mass / none), ragged c5_gradient_branch 3.6 / 4.1 / 3.4
@@ -176,6 +198,31 @@ CASES.update({
 })
 
 
+def float_rows_pack(damping):
+    """Whether per-element units can pack when the n_t rows arrive as floats.  The planner packs a unit only if every
+    owned row comes back out of the two doubles {m0, m0 - m1}: m1 exactly and m2 = 2 m0 - (m0 - m1) to 1e-15.  Rows rounded
+    to float keep that relation only where it is exact to begin with: without damping m1 = m0 and m2 = 2 m0 (a power of
+    two times the same float).  With Rayleigh or mass damping m2 and 2 m0 - m1 differ by the rows' float rounding, about
+    6e-8, at every node, so hq_k_brick_het runs unpacked there -- the form does not exist in the float build."""
+    return damping == "none"
+
+
+def float_twin(c):
+    """The f32 twin of an f64 case: the same mesh, options, damping and CHECKS entry on float32 n_t rows and fields.  A
+    check that expects packed units expects them only where float rows can pack; elsewhere it asserts from hq_info that
+    the unpacked form runs instead (brick_units_packed == 0 with the same per-element units)."""
+    check = c["check"]
+    if check[0] in ("het", "gradient") and check[1] and not float_rows_pack(c["damping"]):
+        check = (check[0], type(check[1])(0))
+    return dict(c, precision="f32", check=check)
+
+
+# every f64 key has an f32- twin (two of the three older f32 cases carry their twin's name already; "f32-het-het70x20x12"
+# keeps its own and equals "f32-het-het70x20x12-rayleigh")
+for _k in [k for k, c in CASES.items() if c["precision"] == "f64"]:
+    CASES["f32-" + _k] = float_twin(CASES[_k])
+
+
 def make(c, p, nt, u1, u2):
     kw = dict(edata=p["edata"], material=p["material"]) if c["pack"] else {}
     return ha.Solver(p["lnid"], p["etable"], nt, p["dt"], tm1=u1, tm2=u2, dangling=p["dangling"], node_xyz=p["node_xyz"],
@@ -206,6 +253,109 @@ def worst(got, ref, T, B, f32=False, dangling=None):
     return float(q[n, d]), int(n), int(d), float((err / (EPS * T)).max())
 
 
+# ---------------------------------------------------------------------------------------------
+# the float library: one step is float32(double step), per node and component
+# ---------------------------------------------------------------------------------------------
+UNDETERMINED_CAP = 1e-4                                          # of a case's plain components: a condition, not a measurement
+
+
+def _ordered(x):
+    """float32 -> int64 that counts floats in order (the distance of two of them is their distance in ulps)."""
+    i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
+    return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+
+
+def hanging_assignment(got, dangling):
+    """hq_k_adjust_assign restated on the library's OWN output: per hanging node the anchors' stored floats widened,
+    each divided by deps, summed in double in list order, rounded once.  -> (ids, expected float32 [n, 3], exact): exact
+    says that the double sum equals the same sum in np.longdouble in either order, so the order cannot matter."""
+    ids, ptr, anc = [np.asarray(a, np.int64) for a in dangling]
+    deps = np.diff(ptr)
+    s = np.zeros((len(ids), 3), np.float64)
+    fwd, bwd = np.zeros((len(ids), 3), np.longdouble), np.zeros((len(ids), 3), np.longdouble)
+    for j in range(int(deps.max()) if len(ids) else 0):
+        sel = np.nonzero(j < deps)[0]
+        s[sel] += got[anc[ptr[sel] + j]].astype(np.float64) / deps[sel, None].astype(np.float64)
+        fwd[sel] += got[anc[ptr[sel] + j]].astype(np.longdouble) / deps[sel, None].astype(np.longdouble)
+        bwd[sel] += got[anc[ptr[sel + 1] - 1 - j]].astype(np.longdouble) / deps[sel, None].astype(np.longdouble)
+    exact = bool(np.array_equal(s.astype(np.longdouble), fwd) and np.array_equal(fwd, bwd))
+    return ids, s.astype(np.float32), exact
+
+
+def rounded_step(got, ref, T, B, dangling=None, nodes=None):
+    """The float library rounds the state ONCE and sums in double: what it returns is float32(double step).  With
+    lo = float32(ref - B 2^-53 T) and hi = float32(ref + B 2^-53 T), both rounded to nearest from np.longdouble:
+      plain node, lo == hi    got equals it bit for bit                                           (else a mismatch)
+      plain node, lo != hi    "undetermined": got is one of the floats in [lo, hi]                (else a mismatch); counted
+      hanging node            got == hanging_assignment() of got's own anchors, bit for bit       (else a mismatch)
+    nodes: a mask of the nodes that count (a rank's copies among a global field); None = all.
+    -> dict(mismatches, undetermined, plain = the plain components counted, share = undetermined / plain,
+            off_centre = plain components with got != float32(ref) (inside the band then, unless they are mismatches),
+            hanging_exact, first = None or (node, component, "plain" / "hanging", got, expected = float32(ref) or the
+            assignment, their distance in float ulps, lo, hi))."""
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    L = np.longdouble
+    half = L(B) * L(EPS) * T
+    lo, hi, mid = (ref - half).astype(np.float32), (ref + half).astype(np.float32), ref.astype(np.float32)
+    bits = lambda a: np.ascontiguousarray(a).view(np.int32)
+    count = np.ones(len(got), bool) if nodes is None else np.asarray(nodes, bool).copy()
+    plain = count.copy()
+    expected, exact = mid.copy(), True
+    bad = np.zeros(got.shape, bool)
+    if dangling is not None and len(dangling[0]):
+        ids, want, exact = hanging_assignment(got, dangling)
+        plain[ids] = False
+        expected[ids] = want
+        bad[ids] = (bits(got[ids]) != bits(want)) & count[ids, None]
+    determined = bits(lo) == bits(hi)
+    ok = np.where(determined, bits(got) == bits(lo), (got >= lo) & (got <= hi))
+    bad |= ~ok & plain[:, None]
+    undetermined = int((~determined & plain[:, None]).sum())
+    nplain = 3 * int(plain.sum())
+    first = None
+    if bad.any():
+        n, d = [int(v) for v in np.argwhere(bad)[0]]
+        first = (n, d, "plain" if plain[n] else "hanging", float(got[n, d]), float(expected[n, d]),
+                 abs(int(_ordered(got[n, d:d + 1])[0]) - int(_ordered(expected[n, d:d + 1])[0])), float(lo[n, d]), float(hi[n, d]))
+    return dict(mismatches=int(bad.sum()), undetermined=undetermined, plain=nplain, share=undetermined / max(nplain, 1),
+                off_centre=int(((bits(got) != bits(mid)) & plain[:, None]).sum()), hanging_exact=exact, first=first)
+
+
+def assert_rounded_step(case, r, family, branches=None):
+    """0 mismatches and the cap, with a message that names the node, the figures, the kernel family and the branches."""
+    f = r["first"]
+    assert r["mismatches"] == 0, (
+        "%s: %d components are not float32(double step); the first: %s node %d component %d got %.9g expected %.9g (%d float ulps "
+        "apart; band [%.9g, %.9g]); kernel family %s; branch_of %s" % ((case, r["mismatches"], f[2], f[0], f[1]) + f[3:] + (family, branches)))
+    assert r["hanging_exact"], (case, "the double sum of a hanging node's anchors is not exact: its order would matter")
+    assert r["undetermined"] <= UNDETERMINED_CAP * r["plain"], (case, r["undetermined"], r["plain"])
+
+
+def float_model(p, nt, u1, u2, etable=None):
+    """The stand-in for the float library on a machine without a device: the DOUBLE C oracle on the widened float n_t rows
+    and fields (`dangling` given), rounded once to float32; then hq_k_adjust_assign's text on the rounded state (a hanging
+    node is the rounded double mean of its anchors' STORED floats -- so for the model the hanging rule checks only the
+    sum's exactness; the anchors are plain nodes under the first two rules)."""
+    wide = lambda a: np.ascontiguousarray(a, np.float64)
+    out = oracle_step(p, wide(nt), wide(u1), wide(u2), etable).astype(np.float32)
+    if p["dangling"] is not None and len(p["dangling"][0]):
+        ids, want, _ = hanging_assignment(out, p["dangling"])
+        out[ids] = want
+    return out
+
+
+def additive_bound_trips(got, ref, T, B, dangling):
+    """The components over 2^-24 |ref| + B 2^-53 T (hanging nodes: float_rounding): the f32 bound that worst() asserts."""
+    return int((np.abs(got.astype(np.longdouble) - ref) > B * EPS * T + float_rounding(ref, dangling)).sum())
+
+
+def family_of(s):
+    """The kernel family of a context from its counters, for a failure's message."""
+    info = s.info()
+    return (s.dominant_kernel(),) + tuple("%s=%d" % (k, info[k]) for k in ("brick_units", "brick_units_het", "brick_units_packed",
+                                                                          "brick_units_ragged_het", "npatches", "stencil_patches"))
+
+
 def branch_of(p, node):
     """The branch labels of the elements around a node (meshes with branch_materials), for a failure's message."""
     if "labels" not in p:
@@ -225,6 +375,7 @@ def test_one_step_from_independent_fields(case):
     try:
         assert s.info()["variant"] == c["variant"]
         CHECKS[c["check"][0]](*c["check"][1:])(s, p, c["mesh"])
+        family = family_of(s)
         s.run(1)
         got, old = s.download()
         nonfinite = s.check_finite()
@@ -236,3 +387,8 @@ def test_one_step_from_independent_fields(case):
     print("\n[step-terms] %-48s %-8s nodes %6d worst %.3f of the bound (node %d.%d) = %.2f x 2^-53 T%s"
           % (case, c["damping"], p["N"], w[0], w[1], w[2], w[3], " (f32: mostly the state's rounding)" if f32 else ""))
     assert w[0] <= 1.0, (w, got[w[1]], np.asarray(ref[w[1]], np.float64), branch_of(p, w[1]))
+    if f32:
+        r = rounded_step(got, ref, T, B, p["dangling"])
+        print("[step-terms] %-48s float32(double step): mismatches %d, undetermined %d of %d, got != float32(ref) inside the band %d; %s"
+              % (case, r["mismatches"], r["undetermined"], r["plain"], r["off_centre"], family[0]))
+        assert_rounded_step(case, r, family, branch_of(p, r["first"][0]) if r["first"] else None)

@@ -15,7 +15,10 @@ tests/test_gpu_partition_step.py, whose problems, fields, reference and bound ar
    two records of one c-list messenger swapped (what HQ_TEST_SWAP_RANK does); one owner's m1 at one interface node
    scaled by 1 + 1e-9; one shared hanging node's distribution skipped.
 5. The m1 mutation under the criterion the partition tests used so far (one step from tm2 = tm1 + 1e-6 noise, the error
-   over the field's maximum): below 1e-9 -- that criterion does not see it."""
+   over the field's maximum): below 1e-9 -- that criterion does not see it.
+6. The f32 problems: the rounded double oracle on the global float tables meets the float criterion
+   (tests/test_gpu_step_terms.rounded_step) with undetermined components under the cap (0; the stencil boxes 1 of 55 539
+   and 2 of 107 811); het70x20x12's ranks pack their per-element units on float rows only without damping."""
 import numpy as np
 import pytest
 
@@ -92,6 +95,41 @@ def test_box_oracle_step_against_the_extended_reference(shape, nranks, precision
     assert np.array_equal(q["etable"], single["etable"])
     if precision == "f64":
         assert H.rel_linf(q["ntable"], single["ntable"]) <= 4e-16
+
+
+F32_PROBLEMS = [("oct",) + t for t in OCT if t[3] == "f32"] + [("box",) + t for t in BOX if t[2] == "f32"]
+
+
+@pytest.mark.parametrize("problem", F32_PROBLEMS, ids=[_id(t) for t in F32_PROBLEMS])
+def test_rounded_double_step_meets_the_float_criterion_on_the_partitioned_problems(problem):
+    """The float cases' criterion (tests/test_gpu_step_terms.rounded_step) is satisfiable on every f32 problem of the device
+    file: the double oracle on the widened global float tables and fields, rounded once, hanging nodes assigned from the
+    stored floats -- no mismatch, exact hanging sums, undetermined components under the cap."""
+    ST = G.ST
+    q = (H.partition_step_problem(*problem[1:]) if problem[0] == "oct" else H.box_step_problem(*problem[1:]))
+    wide = lambda a: np.ascontiguousarray(a, np.float64)
+    o1, o2 = wide(q["u2"]), wide(q["u1"])
+    ho.solver_run(np.ascontiguousarray(q["lnid"], np.int32), q["etable"], wide(q["ntable"]), o1, o2, 0, 1, q["dt"],
+                  damping=q.get("kind", ho.DAMP_RAYLEIGH), dangling=q["dangling"])
+    got = o2.astype(np.float32)
+    if q["dangling"] is not None:
+        ids, want, _ = ST.hanging_assignment(got, q["dangling"])
+        got[ids] = want
+    r = ST.rounded_step(got, q["ref"], q["T"], G.bound_factor(q), q["dangling"])
+    print("\n[partition-step] float32(double oracle) %-40s mismatches %d, undetermined %d of %d (cap %d)"
+          % (_id(problem[1:]), r["mismatches"], r["undetermined"], r["plain"], int(ST.UNDETERMINED_CAP * r["plain"])))
+    ST.assert_rounded_step(_id(problem[1:]), r, "float32(double oracle)")
+
+
+@pytest.mark.parametrize("damping", ["rayleigh", "none"])
+def test_float_rows_pack_only_without_damping_on_the_het_partitions(damping):
+    """What the f32 het70x20x12 cases on 3 ranks assert from hq_info, from the planner's host-only check on the ranks' float
+    rows: every per-element unit packs without damping, none with Rayleigh damping (ST.float_rows_pack)."""
+    from hercules_amd import capi
+    q = H.partition_step_problem("het70x20x12", 3, damping, "f32")
+    reps = [capi.brick_plan_check(H.rank_desc(q, r, pack=True)) for r in range(3)]
+    assert all(b["faults"] == 0 and b["het_units"] > 0 for b in reps), reps
+    assert [b["packed_units"] for b in reps] == [b["het_units"] if G.ST.float_rows_pack(damping) else 0 for b in reps], reps
 
 
 def test_box_partitions_have_bricks_and_stencil_patches_on_every_rank():
