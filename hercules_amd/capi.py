@@ -24,7 +24,8 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_record_add", "hq_record_pending", "hq_record_fetch", "hq_record_clear",
            "hq_snapshot_add", "hq_snapshot_pending", "hq_snapshot_fetch", "hq_snapshot_clear",
            "hq_peak_add", "hq_peak_fetch", "hq_peak_load", "hq_peak_reset", "hq_peak_clear",
-           "hq_spec_add", "hq_spec_coefficients", "hq_spec_fetch", "hq_spec_load", "hq_spec_reset", "hq_spec_clear"]
+           "hq_spec_add", "hq_spec_coefficients", "hq_spec_fetch", "hq_spec_load", "hq_spec_reset", "hq_spec_clear",
+           "hq_cum_add", "hq_cum_fetch", "hq_cum_load", "hq_cum_reset", "hq_cum_clear"]
 HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
 HQ_PEAK_DISP, HQ_PEAK_VEL, HQ_PEAK_ACC = 1, 2, 4
 HQ_SPEC_MAX_PERIODS, HQ_SPEC_NVAL = 32, 4
@@ -85,6 +86,13 @@ class _SpecDesc(ctypes.Structure):
                 ("phi", ctypes.c_void_p), ("rate", ctypes.c_int32), ("first_step", ctypes.c_int32),
                 ("nperiods", ctypes.c_int32), ("reserved", ctypes.c_int32), ("periods", ctypes.c_void_p),
                 ("damping", ctypes.c_double)]
+
+
+class _CumDesc(ctypes.Structure):
+    _fields_ = [("npoints", ctypes.c_int32), ("nodes_per_point", ctypes.c_int32), ("ids", ctypes.c_void_p),
+                ("phi", ctypes.c_void_p), ("rate", ctypes.c_int32), ("first_step", ctypes.c_int32),
+                ("quantities", ctypes.c_int32), ("husid_every", ctypes.c_int32), ("husid_slots", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("threshold", ctypes.c_double * 3)]
 
 
 class _Info(ctypes.Structure):
@@ -591,6 +599,83 @@ class Solver:
         """hq_spec_clear: drop every spectrum tracker of the context and its device memory."""
         _check(self._lib.hq_spec_clear(self._h), self._lib)
         self._specs = {}
+
+    def cum_add(self, ids, phi=None, rate=1, first_step=0, quantities=HQ_PEAK_ACC, threshold=0.0, husid_every=0, husid_slots=0):
+        """hq_cum_add: a cumulative-intensity tracker (Arias, CAV, energy density, durations).  Points as peak_add's (phi
+        None: single nodes).  At the head of every step s >= first_step with s % rate == 0 the sample of every quantity of
+        the mask is added into sum |v| and sum v v per axis, and counted where its total exceeds `threshold` (a scalar, or
+        one value per quantity of the mask in mask order).  husid_every >= 1: the sums of squares after every
+        husid_every-th due sample are kept, husid_slots of them (the Husid curve).  Returns its handle."""
+        if phi is None:
+            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32)
+            k = 1
+        else:
+            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
+            phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
+            if len(ids) != len(phi):
+                raise HqError("cum_add: %d rows of ids, %d of phi" % (len(ids), len(phi)))
+            k = 8
+        nq = bin(int(quantities) & 7).count("1")
+        thr = np.broadcast_to(np.asarray(threshold, np.float64), (nq,)) if np.ndim(threshold) == 0 else np.asarray(threshold, np.float64).reshape(-1)
+        if len(thr) != nq:
+            raise HqError("cum_add: %d thresholds for %d quantities" % (len(thr), nq))
+        d = _CumDesc(len(ids), k, ids.ctypes.data, None if phi is None else phi.ctypes.data, int(rate), int(first_step),
+                     int(quantities), int(husid_every), int(husid_slots), 0, (ctypes.c_double * 3)(*([float(v) for v in thr] + [0.0] * (3 - nq))))
+        h = ctypes.c_int32(-1)
+        _check(self._lib.hq_cum_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
+        if not hasattr(self, "_cums"):
+            self._cums = {}
+        self._cums[h.value] = (len(ids), nq, int(husid_slots))
+        return h.value
+
+    def _cum_shape(self, handle):
+        if handle not in getattr(self, "_cums", {}):
+            raise HqError("unknown cumulative tracker handle %r" % (handle,))
+        return self._cums[handle]
+
+    def cum_fetch(self, handle, curve=True):
+        """hq_cum_fetch: (sums [npoints, nq, 6] float64, span [npoints, nq, 3] int32, curve [nfilled, npoints, nq, 3] or None,
+        curve_steps [nfilled] int32, nsamples) -- per quantity of the mask sum |x|, |y|, |z|, sum x x, y y, z z; the first and
+        the last step over the threshold (-1: never) and the count of such samples; the sums of squares as they stood behind
+        the samples of curve_steps.  Nothing is multiplied by the step h = rate dt: that is the caller's.  Waits for the
+        enqueued steps; the state stays on the device."""
+        npoints, nq, slots = self._cum_shape(handle)
+        sums = np.zeros((npoints, nq, 6))
+        span = np.zeros((npoints, nq, 3), np.int32)
+        cv = np.zeros((max(slots, 1), npoints, nq, 3)) if curve else None
+        steps = np.zeros(max(slots, 1), np.int32)
+        nf, n = ctypes.c_int32(), ctypes.c_int64()
+        pad = np.zeros(1)                                       # (an empty array has no address worth passing)
+        arg = lambda x: None if x is None else _ptr(x if x.size else pad)
+        _check(self._lib.hq_cum_fetch(self._h, ctypes.c_int32(handle), arg(sums), arg(span), arg(cv), _ptr(steps),
+                                      ctypes.byref(nf), ctypes.byref(n)), self._lib)
+        return sums, span, (cv[:nf.value].copy() if curve else None), steps[:nf.value].copy(), int(n.value)
+
+    def cum_load(self, handle, sums, span, curve, curve_steps, nsamples):
+        """hq_cum_load: put back what cum_fetch returned (a run that restarts from a checkpoint)."""
+        npoints, nq, _ = self._cum_shape(handle)
+        sums = np.ascontiguousarray(sums, np.float64)
+        span = np.ascontiguousarray(span, np.int32)
+        steps = np.ascontiguousarray(curve_steps, np.int32).reshape(-1)
+        nf = len(steps)
+        if nf and curve is None:
+            raise HqError("cum_load: curve_steps without a curve")
+        cv = np.zeros((0, npoints, nq, 3)) if curve is None else np.ascontiguousarray(curve, np.float64)
+        if sums.shape != (npoints, nq, 6) or span.shape != (npoints, nq, 3) or cv.shape != (nf, npoints, nq, 3):
+            raise HqError("cum_load: the arrays are not those of cum_fetch")
+        pad = np.zeros(1)
+        arg = lambda x: _ptr(x if x.size else pad)
+        _check(self._lib.hq_cum_load(self._h, ctypes.c_int32(handle), arg(sums), arg(span), arg(cv), arg(steps),
+                                     ctypes.c_int32(nf), ctypes.c_int64(int(nsamples))), self._lib)
+
+    def cum_reset(self, handle):
+        """hq_cum_reset: sums and counts 0, first / last step -1, no Husid slot filled, nsamples 0."""
+        _check(self._lib.hq_cum_reset(self._h, ctypes.c_int32(handle)), self._lib)
+
+    def cum_clear(self):
+        """hq_cum_clear: drop every cumulative tracker of the context and its device memory."""
+        _check(self._lib.hq_cum_clear(self._h), self._lib)
+        self._cums = {}
 
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)

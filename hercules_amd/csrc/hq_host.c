@@ -35,6 +35,7 @@
 #include "hq_host.h"
 #include "hq_cadence.h"
 #include "hq_peak.h"
+#include "hq_cumul.h"
 #include "hq_sdof.h"
 #include "hq_sample.h"
 
@@ -1440,6 +1441,57 @@ int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const i
                 if (!(quantities & (1 << q))) continue;
                 hq_peak_fold(v[3 * q], v[3 * q + 1], v[3 * q + 2], steps[k], pk, 1, w, 1);
                 pk += HQ_PEAK_NVAL; w += HQ_PEAK_NWHEN;
+            }
+        }
+    return HQ_OK;
+}
+
+int hqh_cum_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps, const double* samples,
+                 const double* threshold, double* sums, int32_t* span)
+{
+    if (npoints < 0 || nsamples < 0 || quantities == 0 || (quantities & ~(HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC)) != 0 || !threshold)
+        return HQ_ERR_ARG;
+    const int32_t nq = hq_peak_nq(quantities), ncomp = 3 * (1 + hq_peak_derivs(quantities));
+    double thr2[HQ_PEAK_NQ] = { 0.0, 0.0, 0.0 };
+    for (int32_t q = 0; q < nq; q++) {
+        if (!(threshold[q] >= 0.0) || threshold[q] - threshold[q] != 0.0) return HQ_ERR_ARG;
+        thr2[q] = threshold[q] * threshold[q];
+    }
+    if (npoints == 0 || nsamples == 0) return HQ_OK;
+    if (!steps || !samples || !sums || !span) return HQ_ERR_ARG;
+    for (int32_t k = 0; k < nsamples; k++)
+        for (int32_t p = 0; p < npoints; p++) {
+            const double* v = samples + ((int64_t)k * npoints + p) * ncomp;
+            double* sm = sums + (int64_t)p * nq * HQ_CUM_NSUM;
+            int32_t* w = span + (int64_t)p * nq * HQ_CUM_NSPAN;
+            for (int q = 0, m = 0; q < HQ_PEAK_NQ; q++) {
+                if (!(quantities & (1 << q))) continue;
+                hq_cum_fold(v[3 * q], v[3 * q + 1], v[3 * q + 2], steps[k], thr2[m++], sm, 1, w, 1);
+                sm += HQ_CUM_NSUM; w += HQ_CUM_NSPAN;
+            }
+        }
+    return HQ_OK;
+}
+
+int hqh_husid_cross(int32_t nslots, const int32_t* curve_steps, double step0, int64_t nseries, const double* curve,
+                    const double* total, int32_t nfrac, const double* fracs, double* out)
+{
+    if (nslots < 0 || nseries < 0 || nfrac < 0) return HQ_ERR_ARG;
+    if (nseries == 0 || nfrac == 0) return HQ_OK;
+    if (!total || !fracs || !out || (nslots > 0 && (!curve_steps || !curve))) return HQ_ERR_ARG;
+    for (int64_t s = 0; s < nseries; s++)
+        for (int32_t f = 0; f < nfrac; f++) {
+            double* o = out + s * nfrac + f;
+            *o = NAN;
+            if (!(total[s] > 0.0) || total[s] - total[s] != 0.0) continue;
+            const double want = fracs[f] * total[s];
+            for (int32_t k = 0; k < nslots; k++) {
+                const double c1 = curve[(int64_t)k * nseries + s];
+                if (!(c1 >= want)) continue;
+                const double c0 = k ? curve[(int64_t)(k - 1) * nseries + s] : 0.0;
+                const double s0 = k ? (double)curve_steps[k - 1] : step0, s1 = (double)curve_steps[k];
+                *o = c1 == c0 ? s1 : s0 + (s1 - s0) * (want - c0) / (c1 - c0);
+                break;
             }
         }
     return HQ_OK;

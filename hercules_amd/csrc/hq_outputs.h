@@ -1,7 +1,7 @@
 /*
- * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion and response-spectrum
- * trackers, field snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at the head of a step and
- * the hq_record_* / hq_peak_* / hq_spec_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
+ * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion, response-spectrum
+ * and cumulative-intensity trackers, field snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at
+ * the head of a step and the hq_record_* / hq_peak_* / hq_spec_* / hq_cum_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
  */
 #ifndef HQ_OUTPUTS_H
 #define HQ_OUTPUTS_H
@@ -95,6 +95,77 @@ hq_k_peak(int32_t np, const int32_t* __restrict__ ids, const double* __restrict_
     if (acc) {
         hq_sample_acc(K, w, row, u2, u3, d);
         hq_peak_fold(d[0] / dt2, d[1] / dt2, d[2] / dt2, step, s, np, sw, np);
+    }
+}
+
+/* a cumulative tracker's thresholds, squared, by quantity BIT (displacement, velocity, acceleration): a kernel argument, read
+ * with constant indices */
+struct hq_cum_thr2 { double v[3]; };
+
+/*
+ * One due step of a cumulative-intensity tracker (hq_cum_add): the sample hq_k_record would take at the point -- formed
+ * exactly as hq_k_peak forms it: hq_sample.h's stages, every value widened to double first, / dt and / dt2 divisions --
+ * added into the point's running sums (hq_cumul.h, the text hqh_cum_fold compiles) instead of being appended to a ring.
+ * One lane per point, no atomics, no LDS: a point belongs to one lane, and the launches of one stream are ordered.
+ * K as in hq_k_peak: 8 nodes and weights per point, or the point is a node.
+ * The state is [nq][6][np] doubles and [nq][3][np] int32, nq the set bits of `quantities` in the order displacement,
+ * velocity, acceleration: consecutive lanes on consecutive addresses, so a wave reads and writes each row in whole lines.
+ * A quantity's six sums are loaded into registers ahead of the arithmetic, folded there (stride 1) and stored back; the
+ * span is folded in place and touched only where the threshold was passed.  u2 / u3 are read only if the mask needs them.
+ * slot >= 0: a Husid step -- the lane copies the three sums of squares of every quantity, as just folded, to
+ * curve[slot][nq][3][np]; the host accounts which due sample fills which slot (hq_cum_launch) and never hands out a slot
+ * past the curve's end.  slot = -1 stores nothing.
+ * Bytes per point and due step, K = 1, acceleration only (a model, not a measurement): 4 (id) + 72 of gathers (u1, u2,
+ * u3; 36 in the f32 library) + 48 of sums read + 48 written = 172, plus 24 on a Husid step; the span adds 4 read and 8-12
+ * written on the samples over the threshold only.  K = 8, all three quantities: 96 of tables + 576 of gathers + 288 of sums.
+ */
+template <int K>
+__global__ void __launch_bounds__(256)
+hq_k_cum(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ phi,
+         const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, const hq_real* __restrict__ u3,
+         double dt, double dt2, int32_t quantities, int32_t step, hq_cum_thr2 thr2, double* __restrict__ sum,
+         int32_t* __restrict__ span, double* __restrict__ curve, int32_t slot)
+{
+#pragma clang fp contract(off)
+    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= np) return;
+    const bool vel = (quantities & HQ_PEAK_VEL) != 0, acc = (quantities & HQ_PEAK_ACC) != 0;
+    int64_t row[K];
+    double wk[K];
+#pragma unroll
+    for (int c = 0; c < K; c++) {
+        row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
+        if (K > 1) wk[c] = phi[(int64_t)c * np + p];
+    }
+    const double* w = K > 1 ? wk : nullptr;                      /* (a node: weight 1, hq_sample.h) */
+    double* s = sum + p;
+    int32_t* sw = span + p;
+    double* cv = slot >= 0 ? curve + (int64_t)slot * HQ_CUM_NCURVE * hq_peak_nq(quantities) * np + p : nullptr;
+    /* one quantity: its sums through registers, the span in place, the Husid rows behind the fold */
+    auto fold = [&](double x, double y, double z, double t2) {
+        double r[HQ_CUM_NSUM];
+#pragma unroll
+        for (int j = 0; j < HQ_CUM_NSUM; j++) r[j] = s[(int64_t)j * np];
+        hq_cum_fold(x, y, z, step, t2, r, 1, sw, np);
+#pragma unroll
+        for (int j = 0; j < HQ_CUM_NSUM; j++) s[(int64_t)j * np] = r[j];
+        if (cv) {
+#pragma unroll
+            for (int j = 0; j < HQ_CUM_NCURVE; j++) cv[(int64_t)j * np] = r[HQ_CUM_NSUM - HQ_CUM_NCURVE + j];
+            cv += (int64_t)HQ_CUM_NCURVE * np;
+        }
+        s += (int64_t)HQ_CUM_NSUM * np; sw += (int64_t)HQ_CUM_NSPAN * np;
+    };
+    double d[3] = { 0.0, 0.0, 0.0 };
+    hq_sample_disp(K, w, row, u1, d);
+    if (quantities & HQ_PEAK_DISP) fold(d[0], d[1], d[2], thr2.v[0]);
+    if (vel || acc) {
+        hq_sample_vel(K, w, row, u2, d);
+        if (vel) fold(d[0] / dt, d[1] / dt, d[2] / dt, thr2.v[1]);
+    }
+    if (acc) {
+        hq_sample_acc(K, w, row, u2, u3, d);
+        fold(d[0] / dt2, d[1] / dt2, d[2] / dt2, thr2.v[2]);
     }
 }
 
@@ -321,6 +392,19 @@ struct hq_ctx::hq_spec_tracker : hq_ctx::hq_output {
     hq_dbuf<double> d_osc;        /* [nper][2][3][np] */
     hq_dbuf<double> d_sd;         /* [nper][4][np] */
 };
+/* cumulative-intensity trackers (hq_cum_add): running sums and threshold spans per point, updated in place by hq_k_cum, and
+ * the Husid curve -- the sums of squares as they stood after every husid_every-th due sample, husid_slots of them.  As a peak
+ * tracker, no ring, nothing pending, nothing for hq_run to count: which sample fills which slot follows from nsamples alone */
+struct hq_ctx::hq_cum_tracker : hq_ctx::hq_output {
+    hq_point_set pts;
+    int32_t quantities = 0, nq = 0, husid_every = 0, husid_slots = 0;
+    int64_t nsamples = 0;         /* due steps folded or enqueued so far */
+    hq_cum_thr2 thr2 = { { 0.0, 0.0, 0.0 } };   /* by quantity bit */
+    std::vector<int32_t> curve_steps;           /* [nfilled] the step of the sample each filled slot was stored behind */
+    hq_dbuf<double> d_sum;        /* [nq][6][np] */
+    hq_dbuf<int32_t> d_span;      /* [nq][3][np] */
+    hq_dbuf<double> d_curve;      /* [husid_slots][nq][3][np] */
+};
 /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
  * pinned host memory.  A slot holds the fields one behind the other,
  * each at a 256-byte boundary (off[]; the same layout on both sides, so one copy carries a slot).  sstream, the copy
@@ -444,6 +528,43 @@ static void hq_spec_launch(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
                                                         c->d_u[c->spare], c->dt2, t.nper, t.d_coef, t.d_aprev, t.d_osc, t.d_sd);
 }
 
+/* the state of one cumulative tracker as it is before its first sample: sums 0, first / last step -1 (every byte 0xff), count
+ * 0, no Husid slot filled -- as hq_peak_zero */
+static int hq_cum_zero(hq_ctx* c, hq_ctx::hq_cum_tracker& t)
+{
+    HQ_TRY(t.d_sum.fill(0, c->stream));
+    HQ_TRY(t.d_curve.fill(0, c->stream));
+    HQ_TRY(t.d_span.fill(0xff, c->stream));
+    const size_t np = (size_t)t.pts.np;
+    for (int32_t q = 0; q < t.nq && np > 0; q++)
+        HQ_HIP(hipMemsetAsync(t.d_span + ((size_t)q * HQ_CUM_NSPAN + 2) * np, 0, sizeof(int32_t) * np, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    t.curve_steps.clear();
+    return HQ_OK;
+}
+
+/* head of a step, where hq_peak_launch sits and behind the same waits: one hq_k_cum launch per due tracker on the compute
+ * stream.  As with a peak tracker, only a mask with accelerations reads d_u[spare], and only then does the caller hold the
+ * streams back.  The Husid slot is accounted HERE, on the host, from the count of due samples: this sample is number
+ * n + 1; every husid_every-th one is stored, into slot (n + 1) / husid_every - 1, as long as that slot exists -- past the
+ * last slot the sums go on growing and the curve simply ends. */
+static void hq_cum_launch(hq_ctx* c, hq_ctx::hq_cum_tracker& t)
+{
+    const int64_t n1 = ++t.nsamples;
+    int32_t slot = -1;
+    if (t.husid_every > 0 && n1 % t.husid_every == 0 && n1 / t.husid_every - 1 < t.husid_slots) {
+        slot = (int32_t)(n1 / t.husid_every - 1);
+        t.curve_steps.resize((size_t)slot + 1, -1);
+        t.curve_steps[(size_t)slot] = c->step;
+    }
+    if (t.pts.np <= 0) return;
+    const hq_real* u3 = (t.quantities & HQ_PEAK_ACC) ? c->d_u[c->spare] : c->d_u[c->prev];
+    const auto k = t.pts.K == 1 ? hq_k_cum<1> : hq_k_cum<8>;
+    k<<<hq_blocks(t.pts.np, 256), 256, 0, c->stream>>>(t.pts.np, t.pts.d_ids, t.pts.d_phi, c->d_u[c->now], c->d_u[c->prev], u3,
+                                                        c->dt, c->dt2, t.quantities, c->step, t.thr2, t.d_sum, t.d_span,
+                                                        t.d_curve, slot);
+}
+
 /* what of a snapshot is not device memory: the pinned mirror and the slots' events */
 static void hq_output_free(hq_ctx::hq_snapshot& sn)
 {
@@ -479,7 +600,7 @@ static int hq_snapshot_launch(hq_ctx* c, hq_ctx::hq_snapshot& sn)
 
 /* The head of a step: every due output in solver_run's order (psolve.c:4277-4280: checkpoint / wavefield, then planes /
  * stations), then the trackers.  The launches that the step's other streams must stay behind (every snapshot, every recorder,
- * a tracker of accelerations, a spectrum tracker: the comments above tell why) go first; ONE record of ev_output behind the last of them -- a
+ * a peak or cumulative tracker of accelerations, a spectrum tracker: the comments above tell why) go first; ONE record of ev_output behind the last of them -- a
  * snapshot's own serves if nothing followed it -- holds the bricks' stream and the exchange chain's, on the patch variant,
  * where there is such a stream.  The trackers that need no hold follow that record: the streams never wait for them. */
 static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
@@ -494,6 +615,8 @@ static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
         if ((t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) { hq_peak_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
     for (auto& t : c->specs)                     /* ... and the spectrum trackers, which all do */
         if (hq_cadence_due(t.due, c->step)) { hq_spec_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
+    for (auto& t : c->cums)                      /* ... and the cumulative trackers of accelerations */
+        if ((t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) { hq_cum_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
     if (hold && c->variant == HQ_VARIANT_PATCH && (hold_b || hold_c)) {
         if (!recorded) HQ_HIP(hipEventRecord(c->ev_output, c->stream));
         if (hold_b) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_output, 0));
@@ -501,6 +624,8 @@ static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
     }
     for (auto& t : c->peaks)                     /* the other trackers: no stream waits for them */
         if (!(t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) hq_peak_launch(c, t);
+    for (auto& t : c->cums)
+        if (!(t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) hq_cum_launch(c, t);
     return HQ_OK;
 }
 
@@ -511,7 +636,7 @@ static void hq_outputs_drop(std::vector<hq_ctx::hq_snapshot>& snaps)
     snaps.clear();
 }
 
-/* hq_record_clear, hq_peak_clear, hq_spec_clear: every output of one kind goes, behind the steps enqueued so far */
+/* hq_record_clear, hq_peak_clear, hq_spec_clear, hq_cum_clear: every output of one kind goes, behind the steps enqueued so far */
 template <typename T>
 static int hq_outputs_clear(hq_ctx* c, std::vector<T> hq_ctx::*outs)
 {
@@ -778,6 +903,116 @@ extern "C" int hq_spec_reset(hq_ctx* c, int32_t handle)
 }
 
 extern "C" int hq_spec_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::specs); }
+
+/* ---- cumulative-intensity trackers: entry points (include/hq_solver.h) ---- */
+
+extern "C" int hq_cum_add(hq_ctx* c, const hq_cum_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const int32_t all = HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC;
+    const int32_t K = d->nodes_per_point;
+    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->quantities == 0 || (d->quantities & ~all) != 0 ||
+        (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
+        return hq_fail(HQ_ERR_ARG, "bad cumulative tracker description%s", "");
+    if (!((d->husid_every == 0 && d->husid_slots == 0) || (d->husid_every >= 1 && d->husid_slots >= 1)))
+        return hq_fail(HQ_ERR_ARG, "husid_every and husid_slots are both 0 or both >= 1%s", "");
+    const int32_t nq = hq_peak_nq(d->quantities);
+    for (int32_t q = 0; q < nq; q++)                             /* finite and >= 0 (x - x is NaN for an infinity) */
+        if (!(d->threshold[q] >= 0.0) || d->threshold[q] - d->threshold[q] != 0.0)
+            return hq_fail(HQ_ERR_ARG, "a threshold of a cumulative tracker is not finite and >= 0%s", "");
+    if ((d->quantities & HQ_PEAK_ACC) && c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    hq_ctx::hq_cum_tracker t;
+    t.quantities = d->quantities; t.nq = nq; t.due = { d->rate, d->first_step };
+    t.husid_every = d->husid_every; t.husid_slots = d->husid_slots;
+    for (int32_t b = 0, q = 0; b < HQ_PEAK_NQ; b++)              /* mask order -> quantity bit; squared once, here */
+        if (d->quantities & (1 << b)) { t.thr2.v[b] = d->threshold[q] * d->threshold[q]; q++; }
+    const size_t n = (size_t)nq * (size_t)d->npoints;
+    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts));
+    HQ_TRY(t.d_sum.alloc(&c->bytes, HQ_CUM_NSUM * n));
+    HQ_TRY(t.d_span.alloc(&c->bytes, HQ_CUM_NSPAN * n));
+    HQ_TRY(t.d_curve.alloc(&c->bytes, HQ_CUM_NCURVE * n * (size_t)d->husid_slots));
+    HQ_TRY(hq_cum_zero(c, t));
+    c->h2d_bytes += t.pts.h2d();
+    t.id = c->cum_next_id++;
+    *handle = t.id;
+    c->cums.push_back(std::move(t));
+    return HQ_OK;
+}
+
+/* the state crosses PCIe as the device keeps it ([nq][6][np], [nq][3][np], per slot [nq][3][np]); the caller's arrays are
+ * [np][nq][6], [np][nq][3], per slot [np][nq][3].  Only the filled slots of the curve travel. */
+extern "C" int hq_cum_fetch(hq_ctx* c, int32_t handle, double* sums, int32_t* span, double* curve, int32_t* curve_steps,
+                            int32_t* nfilled, int64_t* nsamples)
+{
+    if (!c || !sums || !span || !nfilled || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_cum_tracker* t = hq_output_find(c->cums, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown cumulative tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq, nf = t->curve_steps.size();
+    *nsamples = t->nsamples;
+    *nfilled = (int32_t)nf;
+    if (curve_steps) std::copy(t->curve_steps.begin(), t->curve_steps.end(), curve_steps);
+    if (n == 0) return HQ_OK;
+    std::vector<double> sm(HQ_CUM_NSUM * n), cv(curve ? HQ_CUM_NCURVE * n * nf : 0);
+    std::vector<int32_t> sp(HQ_CUM_NSPAN * n);
+    HQ_HIP(hipMemcpyAsync(sm.data(), t->d_sum, sizeof(double) * sm.size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_HIP(hipMemcpyAsync(sp.data(), t->d_span, sizeof(int32_t) * sp.size(), hipMemcpyDeviceToHost, c->stream));
+    if (!cv.empty()) HQ_HIP(hipMemcpyAsync(cv.data(), t->d_curve, sizeof(double) * cv.size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    hq_peak_transpose(np, nq * HQ_CUM_NSUM, true, sm.data(), sums);
+    hq_peak_transpose(np, nq * HQ_CUM_NSPAN, true, sp.data(), span);
+    for (size_t k = 0; k < nf && curve; k++)
+        hq_peak_transpose(np, nq * HQ_CUM_NCURVE, true, cv.data() + k * HQ_CUM_NCURVE * n, curve + k * HQ_CUM_NCURVE * n);
+    c->d2h_bytes += (int64_t)(sizeof(double) * (sm.size() + cv.size()) + sizeof(int32_t) * sp.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_cum_load(hq_ctx* c, int32_t handle, const double* sums, const int32_t* span, const double* curve,
+                           const int32_t* curve_steps, int32_t nfilled, int64_t nsamples)
+{
+    if (!c || !sums || !span || nsamples < 0 || nfilled < 0 || (nfilled > 0 && (!curve || !curve_steps)))
+        return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
+    hq_ctx::hq_cum_tracker* t = hq_output_find(c->cums, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown cumulative tracker handle%s", "");
+    /* the slots that nsamples due samples fill: the accounting of hq_cum_launch goes on from nsamples alone */
+    const int64_t filled = t->husid_every > 0 ? std::min<int64_t>(nsamples / t->husid_every, t->husid_slots) : 0;
+    if (nfilled != filled) return hq_fail(HQ_ERR_ARG, "nfilled is not what nsamples due samples fill of this tracker's curve%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq, nf = (size_t)nfilled;
+    t->nsamples = nsamples;
+    t->curve_steps.assign(curve_steps, curve_steps + nf);
+    if (n == 0) return HQ_OK;
+    std::vector<double> sm(HQ_CUM_NSUM * n), cv(HQ_CUM_NCURVE * n * nf);
+    std::vector<int32_t> sp(HQ_CUM_NSPAN * n);
+    hq_peak_transpose(np, nq * HQ_CUM_NSUM, false, sums, sm.data());
+    hq_peak_transpose(np, nq * HQ_CUM_NSPAN, false, span, sp.data());
+    for (size_t k = 0; k < nf; k++)
+        hq_peak_transpose(np, nq * HQ_CUM_NCURVE, false, curve + k * HQ_CUM_NCURVE * n, cv.data() + k * HQ_CUM_NCURVE * n);
+    HQ_HIP(hipMemcpyAsync(t->d_sum, sm.data(), sizeof(double) * sm.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipMemcpyAsync(t->d_span, sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, c->stream));
+    if (!cv.empty()) HQ_HIP(hipMemcpyAsync(t->d_curve, cv.data(), sizeof(double) * cv.size(), hipMemcpyHostToDevice, c->stream));
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    c->h2d_bytes += (int64_t)(sizeof(double) * (sm.size() + cv.size()) + sizeof(int32_t) * sp.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_cum_reset(hq_ctx* c, int32_t handle)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_ctx::hq_cum_tracker* t = hq_output_find(c->cums, handle);
+    if (!t) return hq_fail(HQ_ERR_ARG, "unknown cumulative tracker handle%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    HQ_TRY(hq_cum_zero(c, *t));
+    t->nsamples = 0;
+    return HQ_OK;
+}
+
+extern "C" int hq_cum_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::cums); }
 
 /* ---- field snapshots: entry points (include/hq_solver.h) ---- */
 

@@ -18,7 +18,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_forcefile_info", "hqh_forcefile_read", "hqh_forcefile_write",
            "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
-           "hqh_station_kinematics", "hqh_peak_fold", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
+           "hqh_station_kinematics", "hqh_peak_fold", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
            "hqh_cvm_open", "hqh_cvm_close", "hqh_cvm_info", "hqh_cvm_query", "hqh_cvm_grid"]
 
@@ -842,6 +842,54 @@ def peak_fold(steps, samples, quantities, peaks=None, when=None):
                                              ctypes.c_void_p(steps.ctypes.data), ctypes.c_void_p(samples.ctypes.data),
                                              ctypes.c_void_p(peaks.ctypes.data), ctypes.c_void_p(when.ctypes.data)))
     return peaks, when
+
+
+def cum_fold(steps, samples, quantities, threshold=0.0, sums=None, span=None):
+    """hqh_cum_fold: recorder samples [k, npoints, 3 (1 + derivs)] taken at `steps` [k] (as peak_fold's) added into (sums
+    [npoints, nq, 6], span [npoints, nq, 3]), the state Solver.cum_fetch returns; `threshold` a scalar or one value per
+    quantity of the mask.  sums / span None: a fresh state (0; -1, -1, 0); given, they are folded into in place (float64 /
+    int32, C-contiguous) -- two calls in sequence equal one on the concatenation.  Returns (sums, span)."""
+    quantities = int(quantities)
+    nq = bin(quantities & 7).count("1")
+    derivs = 2 if quantities & capi.HQ_PEAK_ACC else 1 if quantities & capi.HQ_PEAK_VEL else 0
+    steps = np.ascontiguousarray(steps, np.int32).reshape(-1)
+    samples = np.ascontiguousarray(samples, np.float64)
+    if samples.ndim != 3 or samples.shape[0] != len(steps) or samples.shape[2] != 3 * (1 + derivs):
+        raise capi.HqError("cum_fold: samples %r do not match %d steps of %d columns" % (samples.shape, len(steps), 3 * (1 + derivs)))
+    npoints = samples.shape[1]
+    thr = np.zeros(3)
+    thr[:nq] = threshold
+    if sums is None:
+        sums = np.zeros((npoints, nq, 6))
+        span = np.zeros((npoints, nq, 3), np.int32)
+        span[:, :, :2] = -1
+    if (sums.dtype != np.float64 or span.dtype != np.int32 or sums.shape != (npoints, nq, 6) or span.shape != (npoints, nq, 3)
+            or not sums.flags.c_contiguous or not span.flags.c_contiguous):
+        raise capi.HqError("cum_fold: sums / span are not a state of %d points and %d quantities" % (npoints, nq))
+    capi._check(load_library().hqh_cum_fold(ctypes.c_int32(npoints), ctypes.c_int32(quantities), ctypes.c_int32(len(steps)),
+                                            ctypes.c_void_p(steps.ctypes.data), ctypes.c_void_p(samples.ctypes.data),
+                                            ctypes.c_void_p(thr.ctypes.data), ctypes.c_void_p(sums.ctypes.data),
+                                            ctypes.c_void_p(span.ctypes.data)))
+    return sums, span
+
+
+def husid_cross(curve_steps, curve, total, fracs, step0=0.0):
+    """hqh_husid_cross: the fractional steps at which Husid curves reach fractions of their totals.  curve [nslots, ...] (any
+    trailing shape: Solver.cum_fetch's [nfilled, npoints, nq, 3] as it is) the running sums at `curve_steps` [nslots], total
+    [...] the final sums, (step0, 0) in front of slot 0.  Returns [..., nfrac]: NaN where the total is 0 or not finite or no
+    stored slot reaches the fraction.  D5-95 = (out[..., 1] - out[..., 0]) dt for fracs = (0.05, 0.95)."""
+    steps = np.ascontiguousarray(curve_steps, np.int32).reshape(-1)
+    curve = np.ascontiguousarray(curve, np.float64)
+    total = np.asarray(total, np.float64, order="C")            # (ascontiguousarray would make a scalar total 1-d)
+    fracs = np.ascontiguousarray(fracs, np.float64).reshape(-1)
+    if curve.shape[:1] != (len(steps),) or curve.shape[1:] != total.shape:
+        raise capi.HqError("husid_cross: curve %r does not match %d steps and totals %r" % (curve.shape, len(steps), total.shape))
+    out = np.full(total.shape + (len(fracs),), np.nan)
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)
+    capi._check(load_library().hqh_husid_cross(ctypes.c_int32(len(steps)), ptr(steps), ctypes.c_double(step0),
+                                               ctypes.c_int64(total.size), ptr(curve), ptr(total), ctypes.c_int32(len(fracs)),
+                                               ptr(fracs), ptr(out)))
+    return out
 
 
 def station_header(derivs=0):

@@ -302,6 +302,25 @@ HQ_API int hqh_station_kinematics(const double* phi, const double* tm1, const do
  * HQ_ERR_ARG for null pointers (where there is something to read), negative counts, quantities 0 or with unknown bits. */
 HQ_API int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps,
                          const double* samples, double* peaks, int32_t* when);
+/* The cumulative-intensity fold on the host (csrc/hq_cumul.h, the text hq_k_cum compiles): recorder samples added into the
+ * state hq_cum_fetch delivers -- the route of a caller without device trackers.  samples, steps and `quantities` as
+ * hqh_peak_fold's; threshold [nq], per quantity of the mask in mask order, finite and >= 0, squared once here.  sums
+ * [npoints][nq][6] and span [npoints][nq][3] are folded INTO: the caller starts them at 0 and (-1, -1, 0), and two calls in
+ * sequence equal one call on the concatenation.  HQ_ERR_ARG for null pointers (where there is something to read), negative
+ * counts, quantities 0 or with unknown bits, a threshold that is negative or not finite. */
+HQ_API int hqh_cum_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps,
+                        const double* samples, const double* threshold, double* sums, int32_t* span);
+/* Where Husid curves cross fractions of their totals (significant durations: D5-95 is the difference of the crossings of
+ * 0.05 and 0.95, times dt).  curve [nslots][nseries] holds the running sum of every series as it stood at curve_steps[k]
+ * (increasing) -- hq_cum_fetch's curve seen as [nfilled][np nq 3] -- and total [nseries] the final sums; (step0, 0) stands
+ * in front of slot 0: the step before the first due one, where the sum was still 0.  For every series and every fraction f,
+ * out[series][f] is the fractional step at which the curve, linear between stored slots, reaches f x total: with k the
+ * smallest slot with curve[k] >= f total, steps[k-1] + (steps[k] - steps[k-1]) (f total - curve[k-1]) / (curve[k] -
+ * curve[k-1]) (steps[k] itself where the two values are equal).  NaN if total is 0 or not finite, or if no stored slot
+ * reaches the fraction.  The caller turns steps into seconds.  HQ_ERR_ARG for null pointers (where there is something to
+ * read) and negative counts. */
+HQ_API int hqh_husid_cross(int32_t nslots, const int32_t* curve_steps, double step0, int64_t nseries, const double* curve,
+                           const double* total, int32_t nfrac, const double* fracs, double* out);
 /* The response-spectrum oscillator on the host (csrc/hq_sdof.h, the text hq_k_spec compiles).  hqh_sdof_coef: the eight
  * coefficients {A11, A12, A21, A22, B11, B12, B21, B22} of the exact step h of x'' + 2 zeta omega x' + omega^2 x = -a_g(t),
  * omega = 2 pi / period, for a piecewise-linear a_g -- a scaled Taylor series of the propagator, no libm: the numbers

@@ -606,6 +606,79 @@ HQ_API int hq_spec_reset(hq_ctx* ctx, int32_t handle);
 HQ_API int hq_spec_clear(hq_ctx* ctx);
 
 /*
+ * Cumulative-intensity trackers (additive under ABI 6): the time integrals landslide, liquefaction and damage models are
+ * written in -- Arias intensity Ia = pi / (2 g) int a^2 dt, cumulative absolute velocity CAV = int |a| dt, the specific
+ * energy density int v^2 dt -- and the durations that go with them, kept ON THE DEVICE.  An integral over time is a
+ * reduction over time in the sense a peak is: a state of fixed size per point folded in place, no ring, no batch cut,
+ * nothing over PCIe until it is fetched.  The other route is a recorder at rate 1 with derivs = 2 and a loop over every
+ * sample on the host (hqh_cum_fold, hq_host.h).
+ * Points, rate, first_step and the mask `quantities` are a peak tracker's.  At the head of every step s >= first_step with
+ * s % rate == 0 -- where hq_k_record sits, on exactly the state hq_gather3 documents -- one launch of hq_k_cum forms the
+ * sample hq_k_record would take at the point (every value widened to double first, csrc/hq_sample.h's order of operations,
+ * / dt and / dt^2 divisions, no contraction: the recorder's sample bit for bit) and adds it in.  Per point and quantity q
+ * of the mask, in the order displacement, velocity, acceleration, the state is (csrc/hq_cumul.h):
+ *   sums[p][q][0..2] = sum of |v_x|, |v_y|, |v_z|         one addition per due sample, in time order
+ *   sums[p][q][3..5] = sum of v_x v_x, v_y v_y, v_z v_z   the product rounded first, then added: never an FMA
+ *   span[p][q][0]    = the first step at which (v_x v_x + v_y v_y) + v_z v_z > threshold[q]^2; -1 = never
+ *   span[p][q][1]    = the last such step; -1 = never
+ *   span[p][q][2]    = the number of such samples
+ * sums always double, in both libraries.  threshold[q] belongs to quantity q of the mask, in mask order; it is squared once,
+ * on the host.  The comparison is strict: a sample exactly at the threshold does not count and a NaN sample never does,
+ * though a NaN does stay in the sums from then on, as in any running sum.
+ * The rectangle rule: the device multiplies by NOTHING, so the state equals hqh_cum_fold of a recorder's samples of the same
+ * run bit for bit.  With h = rate x dt the caller forms CAV = h sums[..][acc][0..2], Ia = pi / (2 g) h sums[..][acc][3..5]
+ * per axis (their sum for the total), the energy density h sums[..][vel][3..5]; the bracketed duration is (span[1] -
+ * span[0]) dt and the uniform duration span[2] h.  As with recorders, step 0 samples the initial state, the sample taken at
+ * the head of step s is the displacement at time s dt (the acceleration the one centred on (s - 1) dt), and the state after the last step is not
+ * sampled until a further step begins.
+ * The Husid curve: with husid_every >= 1 the three sums of squares of every quantity, as they stand after every
+ * husid_every-th due sample (counted from the first due one: samples husid_every, 2 husid_every, ...), are kept in device
+ * memory, husid_slots of them at most; further samples are still folded into the sums, the curve simply ends.  Which sample
+ * fills which slot is accounted on the host when the step is enqueued.  Significant durations (D5-75, D5-95) come out of
+ * one run without a second pass: hqh_husid_cross (hq_host.h) finds where a curve crosses a fraction of its total.
+ * husid_every = husid_slots = 0: no curve.
+ * hq_cum_fetch waits for the enqueued work (as hq_peak_fetch does), copies the state out -- sums [np][nq][6], span
+ * [np][nq][3], nq the number of set bits of `quantities`; curve [nfilled][np][nq][3] and curve_steps [nfilled], the step of
+ * the sample each slot was stored behind, either of which may be NULL (give them room for husid_slots entries) -- and leaves
+ * it in place; *nfilled counts the slots filled or enqueued, *nsamples the due steps folded so far, both accounted on the
+ * host.  It adds exactly the fetched bytes, 60 np nq (+ 24 np nq nfilled with the curve), to hq_info.pcie_d2h_bytes; between
+ * fetches a tracker moves nothing.  hq_cum_load puts fetched values back (a run that restarts from a checkpoint): the same
+ * arrays, curve and curve_steps required unless nfilled == 0, and nfilled must be what nsamples due samples fill, min(nsamples
+ * / husid_every, husid_slots), because the slots go on from nsamples.  hq_cum_reset zeroes the sums and the counts, sets the
+ * first and last steps to -1, nsamples and nfilled to 0.  hq_upload keeps trackers, their state and their curve; the due steps
+ * follow the new step number.  hq_cum_clear drops every cumulative tracker of the context and its memory (hq_destroy does,
+ * too); handles are not reused.  hq_record_clear, hq_snapshot_clear, hq_peak_clear, hq_spec_clear and the hqh_solver_run*
+ * runners leave them alone, and no run call has anything to count for them.  The device memory -- 12 K np of tables (4 np
+ * for K = 1) + np nq (60 + 24 husid_slots) -- counts in hq_info.device_bytes.
+ * Only a tracker with HQ_PEAK_ACC reads u(t - 2 dt), the buffer the step's own kernels overwrite: its due steps hold the
+ * bricks' and the exchange chain's streams back behind the launch, as a recorder's do; other masks hold nothing.
+ * Errors: HQ_ERR_ARG for null pointers, npoints < 0, nodes_per_point not 1 or 8, rate < 1, quantities 0 or with unknown
+ * bits, husid_every and husid_slots not both 0 or both >= 1, a threshold (of a quantity in the mask) that is negative, NaN
+ * or infinite, an id outside [0, nharbored), an unknown handle, an nfilled that does not fit nsamples (hq_cum_load);
+ * HQ_ERR_STATE for HQ_PEAK_ACC in the scatter variant (as hq_gather3); HQ_ERR_NOMEM if the device memory cannot be
+ * allocated -- nothing is kept then.  npoints == 0 is valid.
+ * A context without cumulative trackers enqueues exactly what it did before they existed.
+ */
+typedef struct {
+    int32_t        npoints;
+    int32_t        nodes_per_point;  /* 8: ids [np][8] + phi [np][8]; 1: ids [np], phi ignored (may be NULL) */
+    const int32_t* ids;              /* local node ids, octor numbering */
+    const double*  phi;
+    int32_t        rate, first_step; /* a sample at the head of every step s >= first_step with s % rate == 0 */
+    int32_t        quantities;       /* mask of HQ_PEAK_*; non-zero, no unknown bits */
+    int32_t        husid_every, husid_slots;   /* 0, 0: no curve; else both >= 1 */
+    int32_t        reserved;
+    double         threshold[3];     /* per quantity of the mask, in mask order; finite, >= 0; the rest is not read */
+} hq_cum_desc;
+HQ_API int hq_cum_add(hq_ctx* ctx, const hq_cum_desc* desc, int32_t* handle);
+HQ_API int hq_cum_fetch(hq_ctx* ctx, int32_t handle, double* sums, int32_t* span, double* curve, int32_t* curve_steps,
+                        int32_t* nfilled, int64_t* nsamples);
+HQ_API int hq_cum_load(hq_ctx* ctx, int32_t handle, const double* sums, const int32_t* span, const double* curve,
+                       const int32_t* curve_steps, int32_t nfilled, int64_t nsamples);
+HQ_API int hq_cum_reset(hq_ctx* ctx, int32_t handle);
+HQ_API int hq_cum_clear(hq_ctx* ctx);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
