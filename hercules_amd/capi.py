@@ -292,7 +292,7 @@ class Solver:
         F = np.ascontiguousarray(forces, np.float64)
         nsteps = F.shape[0] if len(ids) else 0
         _check(self._lib.hq_set_source(self._h, ctypes.c_int32(len(ids)), _ptr(ids),
-                                       ctypes.c_int32(step0), ctypes.c_int32(nsteps), _ptr(F)))
+                                       ctypes.c_int32(step0), ctypes.c_int32(nsteps), _ptr(F)), self._lib)
 
     def comm_init(self, id128):
         buf = (ctypes.c_char * 128).from_buffer_copy(bytes(id128))

@@ -2266,6 +2266,7 @@ extern "C" int hq_set_source(hq_ctx* c, int32_t nloaded, const int32_t* loaded, 
     HQ_HIP(hq_quiesce(c));
     for (int32_t i = 0; i < nloaded; i++)
         if (loaded[i] < 0 || loaded[i] >= c->N) return hq_fail(HQ_ERR_ARG, "loaded node id out of range%s", "");
+    const int32_t* caller_ids = loaded;
     std::vector<int32_t> dev_ids;                        /* the loaded nodes in device numbering */
     if (!c->perm.empty() && nloaded > 0) {
         dev_ids.resize((size_t)nloaded);
@@ -2282,6 +2283,19 @@ extern "C" int hq_set_source(hq_ctx* c, int32_t nloaded, const int32_t* loaded, 
         HQ_TRY(c->d_F.upload(F, 3 * (size_t)nloaded * (size_t)nsteps, c->stream));
         c->h2d_bytes += 24 * (int64_t)nloaded * nsteps;
         return HQ_OK;
+    }
+    /* a node named twice: hq_k_source assigns F dt^2 (two threads, one slot) where the brick and patch kernels add both
+     * rows, and the reference's theNodesLoadedList holds every node once -- refused before anything is reset, so the
+     * context keeps the source it had.  Only here: the same-nodes path compared against a list already accepted. */
+    if (nloaded > 1 && nsteps > 0) {
+        std::vector<int32_t> sorted(caller_ids, caller_ids + nloaded);     /* (the renumbering is one to one) */
+        std::sort(sorted.begin(), sorted.end());
+        const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+        if (twice != sorted.end()) {
+            char n[32];
+            snprintf(n, sizeof n, "%d", *twice);
+            return hq_fail(HQ_ERR_ARG, "loaded node %s is named twice in one list (every node once, as theNodesLoadedList)", n);
+        }
     }
     c->d_loaded.reset();
     c->d_F.reset();

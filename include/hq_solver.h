@@ -366,6 +366,13 @@ HQ_API int hq_group_run(hq_ctx** ctxs, int32_t n, int32_t nsteps);
  * payload of force_process.<rank> (quakesource.c:2453-2466).
  * Replaces: read_myForces (psolve.c:3651-3667) + compute_addforce_s (:5912-5928).
  * Steps outside the window apply no source.
+ * Every node is named at most once, as in the reference's theNodesLoadedList:
+ * compute_addforce_s ASSIGNS F dt^2, the scatter variant's source kernel does the
+ * same and the brick and patch kernels ADD it, so a node named twice would get
+ * one row in one variant and the sum in the other.  Such a list is refused with
+ * HQ_ERR_ARG (hq_last_error() names the node) and the context keeps the source
+ * it had.  A call with the same node list as the last accepted one only uploads
+ * the force table and is not checked again.
  */
 HQ_API int hq_set_source(hq_ctx* ctx, int32_t nloaded, const int32_t* loaded_lnid,
                          int32_t step0, int32_t nsteps, const double* F);

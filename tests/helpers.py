@@ -348,18 +348,16 @@ def solver_desc(p, pack=False, precision="f64"):
 # ---------------------------------------------------------------------------------------------
 # one step from two independent fields, term by term (tests/test_step_terms_cpu.py, tests/test_gpu_step_terms.py)
 # ---------------------------------------------------------------------------------------------
-def extended_step(lnid, etable, ntable, u1, u2, dangling=None):
-    """The oracle's step (oracle/herc_oracle.c: ho_solver_run with the conventional element matrices) restated in
-    np.longdouble, the inputs taken as given and widened: element forces -(c1 K1 + c2 K2) u1 - (c3 K1 + c4 K2)(u1 - u2)
-    with K1, K2 of ho.compute_K(), compute_adjust DISTRIBUTION of the forces, the per-axis update
-    (f + m2[d] u1 - m1[d] u2) / m0 with the 7-double n_t row, compute_adjust ASSIGNMENT.
-    -> (ref [N, 3] = the new displacement, T [N, 3] = the same expression with every product replaced by its absolute
-    value: the node's own scale of summed magnitudes), both np.longdouble."""
+def extended_element_sums(lnid, etable, N, u1, u2):
+    """The element loops of extended_step alone: (force [N, 3], tf [N, 3]) in np.longdouble, the stiffness and damping
+    forces summed per node and the same sums of absolute products.  They depend on the mesh, the eTable and the fields
+    only, so the references of one (mesh, damping, precision) -- unloaded, every node loaded, every third -- share them
+    (extended_step(..., sums=) takes them read-only and copies)."""
     L = np.longdouble
     assert np.finfo(L).eps < 1e-18, "np.longdouble is no wider than double here: the test modules skip before they get here"
     lnid = np.asarray(lnid, np.int64)
-    E, N = len(lnid), len(ntable)
-    et, nt = np.asarray(etable).astype(L), np.asarray(ntable).astype(L)
+    E = len(lnid)
+    et = np.asarray(etable).astype(L)
     u1, u2 = np.asarray(u1).astype(L), np.asarray(u2).astype(L)
     # [8][8][3][3] blocks -> [24 = (i, k)][24 = (j, l)]
     A1, A2 = [np.asarray(K).reshape(8, 8, 3, 3).transpose(0, 2, 1, 3).reshape(24, 24).astype(L) for K in ho.compute_K()]
@@ -372,6 +370,41 @@ def extended_step(lnid, etable, ntable, u1, u2, dangling=None):
     force, tf = np.zeros((N, 3), L), np.zeros((N, 3), L)
     np.add.at(force, lnid.reshape(-1), f.reshape(-1, 3))
     np.add.at(tf, lnid.reshape(-1), t.reshape(-1, 3))
+    return force, tf
+
+
+def extended_step(lnid, etable, ntable, u1, u2, dangling=None, loaded=None, F=None, dt=None, sums=None):
+    """The oracle's step (oracle/herc_oracle.c: ho_solver_run with the conventional element matrices) restated in
+    np.longdouble, the inputs taken as given and widened: element forces -(c1 K1 + c2 K2) u1 - (c3 K1 + c4 K2)(u1 - u2)
+    with K1, K2 of ho.compute_K(), compute_adjust DISTRIBUTION of the forces, the per-axis update
+    (f + m2[d] u1 - m1[d] u2) / m0 with the 7-double n_t row, compute_adjust ASSIGNMENT.
+    loaded, F [len(loaded), 3] (double), dt: compute_addforce_s (psolve.c:5912-5928) -- force[loaded] gets F dt^2, dt^2
+    formed in np.longdouble from the double dt, and T gets |F dt^2| -- BEFORE the hanging-node distribution, as the
+    reference assigns the load ahead of the element loops and distributes the sum of both (psolve.c:5936-5987).  Every
+    node is named once.  F may be a list of such tables (the ranks' loads on one node): force gets their sum and T the
+    sum of their absolute values, not the absolute value of their sum -- the terms may cancel.
+    sums: extended_element_sums(...) of the same mesh and fields, computed elsewhere (left unchanged).
+    -> (ref [N, 3] = the new displacement, T [N, 3] = the same expression with every product replaced by its absolute
+    value: the node's own scale of summed magnitudes), both np.longdouble."""
+    L = np.longdouble
+    assert np.finfo(L).eps < 1e-18, "np.longdouble is no wider than double here: the test modules skip before they get here"
+    N = len(ntable)
+    nt = np.asarray(ntable).astype(L)
+    if sums is None:
+        force, tf = extended_element_sums(lnid, etable, N, u1, u2)
+    else:
+        force, tf = sums[0].copy(), sums[1].copy()
+    u1, u2 = np.asarray(u1).astype(L), np.asarray(u2).astype(L)
+    if loaded is not None and len(loaded):
+        ld = np.asarray(loaded, np.int64)
+        assert len(np.unique(ld)) == len(ld) and dt is not None
+        dt2 = L(float(dt)) * L(float(dt))
+        for Fk in (F if isinstance(F, (list, tuple)) else [F]):
+            Fk = np.asarray(Fk)
+            assert Fk.dtype == np.float64 and Fk.shape == (len(ld), 3)
+            load = Fk.astype(L) * dt2
+            force[ld] += load
+            tf[ld] += np.abs(load)
     if dangling is not None and len(dangling[0]):
         ids, ptr, anc = [np.asarray(a, np.int64) for a in dangling]
         deps = np.diff(ptr)
@@ -386,6 +419,19 @@ def extended_step(lnid, etable, ntable, u1, u2, dangling=None):
             np.add.at(mean, np.repeat(np.arange(len(ids)), deps), table[anc] / np.repeat(deps, deps)[:, None].astype(L))
             table[ids] = mean
     return ref, T
+
+
+def oracle_loaded_step(p, nt, u1, u2, loaded, F, etable=None):
+    """The C oracle's new displacement from tm1 = u1, tm2 = u2 with the nodes `loaded` forced by F [len(loaded), 3]
+    (double, as hq_set_source takes it), in nt's type: the twin of extended_step(..., loaded, F, dt).  p: a step_mesh
+    (lnid, etable, dt, kind, dangling).  The float build keeps its force accumulator in float, so F dt^2 is rounded
+    before the element sums are added: the reference's own behaviour, and not what the float library does."""
+    o1, o2 = u2.copy(), u1.copy()
+    ho.solver_run(p["lnid"], np.ascontiguousarray(p["etable"] if etable is None else etable, np.float64), np.ascontiguousarray(nt),
+                  o1, o2, 0, 1, p["dt"], damping=p["kind"], loaded_lnid=np.ascontiguousarray(loaded, np.int32),
+                  forces=np.ascontiguousarray(F, np.float64)[None], dangling=p["dangling"])
+    assert np.array_equal(o1, u1)
+    return o2
 
 
 def step_fields(n, seed, dangling=None, real=np.float64):

@@ -68,7 +68,20 @@ update of hq_k_interface_update do not depend on how the records travel.
     hq_k_brick on the box, 2 ranks 1.72 | 1.12, 8 ranks 1.72 | 1.21 (overlap, brick_by_component, no_fused_share alike)
     hq_k_patch_stencil on the boxes without bricks: 2 ranks 1.73 | 1.05, 8 ranks 1.84 | 1.37
     float state: 0.992 (c5_gradient_branch on 8), 0.975 (two_level), 0.992 (box), 0.995 (IPC between processes) of the f32 bound
-59 cases in 26 s on the device (50 in 25 s before the nine float twins, which take 0.1 - 0.7 s each); the slowest are the
+The same step LOADED (LOADED_CASES, loaded_reference below): every rank calls hq_set_source for ALL the nodes it harbors with
+forces of its own ahead of the step, so the load meets every stiffness and damping sum on its way through the interface
+launch, d_iforce, the contribution exchange and the hanging-node schedules; hanging nodes with anchors on other ranks are
+loaded on both sides.  The reference is the global extended step loaded with the sum over the ranks, T with sum_r |F_r dt^2|
+(not |sum_r F_r| dt^2: the device sums the ranks' contributions in messenger order and they may cancel); B_oracle = the
+single-rank C oracle on the assembled tables with the summed load, pinned below 4 by tests/test_loaded_step_cpu.py:
+    c5_gradient_branch on 8: 3.22 (float 3.03)   het70x20x12 on 3: 3.43   two_level on 5: 2.04   box 32x16x16 on 2: 2.19 (float
+    2.12)   box 32x32x16 on 2 without bricks: 2.49
+Measured on an MI355X (all | owned interface = non-owned | hanging): c5_gradient_branch on 8, patch, overlap 0 and 1:
+5.09 | 1.94 | 4.19; scatter 2.65 | 2.65 | 2.02; het70x20x12 on 3 packed 3.82 | 2.21; two_level on 5 1.96 | 1.20 | 1.30; the brick
+box 1.81 | 1.21; the stencil box 1.59 | 1.30; the float twins (c5 on 8, the brick box): 0 mismatches, 0 off float32(ref),
+undetermined 0 of 17 550 and 1 of 28 611 (the reference side's own count), 0.997 and 0.987 of the f32 bound.  Not covered: the
+routes between processes carry the same d_iforce records whatever filled them; the unloaded cases cover them.
+68 cases in 26 s on the device, the nine loaded ones 1.6 s of it (59 in 26 s before them; 50 in 25 s before the nine float twins, which take 0.1 - 0.7 s each); the slowest are the
 four between processes (2.6 - 3.9 s: five processes start), of the others the first of a problem (2.1 s with its
 reference), then 0.2 - 0.7 s each."""
 import numpy as np
@@ -323,6 +336,90 @@ def test_one_step_from_independent_fields_on_partitions(case):
         close_all(solvers, boxes)
     assert nonfinite == [0] * c["nranks"], nonfinite
     check_fields(case, q, [g[0] for g in got], [g[1] for g in got], B, family)
+
+
+# ---------------------------------------------------------------------------------------------
+# the same step LOADED: every rank loads all it harbors, on a field that moves
+# ---------------------------------------------------------------------------------------------
+LOADED_CASES = {
+    "loaded-c5-8-patch-ov0": _oct(C5, 8, 0, route=NOBRICKS),
+    "loaded-c5-8-patch-ov1": _oct(C5, 8, 1, route=NOBRICKS),
+    "loaded-c5-8-scatter": _oct(C5, 8, 1, variant=SCATTER, route=("scatter",)),
+    "loaded-het-3-packed": _oct("het70x20x12", 3, 1, pack=True, route=("het",)),
+    "loaded-two_level-5": _oct("two_level", 5, 1, route=NOBRICKS),
+    "loaded-box-2": _box(2, 1),
+    "loaded-box-2-stencil": _box(2, 0, {"no_bricks": 1}),
+    "loaded-f32-c5-8-patch": _oct(C5, 8, 1, precision="f32", route=NOBRICKS),
+    "loaded-f32-box-2": _box(2, 1, precision="f32"),
+}
+LOADED_SEED = 31000                                              # rank r: H.rest_forces(..., LOADED_SEED + r), as tests/test_gpu_sources.py
+_LOADED = {}
+
+
+def loaded_reference(c):
+    """The loaded step of a case's problem: rank r loads ALL the nodes it harbors (owned, merely harbored, hanging) with
+    forces of its own, H.rest_forces on the global n_t rows with seed LOADED_SEED + r, taken at its nodes.  The reference is
+    the global H.extended_step loaded with every rank's table in turn -- force gets the sum over ranks and T the sum of
+    |F_r dt^2|, not |sum F_r| dt^2: the device sums the ranks' contributions in messenger order and they may cancel.
+    B_oracle: the single-rank C oracle on the assembled global tables with the summed load (double sum in rank order).
+    Built once per problem, read-only.  -> dict(Fr = per rank [its nodes, 3], total [N, 3], ref, T, B_oracle)"""
+    key = (c["kind"], c["mesh"], c["nranks"], c["damping"], c["precision"])
+    if key in _LOADED:
+        return _LOADED[key]
+    from oracle import herc_oracle as ho
+    q = problem_of(c)
+    N = q["N"]
+    tables, total = [], np.zeros((N, 3))
+    for r, g in enumerate(q["gid"]):
+        Fk = np.zeros((N, 3))
+        Fk[g] = H.rest_forces(q["ntable"][:, 0], q["dt"], LOADED_SEED + r)[g]
+        tables.append(Fk)
+        total += Fk
+    every = np.arange(N, dtype=np.int32)
+    ref, T = H.extended_step(q["lnid"], q["etable"], q["ntable"], q["u1"], q["u2"], q["dangling"], loaded=every, F=tables, dt=q["dt"])
+    o1, o2 = np.array(q["u2"]), np.array(q["u1"])
+    ho.solver_run(np.ascontiguousarray(q["lnid"], np.int32), np.ascontiguousarray(q["etable"]), np.ascontiguousarray(q["ntable"]), o1, o2, 0, 1,
+                  q["dt"], damping=q.get("kind", ho.DAMP_RAYLEIGH), loaded_lnid=every, forces=total[None], dangling=q["dangling"])
+    b = float((np.abs(o2 - ref) / ((2.0 ** -24 if c["precision"] == "f32" else EPS) * T)).max())
+    out = H._freeze(dict(Fr=[np.ascontiguousarray(Fk[g]) for Fk, g in zip(tables, q["gid"])], total=total, ref=ref, T=T, B_oracle=b,
+                         oracle=o2))
+    _LOADED[key] = out
+    return out
+
+
+def loaded_bound_factor(c):
+    """B = 16 * max(B_oracle, 4), B_oracle of the DOUBLE oracle's loaded step on that problem."""
+    b = loaded_reference(dict(c, precision="f64"))["B_oracle"]
+    assert b <= 64.0, b                                          # (a broken reference cannot raise the bar)
+    return 16.0 * max(b, 4.0)
+
+
+@pytest.mark.parametrize("case", list(LOADED_CASES), ids=list(LOADED_CASES))
+def test_one_loaded_step_on_partitions(case):
+    """hq_set_source on every rank ahead of the step from independent fields: the load through the interface launch of the
+    patch kernels, d_iforce, the contribution exchange and the hanging-node schedules, where every stiffness and damping
+    sum is in play -- hanging nodes with anchors on other ranks are loaded on both sides (c5_gradient_branch, two_level).
+    The routes between processes carry the same d_iforce records whatever filled them: the unloaded cases cover them."""
+    from hercules_amd import capi
+    c = LOADED_CASES[case]
+    q = problem_of(c)
+    L = loaded_reference(c)
+    B = loaded_bound_factor(c)
+    solvers, boxes = make_solvers(c, q)
+    try:
+        for r, s in enumerate(solvers):
+            s.set_source(np.arange(len(q["gid"][r]), dtype=np.int32), L["Fr"][r][None])
+        capi.group_link(solvers)
+        infos = check_route(c, solvers, q)
+        family = (sorted({s.dominant_kernel() for s in solvers}),) + tuple(
+            "%s=%d" % (k, sum(i[k] for i in infos)) for k in ("brick_units", "brick_units_het", "brick_units_packed", "npatches", "stencil_patches"))
+        capi.group_run(solvers, 1)
+        got = [s.download() for s in solvers]
+        nonfinite = [s.check_finite() for s in solvers]
+    finally:
+        close_all(solvers, boxes)
+    assert nonfinite == [0] * c["nranks"], nonfinite
+    check_fields(case, dict(q, ref=L["ref"], T=L["T"]), [g[0] for g in got], [g[1] for g in got], B, family)
 
 
 # ---------------------------------------------------------------------------------------------
