@@ -193,6 +193,23 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+_PAD = np.zeros(1)
+
+
+def _ptr_or_pad(a):
+    """_ptr, but an empty array has no address worth passing: a pad's instead (nothing is read or written there)."""
+    return None if a is None else _ptr(a if a.size else _PAD)
+
+
+# the trackers' kinds: the prefix of their entry points -> the word of their error texts
+_TRACKER_KINDS = {"peak": "peak", "spec": "spectrum", "cum": "cumulative"}
+
+
+def _no_trackers():
+    """Solver._trackers of a fresh context: per kind, handle -> the shape its fetch and load size their arrays by."""
+    return {kind: {} for kind in _TRACKER_KINDS}
+
+
 def _schedule(sched, keep):
     """sched = {"c": [(procid, mapping ndarray), ...], "s": [...]} or None."""
     out = _Schedule()
@@ -264,6 +281,7 @@ class Solver:
         self._h = ctypes.c_void_p()
         self.N, self.E = d.nharbored, d.lenum
         self._lib = lib
+        self._trackers = _no_trackers()
         if options is None:
             _check(lib.hq_create(ctypes.byref(d), ctypes.c_int(device), ctypes.byref(self._h)), lib)
         else:
@@ -466,98 +484,87 @@ class Solver:
         _check(self._lib.hq_snapshot_clear(self._h), self._lib)
         self._snapshots = {}
 
+    @staticmethod
+    def _points(ids, phi, who):
+        """(ids, phi, nodes per point) of a tracker's description: ids [n] single nodes with phi None, ids and phi [n,8] else."""
+        if phi is None:
+            return np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32), None, 1
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
+        phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
+        if len(ids) != len(phi):
+            raise HqError("%s: %d rows of ids, %d of phi" % (who, len(ids), len(phi)))
+        return ids, phi, 8
+
+    def _tracker_add(self, kind, desc, shape):
+        """hq_<kind>_add; `shape` is what the kind's fetch and load size their arrays by."""
+        h = ctypes.c_int32(-1)
+        _check(getattr(self._lib, "hq_%s_add" % kind)(self._h, ctypes.byref(desc), ctypes.byref(h)), self._lib)
+        self._trackers[kind][h.value] = shape
+        return h.value
+
+    def _tracker_shape(self, kind, handle):
+        if handle not in self._trackers[kind]:
+            raise HqError("unknown %s tracker handle %r" % (_TRACKER_KINDS[kind], handle))
+        return self._trackers[kind][handle]
+
+    def _tracker_reset(self, kind, handle):
+        _check(getattr(self._lib, "hq_%s_reset" % kind)(self._h, ctypes.c_int32(handle)), self._lib)
+
+    def _tracker_clear(self, kind):
+        _check(getattr(self._lib, "hq_%s_clear" % kind)(self._h), self._lib)
+        self._trackers[kind] = {}
+
     def peak_add(self, ids, phi=None, rate=1, first_step=0, quantities=HQ_PEAK_VEL):
         """hq_peak_add: a peak-motion tracker.  phi [n,8] with ids [n,8]: points inside elements, as record_add's; phi
         None: ids [n] are single nodes (a surface map).  A sample is folded in at the head of every step s >= first_step
         with s % rate == 0; `quantities` a mask of HQ_PEAK_DISP | VEL | ACC.  Returns its handle."""
-        if phi is None:
-            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32)
-            k = 1
-        else:
-            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
-            phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
-            if len(ids) != len(phi):
-                raise HqError("peak_add: %d rows of ids, %d of phi" % (len(ids), len(phi)))
-            k = 8
-        d = _PeakDesc(len(ids), k, ids.ctypes.data, None if phi is None else phi.ctypes.data, int(rate), int(first_step),
-                      int(quantities), 0)
-        h = ctypes.c_int32(-1)
-        _check(self._lib.hq_peak_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
-        if not hasattr(self, "_peaks"):
-            self._peaks = {}
-        self._peaks[h.value] = (len(ids), bin(int(quantities) & 7).count("1"))
-        return h.value
-
-    def _peak_shape(self, handle):
-        if handle not in getattr(self, "_peaks", {}):
-            raise HqError("unknown peak tracker handle %r" % (handle,))
-        return self._peaks[handle]
+        ids, phi, k = self._points(ids, phi, "peak_add")
+        d = _PeakDesc(len(ids), k, _ptr(ids), _ptr(phi), int(rate), int(first_step), int(quantities), 0)
+        return self._tracker_add("peak", d, (len(ids), bin(int(quantities) & 7).count("1")))
 
     def peak_fetch(self, handle):
         """hq_peak_fetch: (peaks [npoints, nq, 5] float64, when [npoints, nq, 2] int32, nsamples) -- per quantity of the
         mask max |x|, |y|, |z|, the horizontal and the total SQUARED, and the steps the last two were last raised at (-1:
         never).  Waits for the enqueued steps; the state stays on the device."""
-        npoints, nq = self._peak_shape(handle)
+        npoints, nq = self._tracker_shape("peak", handle)
         peaks = np.zeros((npoints, nq, 5))
         when = np.full((npoints, nq, 2), -1, np.int32)
         n = ctypes.c_int64()
-        pad = np.zeros(1)                                       # (an empty array has no address worth passing)
-        _check(self._lib.hq_peak_fetch(self._h, ctypes.c_int32(handle), _ptr(peaks if peaks.size else pad),
-                                       _ptr(when if when.size else pad), ctypes.byref(n)), self._lib)
+        _check(self._lib.hq_peak_fetch(self._h, ctypes.c_int32(handle), _ptr_or_pad(peaks), _ptr_or_pad(when), ctypes.byref(n)), self._lib)
         return peaks, when, int(n.value)
 
     def peak_load(self, handle, peaks, when, nsamples):
         """hq_peak_load: put back what peak_fetch returned (a run that restarts from a checkpoint)."""
-        npoints, nq = self._peak_shape(handle)
+        npoints, nq = self._tracker_shape("peak", handle)
         peaks = np.ascontiguousarray(peaks, np.float64)
         when = np.ascontiguousarray(when, np.int32)
         if peaks.shape != (npoints, nq, 5) or when.shape != (npoints, nq, 2):
             raise HqError("peak_load: the arrays are not those of peak_fetch")
-        pad = np.zeros(1)
-        _check(self._lib.hq_peak_load(self._h, ctypes.c_int32(handle), _ptr(peaks if peaks.size else pad),
-                                      _ptr(when if when.size else pad), ctypes.c_int64(int(nsamples))), self._lib)
+        _check(self._lib.hq_peak_load(self._h, ctypes.c_int32(handle), _ptr_or_pad(peaks), _ptr_or_pad(when),
+                                      ctypes.c_int64(int(nsamples))), self._lib)
 
     def peak_reset(self, handle):
         """hq_peak_reset: peaks 0, when -1, nsamples 0."""
-        _check(self._lib.hq_peak_reset(self._h, ctypes.c_int32(handle)), self._lib)
+        self._tracker_reset("peak", handle)
 
     def peak_clear(self):
         """hq_peak_clear: drop every tracker of the context and its device memory."""
-        _check(self._lib.hq_peak_clear(self._h), self._lib)
-        self._peaks = {}
+        self._tracker_clear("peak")
 
     def spec_add(self, ids, phi=None, rate=1, first_step=0, periods=(1.0,), damping=0.05):
         """hq_spec_add: a response-spectrum tracker.  Points as peak_add's (phi None: single nodes).  At the head of every
         step s >= first_step with s % rate == 0 the point's acceleration sample drives one damped oscillator per period
         (seconds) and axis, step h = rate dt; the maxima of |x| are SD -- PSV = omega SD, PSA = omega^2 SD are the
         caller's.  Returns its handle."""
-        if phi is None:
-            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32)
-            k = 1
-        else:
-            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
-            phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
-            if len(ids) != len(phi):
-                raise HqError("spec_add: %d rows of ids, %d of phi" % (len(ids), len(phi)))
-            k = 8
+        ids, phi, k = self._points(ids, phi, "spec_add")
         periods = np.ascontiguousarray(np.asarray(periods, np.float64).reshape(-1))
-        d = _SpecDesc(len(ids), k, ids.ctypes.data, None if phi is None else phi.ctypes.data, int(rate), int(first_step),
-                      len(periods), 0, periods.ctypes.data if len(periods) else None, float(damping))
-        h = ctypes.c_int32(-1)
-        _check(self._lib.hq_spec_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
-        if not hasattr(self, "_specs"):
-            self._specs = {}
-        self._specs[h.value] = (len(ids), len(periods))
-        return h.value
-
-    def _spec_shape(self, handle):
-        if handle not in getattr(self, "_specs", {}):
-            raise HqError("unknown spectrum tracker handle %r" % (handle,))
-        return self._specs[handle]
+        d = _SpecDesc(len(ids), k, _ptr(ids), _ptr(phi), int(rate), int(first_step), len(periods), 0,
+                      _ptr(periods) if len(periods) else None, float(damping))
+        return self._tracker_add("spec", d, (len(ids), len(periods)))
 
     def spec_coefficients(self, handle):
         """hq_spec_coefficients: [nperiods, 8] = A11, A12, A21, A22, B11, B12, B21, B22 per period, as the kernel reads them."""
-        _, nper = self._spec_shape(handle)
+        _, nper = self._tracker_shape("spec", handle)
         coef = np.zeros((nper, 8))
         _check(self._lib.hq_spec_coefficients(self._h, ctypes.c_int32(handle), _ptr(coef)), self._lib)
         return coef
@@ -566,19 +573,18 @@ class Solver:
         """hq_spec_fetch: (sd [npoints, nperiods, 4], osc [npoints, nperiods, 2, 3] or None, aprev [npoints, 3] or None,
         nsamples) -- per period max |x| per axis and the horizontal resultant SQUARED; the oscillators (x then v) and the
         last sample as they stand.  Waits for the enqueued steps; the state stays on the device."""
-        npoints, nper = self._spec_shape(handle)
+        npoints, nper = self._tracker_shape("spec", handle)
         sd = np.zeros((npoints, nper, 4))
         o = np.zeros((npoints, nper, 2, 3)) if osc else None
         a = np.zeros((npoints, 3)) if aprev else None
         n = ctypes.c_int64()
-        pad = np.zeros(1)                                       # (an empty array has no address worth passing)
-        arg = lambda x: None if x is None else _ptr(x if x.size else pad)
-        _check(self._lib.hq_spec_fetch(self._h, ctypes.c_int32(handle), arg(sd), arg(o), arg(a), ctypes.byref(n)), self._lib)
+        _check(self._lib.hq_spec_fetch(self._h, ctypes.c_int32(handle), _ptr_or_pad(sd), _ptr_or_pad(o), _ptr_or_pad(a),
+                                       ctypes.byref(n)), self._lib)
         return sd, o, a, int(n.value)
 
     def spec_load(self, handle, sd, osc, aprev, nsamples):
         """hq_spec_load: put back what spec_fetch returned (a run that restarts from a checkpoint)."""
-        npoints, nper = self._spec_shape(handle)
+        npoints, nper = self._tracker_shape("spec", handle)
         if sd is None or osc is None or aprev is None:
             raise HqError("spec_load: sd, osc and aprev are all required")
         sd = np.ascontiguousarray(sd, np.float64)
@@ -586,19 +592,16 @@ class Solver:
         aprev = np.ascontiguousarray(aprev, np.float64)
         if sd.shape != (npoints, nper, 4) or osc.shape != (npoints, nper, 2, 3) or aprev.shape != (npoints, 3):
             raise HqError("spec_load: the arrays are not those of spec_fetch")
-        pad = np.zeros(1)
-        _check(self._lib.hq_spec_load(self._h, ctypes.c_int32(handle), _ptr(sd if sd.size else pad),
-                                      _ptr(osc if osc.size else pad), _ptr(aprev if aprev.size else pad),
+        _check(self._lib.hq_spec_load(self._h, ctypes.c_int32(handle), _ptr_or_pad(sd), _ptr_or_pad(osc), _ptr_or_pad(aprev),
                                       ctypes.c_int64(int(nsamples))), self._lib)
 
     def spec_reset(self, handle):
         """hq_spec_reset: the oscillators at rest, sd 0, the previous sample 0, nsamples 0."""
-        _check(self._lib.hq_spec_reset(self._h, ctypes.c_int32(handle)), self._lib)
+        self._tracker_reset("spec", handle)
 
     def spec_clear(self):
         """hq_spec_clear: drop every spectrum tracker of the context and its device memory."""
-        _check(self._lib.hq_spec_clear(self._h), self._lib)
-        self._specs = {}
+        self._tracker_clear("spec")
 
     def cum_add(self, ids, phi=None, rate=1, first_step=0, quantities=HQ_PEAK_ACC, threshold=0.0, husid_every=0, husid_slots=0):
         """hq_cum_add: a cumulative-intensity tracker (Arias, CAV, energy density, durations).  Points as peak_add's (phi
@@ -606,32 +609,14 @@ class Solver:
         the mask is added into sum |v| and sum v v per axis, and counted where its total exceeds `threshold` (a scalar, or
         one value per quantity of the mask in mask order).  husid_every >= 1: the sums of squares after every
         husid_every-th due sample are kept, husid_slots of them (the Husid curve).  Returns its handle."""
-        if phi is None:
-            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1), np.int32)
-            k = 1
-        else:
-            ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
-            phi = np.ascontiguousarray(np.asarray(phi).reshape(-1, 8), np.float64)
-            if len(ids) != len(phi):
-                raise HqError("cum_add: %d rows of ids, %d of phi" % (len(ids), len(phi)))
-            k = 8
+        ids, phi, k = self._points(ids, phi, "cum_add")
         nq = bin(int(quantities) & 7).count("1")
         thr = np.broadcast_to(np.asarray(threshold, np.float64), (nq,)) if np.ndim(threshold) == 0 else np.asarray(threshold, np.float64).reshape(-1)
         if len(thr) != nq:
             raise HqError("cum_add: %d thresholds for %d quantities" % (len(thr), nq))
-        d = _CumDesc(len(ids), k, ids.ctypes.data, None if phi is None else phi.ctypes.data, int(rate), int(first_step),
-                     int(quantities), int(husid_every), int(husid_slots), 0, (ctypes.c_double * 3)(*([float(v) for v in thr] + [0.0] * (3 - nq))))
-        h = ctypes.c_int32(-1)
-        _check(self._lib.hq_cum_add(self._h, ctypes.byref(d), ctypes.byref(h)), self._lib)
-        if not hasattr(self, "_cums"):
-            self._cums = {}
-        self._cums[h.value] = (len(ids), nq, int(husid_slots))
-        return h.value
-
-    def _cum_shape(self, handle):
-        if handle not in getattr(self, "_cums", {}):
-            raise HqError("unknown cumulative tracker handle %r" % (handle,))
-        return self._cums[handle]
+        d = _CumDesc(len(ids), k, _ptr(ids), _ptr(phi), int(rate), int(first_step), int(quantities), int(husid_every),
+                     int(husid_slots), 0, (ctypes.c_double * 3)(*([float(v) for v in thr] + [0.0] * (3 - nq))))
+        return self._tracker_add("cum", d, (len(ids), nq, int(husid_slots)))
 
     def cum_fetch(self, handle, curve=True):
         """hq_cum_fetch: (sums [npoints, nq, 6] float64, span [npoints, nq, 3] int32, curve [nfilled, npoints, nq, 3] or None,
@@ -639,21 +624,19 @@ class Solver:
         the last step over the threshold (-1: never) and the count of such samples; the sums of squares as they stood behind
         the samples of curve_steps.  Nothing is multiplied by the step h = rate dt: that is the caller's.  Waits for the
         enqueued steps; the state stays on the device."""
-        npoints, nq, slots = self._cum_shape(handle)
+        npoints, nq, slots = self._tracker_shape("cum", handle)
         sums = np.zeros((npoints, nq, 6))
         span = np.zeros((npoints, nq, 3), np.int32)
         cv = np.zeros((max(slots, 1), npoints, nq, 3)) if curve else None
         steps = np.zeros(max(slots, 1), np.int32)
         nf, n = ctypes.c_int32(), ctypes.c_int64()
-        pad = np.zeros(1)                                       # (an empty array has no address worth passing)
-        arg = lambda x: None if x is None else _ptr(x if x.size else pad)
-        _check(self._lib.hq_cum_fetch(self._h, ctypes.c_int32(handle), arg(sums), arg(span), arg(cv), _ptr(steps),
-                                      ctypes.byref(nf), ctypes.byref(n)), self._lib)
+        _check(self._lib.hq_cum_fetch(self._h, ctypes.c_int32(handle), _ptr_or_pad(sums), _ptr_or_pad(span), _ptr_or_pad(cv),
+                                      _ptr(steps), ctypes.byref(nf), ctypes.byref(n)), self._lib)
         return sums, span, (cv[:nf.value].copy() if curve else None), steps[:nf.value].copy(), int(n.value)
 
     def cum_load(self, handle, sums, span, curve, curve_steps, nsamples):
         """hq_cum_load: put back what cum_fetch returned (a run that restarts from a checkpoint)."""
-        npoints, nq, _ = self._cum_shape(handle)
+        npoints, nq, _ = self._tracker_shape("cum", handle)
         sums = np.ascontiguousarray(sums, np.float64)
         span = np.ascontiguousarray(span, np.int32)
         steps = np.ascontiguousarray(curve_steps, np.int32).reshape(-1)
@@ -663,19 +646,16 @@ class Solver:
         cv = np.zeros((0, npoints, nq, 3)) if curve is None else np.ascontiguousarray(curve, np.float64)
         if sums.shape != (npoints, nq, 6) or span.shape != (npoints, nq, 3) or cv.shape != (nf, npoints, nq, 3):
             raise HqError("cum_load: the arrays are not those of cum_fetch")
-        pad = np.zeros(1)
-        arg = lambda x: _ptr(x if x.size else pad)
-        _check(self._lib.hq_cum_load(self._h, ctypes.c_int32(handle), arg(sums), arg(span), arg(cv), arg(steps),
-                                     ctypes.c_int32(nf), ctypes.c_int64(int(nsamples))), self._lib)
+        _check(self._lib.hq_cum_load(self._h, ctypes.c_int32(handle), _ptr_or_pad(sums), _ptr_or_pad(span), _ptr_or_pad(cv),
+                                     _ptr_or_pad(steps), ctypes.c_int32(nf), ctypes.c_int64(int(nsamples))), self._lib)
 
     def cum_reset(self, handle):
         """hq_cum_reset: sums and counts 0, first / last step -1, no Husid slot filled, nsamples 0."""
-        _check(self._lib.hq_cum_reset(self._h, ctypes.c_int32(handle)), self._lib)
+        self._tracker_reset("cum", handle)
 
     def cum_clear(self):
         """hq_cum_clear: drop every cumulative tracker of the context and its device memory."""
-        _check(self._lib.hq_cum_clear(self._h), self._lib)
-        self._cums = {}
+        self._tracker_clear("cum")
 
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)

@@ -92,6 +92,7 @@ public:
     template <typename V>
     int put(int64_t* ledger, const V& v, hipStream_t st) { return put(ledger, v.data(), v.size(), st); }
     T* get() const { return p_; }
+    size_t bytes() const { return bytes_; }
     operator T*() const { return p_; }
 };
 

@@ -241,7 +241,7 @@ struct hq_ctx {
     int64_t clk_steps = 0;
     /* device outputs (recorders, trackers, snapshots).  hq_outputs.h, included ahead of hq_phase, DEFINES the structs: no code
      * above that include may touch recs, peaks, specs, cums or snaps.  ev_output: recorded behind a due step's launches for the streams to wait on */
-    struct hq_output; struct hq_recorder; struct hq_peak_tracker; struct hq_spec_tracker; struct hq_cum_tracker; struct hq_snapshot;
+    struct hq_output; struct hq_recorder; struct hq_tracker; struct hq_peak_tracker; struct hq_spec_tracker; struct hq_cum_tracker; struct hq_snapshot;
     std::vector<hq_recorder> recs;
     int32_t rec_next_id = 0;
     std::vector<hq_peak_tracker> peaks;

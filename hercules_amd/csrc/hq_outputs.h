@@ -2,9 +2,15 @@
  * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion, response-spectrum
  * and cumulative-intensity trackers, field snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at
  * the head of a step and the hq_record_* / hq_peak_* / hq_spec_* / hq_cum_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
+ * The three tracker kinds keep state in place and share everything around it: hq_tracker (points, nsamples), hq_points_ok,
+ * hq_quantities_ok, hq_spare_check, hq_tracker_open / _added / _zero / _fetch / _load and hq_trackers_launch.  A new kind
+ * provides its kernel, its fold header (as hq_peak.h, hq_sdof.h, hq_cumul.h), its struct with reads_spare() and tables()
+ * (hq_state_table.h), its *_zero, and the check of its description in its *_add.
  */
 #ifndef HQ_OUTPUTS_H
 #define HQ_OUTPUTS_H
+
+#include "hq_state_table.h"
 
 /*
  * One sample of a recorder (hq_record_add): interpolate_station_displacements (psolve.c:6705-6787) / Old_planes_print
@@ -371,39 +377,62 @@ struct hq_ctx::hq_recorder : hq_ctx::hq_output {
     int32_t derivs = 0;
     hq_dbuf<double> d_ring;       /* [capacity][np][3 (1 + derivs)] */
 };
-/* peak-motion trackers (hq_peak_add): a running state per point updated in place by hq_k_peak -- no ring, no pending
- * samples, nothing for hq_run to count */
-struct hq_ctx::hq_peak_tracker : hq_ctx::hq_output {
+/* what the trackers share: a running state per point updated in place by the kind's kernel -- no ring, no pending samples,
+ * nothing for hq_run to count.  Each kind says what it is called, whether its launch reads d_u[spare] as u(t - 2 dt)
+ * (hq_outputs_enqueue) and which tables its state is, in the order they are reset in (hq_state_table.h) */
+struct hq_ctx::hq_tracker : hq_ctx::hq_output {
     hq_point_set pts;
-    int32_t quantities = 0, nq = 0;
     int64_t nsamples = 0;         /* due steps folded or enqueued so far: accounted here, from `step` alone */
-    hq_dbuf<double> d_pk;         /* [nq][5][np] */
-    hq_dbuf<int32_t> d_when;      /* [nq][2][np] */
+};
+template <typename T>
+static hq_state_table hq_table(const hq_dbuf<T>& b, const T* host, size_t rows, int reset, bool optional = false, size_t slots = 1)
+{
+    return { b.get(), const_cast<T*>(host), sizeof(T), rows, slots, b.bytes(), reset, optional };
+}
+/* peak-motion trackers (hq_peak_add), updated in place by hq_k_peak */
+struct hq_ctx::hq_peak_tracker : hq_ctx::hq_tracker {
+    static constexpr const char* kind = "peak";
+    int32_t quantities = 0, nq = 0;
+    hq_dbuf<double> d_pk;         /* [nq][5][np]; 0 before the first sample */
+    hq_dbuf<int32_t> d_when;      /* [nq][2][np]; -1 (every byte 0xff) */
+    bool reads_spare() const { return (quantities & HQ_PEAK_ACC) != 0; }
+    hq_state_tables tables(const double* peaks = nullptr, const int32_t* when = nullptr) const   /* (the caller's arrays, if any) */
+    { return { 2, { hq_table(d_pk, peaks, (size_t)nq * HQ_PEAK_NVAL, 0), hq_table(d_when, when, (size_t)nq * HQ_PEAK_NWHEN, 0xff), {} } }; }
 };
 /* response-spectrum trackers (hq_spec_add): per point the last sample and, per period, three oscillators and their maxima,
- * updated in place by hq_k_spec -- as a peak tracker, no ring, nothing pending, nothing for hq_run to count */
-struct hq_ctx::hq_spec_tracker : hq_ctx::hq_output {
-    hq_point_set pts;
+ * updated in place by hq_k_spec */
+struct hq_ctx::hq_spec_tracker : hq_ctx::hq_tracker {
+    static constexpr const char* kind = "spectrum";
     int32_t nper = 0;
-    int64_t nsamples = 0;         /* due steps folded or enqueued so far */
     std::vector<double> coef;     /* [nper][8], hq_sdof_coef at h = rate dt: what d_coef holds */
     hq_dbuf<double> d_coef;
-    hq_dbuf<double> d_aprev;      /* [3][np] */
+    hq_dbuf<double> d_aprev;      /* [3][np]; at rest before the first sample: all 0 */
     hq_dbuf<double> d_osc;        /* [nper][2][3][np] */
     hq_dbuf<double> d_sd;         /* [nper][4][np] */
+    bool reads_spare() const { return true; }   /* (tables(): the rows of a point counted across the periods) */
+    hq_state_tables tables(const double* sd = nullptr, const double* osc = nullptr, const double* aprev = nullptr) const
+    {
+        return { 3, { hq_table(d_aprev, aprev, 3, 0, true), hq_table(d_osc, osc, (size_t)nper * HQ_SPEC_NOSC, 0, true),
+                      hq_table(d_sd, sd, (size_t)nper * HQ_SPEC_NSD, 0) } };
+    }
 };
 /* cumulative-intensity trackers (hq_cum_add): running sums and threshold spans per point, updated in place by hq_k_cum, and
- * the Husid curve -- the sums of squares as they stood after every husid_every-th due sample, husid_slots of them.  As a peak
- * tracker, no ring, nothing pending, nothing for hq_run to count: which sample fills which slot follows from nsamples alone */
-struct hq_ctx::hq_cum_tracker : hq_ctx::hq_output {
-    hq_point_set pts;
+ * the Husid curve -- the sums of squares as they stood after every husid_every-th due sample, husid_slots of them: which
+ * sample fills which slot follows from nsamples alone */
+struct hq_ctx::hq_cum_tracker : hq_ctx::hq_tracker {
+    static constexpr const char* kind = "cumulative";
     int32_t quantities = 0, nq = 0, husid_every = 0, husid_slots = 0;
-    int64_t nsamples = 0;         /* due steps folded or enqueued so far */
     hq_cum_thr2 thr2 = { { 0.0, 0.0, 0.0 } };   /* by quantity bit */
     std::vector<int32_t> curve_steps;           /* [nfilled] the step of the sample each filled slot was stored behind */
-    hq_dbuf<double> d_sum;        /* [nq][6][np] */
-    hq_dbuf<int32_t> d_span;      /* [nq][3][np] */
-    hq_dbuf<double> d_curve;      /* [husid_slots][nq][3][np] */
+    hq_dbuf<double> d_sum;        /* [nq][6][np]; 0 before the first sample */
+    hq_dbuf<int32_t> d_span;      /* [nq][3][np]; -1, and the count row 0 (hq_cum_zero) */
+    hq_dbuf<double> d_curve;      /* [husid_slots][nq][3][np]; 0; `slots` of them travel (tables()): the filled ones */
+    bool reads_spare() const { return (quantities & HQ_PEAK_ACC) != 0; }
+    hq_state_tables tables(const double* sums = nullptr, const int32_t* span = nullptr, const double* curve = nullptr, size_t slots = 0) const
+    {
+        return { 3, { hq_table(d_sum, sums, (size_t)nq * HQ_CUM_NSUM, 0), hq_table(d_curve, curve, (size_t)nq * HQ_CUM_NCURVE, 0, true, slots),
+                      hq_table(d_span, span, (size_t)nq * HQ_CUM_NSPAN, 0xff) } };
+    }
 };
 /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
  * pinned host memory.  A slot holds the fields one behind the other,
@@ -485,12 +514,90 @@ static int hq_record_launch(hq_ctx* c, hq_ctx::hq_recorder& r)
     return HQ_OK;
 }
 
-/* the state of one tracker as it is before its first sample: peaks 0, `when` -1 (every byte 0xff) -- on the compute stream,
- * in place when this returns */
-static int hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
+/* ---- trackers: what is done with every table of every kind alike ---- */
+
+/* the state of one tracker as it is before its first sample: every table filled with its byte on the compute stream, in
+ * place when this returns */
+static int hq_tracker_zero(hq_ctx* c, hq_ctx::hq_tracker& t, const hq_state_tables& tl)
 {
-    HQ_TRY(t.d_pk.fill(0, c->stream));
-    return t.d_when.fill(0xff, c->stream);
+    for (int i = 0; i < tl.n; i++) {
+        HQ_HIP(hipMemsetAsync(tl.t[i].dev, tl.t[i].reset, tl.t[i].whole, c->stream));
+        HQ_HIP(hipStreamSynchronize(c->stream));
+    }
+    t.nsamples = 0;
+    return HQ_OK;
+}
+static int hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t) { return hq_tracker_zero(c, t, t.tables()); }
+static int hq_spec_zero(hq_ctx* c, hq_ctx::hq_spec_tracker& t) { return hq_tracker_zero(c, t, t.tables()); }
+
+/* the state crosses PCIe as the device keeps it, one copy per table, to or from the caller's array in the caller's layout
+ * (hq_state_table.h).  A table without bytes -- no points, no filled slot -- does not travel. */
+static int hq_tracker_copy(hq_ctx* c, const hq_ctx::hq_tracker& t, const hq_state_tables& tl, bool to_caller)
+{
+    const size_t np = (size_t)t.pts.np;
+    std::vector<unsigned char> stage[HQ_STATE_MAX_TABLES];
+    int64_t bytes = 0;
+    for (int i = 0; i < tl.n; i++) {
+        const hq_state_table& tb = tl.t[i];
+        if (!hq_state_table_bytes(tb, np) || (!tb.host && to_caller && tb.optional)) continue;
+        if (!tb.host) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+        stage[i].resize(hq_state_table_bytes(tb, np));
+        if (to_caller)
+            HQ_HIP(hipMemcpyAsync(stage[i].data(), tb.dev, stage[i].size(), hipMemcpyDeviceToHost, c->stream));
+        else {
+            hq_state_transpose(tb, np, false, tb.host, stage[i].data());
+            HQ_HIP(hipMemcpyAsync(tb.dev, stage[i].data(), stage[i].size(), hipMemcpyHostToDevice, c->stream));
+        }
+        bytes += (int64_t)stage[i].size();
+    }
+    if (!bytes) return HQ_OK;
+    HQ_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < tl.n && to_caller; i++)
+        if (!stage[i].empty()) hq_state_transpose(tl.t[i], np, true, stage[i].data(), tl.t[i].host);
+    (to_caller ? c->d2h_bytes : c->h2d_bytes) += bytes;
+    return HQ_OK;
+}
+
+static int hq_tracker_fetch(hq_ctx* c, const hq_ctx::hq_tracker& t, const hq_state_tables& tl, int64_t* nsamples)
+{
+    *nsamples = t.nsamples;
+    return hq_tracker_copy(c, t, tl, true);
+}
+static int hq_tracker_load(hq_ctx* c, hq_ctx::hq_tracker& t, const hq_state_tables& tl, int64_t nsamples)
+{
+    t.nsamples = nsamples;
+    return hq_tracker_copy(c, t, tl, false);
+}
+
+/* what hq_*_fetch, _load and _reset begin with: the arguments they cannot do without (`args`; `text` if one is missing) and
+ * the tracker of that handle (hq_tracker_find); then the device, and the steps enqueued so far behind them */
+template <typename T>
+static int hq_tracker_find(hq_ctx* c, bool args, const char* text, std::vector<T> hq_ctx::*outs, int32_t handle, T** t)
+{
+    if (!c || !args) return hq_fail(HQ_ERR_ARG, "%s", text);
+    *t = hq_output_find(c->*outs, handle);
+    return *t ? HQ_OK : hq_fail(HQ_ERR_ARG, "unknown %s tracker handle", T::kind);
+}
+template <typename T>
+static int hq_tracker_open(hq_ctx* c, bool args, const char* text, std::vector<T> hq_ctx::*outs, int32_t handle, T** t)
+{
+    HQ_TRY(hq_tracker_find(c, args, text, outs, handle, t));
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    return HQ_OK;
+}
+
+/* a description's points: a count, 1 or 8 nodes per point, and the arrays that go with them */
+static bool hq_points_ok(int32_t npoints, int32_t K, const int32_t* ids, const double* phi)
+{
+    return npoints >= 0 && (K == 1 || K == 8) && (npoints == 0 || (ids && (K == 1 || phi)));
+}
+/* a description's mask of HQ_PEAK_DISP | VEL | ACC: some quantity and no other bit */
+static bool hq_quantities_ok(int32_t q) { return q != 0 && (q & ~(HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC)) == 0; }
+/* an output that reads d_u[spare] as u(t - 2 dt) is refused where no kernel keeps it */
+static int hq_spare_check(const hq_ctx* c, bool reads_spare)
+{
+    return reads_spare && c->variant != HQ_VARIANT_PATCH ? hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "") : HQ_OK;
 }
 
 /* head of a step, where hq_record_launch sits and behind the same waits: one hq_k_peak launch per due tracker on the
@@ -509,14 +616,6 @@ static void hq_peak_launch(hq_ctx* c, hq_ctx::hq_peak_tracker& t)
                                                         c->dt, c->dt2, t.quantities, c->step, t.d_pk, t.d_when);
 }
 
-/* the state of one spectrum tracker as it is before its first sample: at rest, aprev 0, sd 0 -- as hq_peak_zero */
-static int hq_spec_zero(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
-{
-    HQ_TRY(t.d_aprev.fill(0, c->stream));
-    HQ_TRY(t.d_osc.fill(0, c->stream));
-    return t.d_sd.fill(0, c->stream);
-}
-
 /* head of a step, where hq_peak_launch sits and behind the same waits: one hq_k_spec launch per due tracker on the compute
  * stream.  It reads d_u[spare] as u(t - 2 dt), as an acceleration peak tracker does: the caller holds the streams back. */
 static void hq_spec_launch(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
@@ -528,19 +627,40 @@ static void hq_spec_launch(hq_ctx* c, hq_ctx::hq_spec_tracker& t)
                                                         c->d_u[c->spare], c->dt2, t.nper, t.d_coef, t.d_aprev, t.d_osc, t.d_sd);
 }
 
-/* the state of one cumulative tracker as it is before its first sample: sums 0, first / last step -1 (every byte 0xff), count
- * 0, no Husid slot filled -- as hq_peak_zero */
+/* a cumulative tracker's own: of the span, first / last step -1 and the count row 0; no Husid slot filled */
 static int hq_cum_zero(hq_ctx* c, hq_ctx::hq_cum_tracker& t)
 {
-    HQ_TRY(t.d_sum.fill(0, c->stream));
-    HQ_TRY(t.d_curve.fill(0, c->stream));
-    HQ_TRY(t.d_span.fill(0xff, c->stream));
+    HQ_TRY(hq_tracker_zero(c, t, t.tables()));
     const size_t np = (size_t)t.pts.np;
     for (int32_t q = 0; q < t.nq && np > 0; q++)
         HQ_HIP(hipMemsetAsync(t.d_span + ((size_t)q * HQ_CUM_NSPAN + 2) * np, 0, sizeof(int32_t) * np, c->stream));
     HQ_HIP(hipStreamSynchronize(c->stream));
     t.curve_steps.clear();
     return HQ_OK;
+}
+
+/* what hq_peak_add, hq_spec_add and hq_cum_add end with, the description checked and the tables allocated: the points, the
+ * state as it is before the first sample, the cadence and a handle */
+template <typename T, typename D>
+static int hq_tracker_added(hq_ctx* c, T& t, const D* d, int (*zero)(hq_ctx*, T&), std::vector<T> hq_ctx::*outs, int32_t hq_ctx::*next_id, int32_t* handle)
+{
+    HQ_TRY(hq_points_build(c, d->npoints, d->nodes_per_point, d->ids, d->phi, &t.pts));
+    HQ_TRY(zero(c, t));
+    c->h2d_bytes += t.pts.h2d();
+    t.due = { d->rate, d->first_step };
+    t.id = (c->*next_id)++;
+    *handle = t.id;
+    (c->*outs).push_back(std::move(t));
+    return HQ_OK;
+}
+
+/* hq_peak_reset, hq_spec_reset, hq_cum_reset */
+template <typename T>
+static int hq_tracker_reset(hq_ctx* c, std::vector<T> hq_ctx::*outs, int32_t handle, int (*zero)(hq_ctx*, T&))
+{
+    T* t;
+    HQ_TRY(hq_tracker_open(c, true, "null argument", outs, handle, &t));
+    return zero(c, *t);
 }
 
 /* head of a step, where hq_peak_launch sits and behind the same waits: one hq_k_cum launch per due tracker on the compute
@@ -598,6 +718,20 @@ static int hq_snapshot_launch(hq_ctx* c, hq_ctx::hq_snapshot& sn)
     return HQ_OK;
 }
 
+/* one launch per due tracker of one kind, of those that read d_u[spare] (`spare`) or of those that do not.  True if a launch
+ * was made that the step's other streams must stay behind */
+template <typename T>
+static bool hq_trackers_launch(hq_ctx* c, std::vector<T>& trackers, bool spare, void (*launch)(hq_ctx*, T&))
+{
+    bool held = false;
+    for (auto& t : trackers)
+        if (t.reads_spare() == spare && hq_cadence_due(t.due, c->step)) {
+            launch(c, t);
+            held |= spare && t.pts.np > 0;
+        }
+    return held;
+}
+
 /* The head of a step: every due output in solver_run's order (psolve.c:4277-4280: checkpoint / wavefield, then planes /
  * stations), then the trackers.  The launches that the step's other streams must stay behind (every snapshot, every recorder,
  * a peak or cumulative tracker of accelerations, a spectrum tracker: the comments above tell why) go first; ONE record of ev_output behind the last of them -- a
@@ -611,21 +745,18 @@ static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
         if (hq_cadence_due(sn.due, c->step)) { HQ_TRY(hq_snapshot_launch(c, sn)); hold = recorded = true; }
     for (auto& r : c->recs)
         if (hq_cadence_due(r.due, c->step)) { HQ_TRY(hq_record_launch(c, r)); if (r.pts.np > 0) { hold = true; recorded = false; } }
-    for (auto& t : c->peaks)                     /* the trackers that read u(t - 2 dt) */
-        if ((t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) { hq_peak_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
-    for (auto& t : c->specs)                     /* ... and the spectrum trackers, which all do */
-        if (hq_cadence_due(t.due, c->step)) { hq_spec_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
-    for (auto& t : c->cums)                      /* ... and the cumulative trackers of accelerations */
-        if ((t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) { hq_cum_launch(c, t); if (t.pts.np > 0) { hold = true; recorded = false; } }
+    /* the trackers that read u(t - 2 dt): a peak or cumulative tracker of accelerations, every spectrum tracker */
+    bool held = hq_trackers_launch(c, c->peaks, true, hq_peak_launch);
+    held |= hq_trackers_launch(c, c->specs, true, hq_spec_launch);
+    held |= hq_trackers_launch(c, c->cums, true, hq_cum_launch);
+    if (held) { hold = true; recorded = false; }
     if (hold && c->variant == HQ_VARIANT_PATCH && (hold_b || hold_c)) {
         if (!recorded) HQ_HIP(hipEventRecord(c->ev_output, c->stream));
         if (hold_b) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_output, 0));
         if (hold_c) HQ_HIP(hipStreamWaitEvent(c->cstream, c->ev_output, 0));
     }
-    for (auto& t : c->peaks)                     /* the other trackers: no stream waits for them */
-        if (!(t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) hq_peak_launch(c, t);
-    for (auto& t : c->cums)
-        if (!(t.quantities & HQ_PEAK_ACC) && hq_cadence_due(t.due, c->step)) hq_cum_launch(c, t);
+    hq_trackers_launch(c, c->peaks, false, hq_peak_launch);     /* the other trackers: no stream waits for them */
+    hq_trackers_launch(c, c->cums, false, hq_cum_launch);
     return HQ_OK;
 }
 
@@ -656,8 +787,7 @@ extern "C" int hq_record_add(hq_ctx* c, const hq_recorder_desc* d, int32_t* hand
     if (d->npoints < 0 || d->rate <= 0 || d->capacity <= 0 || d->derivs < 0 || d->derivs > 2 ||
         (d->npoints > 0 && (!d->ids || !d->phi)))
         return hq_fail(HQ_ERR_ARG, "bad recorder description%s", "");
-    if (d->derivs == 2 && c->variant != HQ_VARIANT_PATCH)
-        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_TRY(hq_spare_check(c, d->derivs == 2));
     HQ_HIP(hipSetDevice(c->device));
     hq_ctx::hq_recorder r;
     r.derivs = d->derivs;
@@ -713,91 +843,33 @@ extern "C" int hq_record_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::
 extern "C" int hq_peak_add(hq_ctx* c, const hq_peak_desc* d, int32_t* handle)
 {
     if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const int32_t all = HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC;
-    const int32_t K = d->nodes_per_point;
-    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->quantities == 0 || (d->quantities & ~all) != 0 ||
-        (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
+    if (!hq_points_ok(d->npoints, d->nodes_per_point, d->ids, d->phi) || d->rate < 1 || !hq_quantities_ok(d->quantities))
         return hq_fail(HQ_ERR_ARG, "bad peak tracker description%s", "");
-    if ((d->quantities & HQ_PEAK_ACC) && c->variant != HQ_VARIANT_PATCH)
-        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_TRY(hq_spare_check(c, (d->quantities & HQ_PEAK_ACC) != 0));
     HQ_HIP(hipSetDevice(c->device));
     hq_ctx::hq_peak_tracker t;
-    t.quantities = d->quantities; t.nq = hq_peak_nq(d->quantities); t.due = { d->rate, d->first_step };
+    t.quantities = d->quantities; t.nq = hq_peak_nq(d->quantities);
     const size_t n = (size_t)t.nq * (size_t)d->npoints;
-    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts));
     HQ_TRY(t.d_pk.alloc(&c->bytes, HQ_PEAK_NVAL * n));
     HQ_TRY(t.d_when.alloc(&c->bytes, HQ_PEAK_NWHEN * n));
-    HQ_TRY(hq_peak_zero(c, t));
-    c->h2d_bytes += t.pts.h2d();
-    t.id = c->peak_next_id++;
-    *handle = t.id;
-    c->peaks.push_back(std::move(t));
-    return HQ_OK;
+    return hq_tracker_added(c, t, d, hq_peak_zero, &hq_ctx::peaks, &hq_ctx::peak_next_id, handle);
 }
 
-/* the state between the device's tables ([nr][np], nr = nq x 5 or nq x 2 rows) and the caller's ([np][nr]), either way */
-template <typename T>
-static void hq_peak_transpose(size_t np, size_t nr, bool to_caller, const T* src, T* dst)
-{
-    for (size_t p = 0, ic = 0; p < np; p++)
-        for (size_t r = 0; r < nr; r++, ic++)
-            if (to_caller) dst[ic] = src[r * np + p]; else dst[r * np + p] = src[ic];
-}
-
-/* the state crosses PCIe as the device keeps it ([nq][5][np], [nq][2][np]); the caller's arrays are [np][nq][5], [np][nq][2] */
 extern "C" int hq_peak_fetch(hq_ctx* c, int32_t handle, double* peaks, int32_t* when, int64_t* nsamples)
 {
-    if (!c || !peaks || !when || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_peak_tracker* t = hq_output_find(c->peaks, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq;
-    *nsamples = t->nsamples;
-    if (n == 0) return HQ_OK;
-    std::vector<double> pk(HQ_PEAK_NVAL * n);
-    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
-    HQ_HIP(hipMemcpyAsync(pk.data(), t->d_pk, sizeof(double) * pk.size(), hipMemcpyDeviceToHost, c->stream));
-    HQ_HIP(hipMemcpyAsync(wh.data(), t->d_when, sizeof(int32_t) * wh.size(), hipMemcpyDeviceToHost, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    hq_peak_transpose(np, nq * HQ_PEAK_NVAL, true, pk.data(), peaks);
-    hq_peak_transpose(np, nq * HQ_PEAK_NWHEN, true, wh.data(), when);
-    c->d2h_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
-    return HQ_OK;
+    hq_ctx::hq_peak_tracker* t;
+    HQ_TRY(hq_tracker_open(c, peaks && when && nsamples, "null argument", &hq_ctx::peaks, handle, &t));
+    return hq_tracker_fetch(c, *t, t->tables(peaks, when), nsamples);
 }
 
 extern "C" int hq_peak_load(hq_ctx* c, int32_t handle, const double* peaks, const int32_t* when, int64_t nsamples)
 {
-    if (!c || !peaks || !when || nsamples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
-    hq_ctx::hq_peak_tracker* t = hq_output_find(c->peaks, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq;
-    t->nsamples = nsamples;
-    if (n == 0) return HQ_OK;
-    std::vector<double> pk(HQ_PEAK_NVAL * n);
-    std::vector<int32_t> wh(HQ_PEAK_NWHEN * n);
-    hq_peak_transpose(np, nq * HQ_PEAK_NVAL, false, peaks, pk.data());
-    hq_peak_transpose(np, nq * HQ_PEAK_NWHEN, false, when, wh.data());
-    HQ_HIP(hipMemcpyAsync(t->d_pk, pk.data(), sizeof(double) * pk.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipMemcpyAsync(t->d_when, wh.data(), sizeof(int32_t) * wh.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    c->h2d_bytes += (int64_t)(sizeof(double) * pk.size() + sizeof(int32_t) * wh.size());
-    return HQ_OK;
+    hq_ctx::hq_peak_tracker* t;
+    HQ_TRY(hq_tracker_open(c, peaks && when && nsamples >= 0, "bad argument", &hq_ctx::peaks, handle, &t));
+    return hq_tracker_load(c, *t, t->tables(peaks, when), nsamples);
 }
 
-extern "C" int hq_peak_reset(hq_ctx* c, int32_t handle)
-{
-    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_peak_tracker* t = hq_output_find(c->peaks, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown peak tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    HQ_TRY(hq_peak_zero(c, *t));
-    t->nsamples = 0;
-    return HQ_OK;
-}
+extern "C" int hq_peak_reset(hq_ctx* c, int32_t handle) { return hq_tracker_reset(c, &hq_ctx::peaks, handle, hq_peak_zero); }
 
 extern "C" int hq_peak_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::peaks); }
 
@@ -806,32 +878,26 @@ extern "C" int hq_peak_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::pe
 extern "C" int hq_spec_add(hq_ctx* c, const hq_spec_desc* d, int32_t* handle)
 {
     if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const int32_t K = d->nodes_per_point;
-    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->nperiods < 1 || d->nperiods > HQ_SPEC_MAX_PERIODS || !d->periods ||
-        !(d->damping >= 0.0 && d->damping < 1.0) || (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
+    if (!hq_points_ok(d->npoints, d->nodes_per_point, d->ids, d->phi) || d->rate < 1 || d->nperiods < 1 ||
+        d->nperiods > HQ_SPEC_MAX_PERIODS || !d->periods || !(d->damping >= 0.0 && d->damping < 1.0))
         return hq_fail(HQ_ERR_ARG, "bad spectrum tracker description%s", "");
     for (int32_t j = 0; j < d->nperiods; j++)                    /* finite and positive (x - x is NaN for an infinity) */
         if (!(d->periods[j] > 0.0) || d->periods[j] - d->periods[j] != 0.0)
             return hq_fail(HQ_ERR_ARG, "a period of a spectrum tracker is not finite and positive%s", "");
-    if (c->variant != HQ_VARIANT_PATCH)
-        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_TRY(hq_spare_check(c, true));
     HQ_HIP(hipSetDevice(c->device));
     hq_ctx::hq_spec_tracker t;
-    t.nper = d->nperiods; t.due = { d->rate, d->first_step };
+    t.nper = d->nperiods;
     t.coef.resize((size_t)HQ_SDOF_NCOEF * (size_t)t.nper);
     for (int32_t j = 0; j < t.nper; j++)
         hq_sdof_coef(d->periods[j], d->damping, (double)d->rate * c->dt, t.coef.data() + (size_t)HQ_SDOF_NCOEF * j);
     const size_t np = (size_t)d->npoints, n = np * (size_t)t.nper;
-    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts));
     HQ_TRY(t.d_coef.put(&c->bytes, t.coef, c->stream));
     HQ_TRY(t.d_aprev.alloc(&c->bytes, 3 * np));
     HQ_TRY(t.d_osc.alloc(&c->bytes, HQ_SPEC_NOSC * n));
     HQ_TRY(t.d_sd.alloc(&c->bytes, HQ_SPEC_NSD * n));
-    HQ_TRY(hq_spec_zero(c, t));
-    c->h2d_bytes += t.pts.h2d() + (int64_t)(sizeof(double) * t.coef.size());
-    t.id = c->spec_next_id++;
-    *handle = t.id;
-    c->specs.push_back(std::move(t));
+    HQ_TRY(hq_tracker_added(c, t, d, hq_spec_zero, &hq_ctx::specs, &hq_ctx::spec_next_id, handle));
+    c->h2d_bytes += (int64_t)(sizeof(double) * HQ_SDOF_NCOEF * (size_t)d->nperiods);   /* (the coefficients) */
     return HQ_OK;
 }
 
@@ -844,63 +910,21 @@ extern "C" int hq_spec_coefficients(hq_ctx* c, int32_t handle, double* coef)
     return HQ_OK;
 }
 
-/* the state crosses PCIe as the device keeps it ([nper][4][np], [nper][2][3][np], [3][np]); the caller's arrays are
- * [np][nper][4], [np][nper][2][3], [np][3] -- hq_peak_transpose with the rows of a point counted across the periods */
 extern "C" int hq_spec_fetch(hq_ctx* c, int32_t handle, double* sd, double* osc, double* aprev, int64_t* nsamples)
 {
-    if (!c || !sd || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_spec_tracker* t = hq_output_find(c->specs, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->pts.np, nper = (size_t)t->nper;
-    *nsamples = t->nsamples;
-    if (np == 0) return HQ_OK;
-    std::vector<double> s(HQ_SPEC_NSD * nper * np), o(osc ? HQ_SPEC_NOSC * nper * np : 0), a(aprev ? 3 * np : 0);
-    HQ_HIP(hipMemcpyAsync(s.data(), t->d_sd, sizeof(double) * s.size(), hipMemcpyDeviceToHost, c->stream));
-    if (osc) HQ_HIP(hipMemcpyAsync(o.data(), t->d_osc, sizeof(double) * o.size(), hipMemcpyDeviceToHost, c->stream));
-    if (aprev) HQ_HIP(hipMemcpyAsync(a.data(), t->d_aprev, sizeof(double) * a.size(), hipMemcpyDeviceToHost, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    hq_peak_transpose(np, nper * HQ_SPEC_NSD, true, s.data(), sd);
-    if (osc) hq_peak_transpose(np, nper * HQ_SPEC_NOSC, true, o.data(), osc);
-    if (aprev) hq_peak_transpose(np, (size_t)3, true, a.data(), aprev);
-    c->d2h_bytes += (int64_t)(sizeof(double) * (s.size() + o.size() + a.size()));
-    return HQ_OK;
+    hq_ctx::hq_spec_tracker* t;
+    HQ_TRY(hq_tracker_open(c, sd && nsamples, "null argument", &hq_ctx::specs, handle, &t));
+    return hq_tracker_fetch(c, *t, t->tables(sd, osc, aprev), nsamples);
 }
 
 extern "C" int hq_spec_load(hq_ctx* c, int32_t handle, const double* sd, const double* osc, const double* aprev, int64_t nsamples)
 {
-    if (!c || !sd || !osc || !aprev || nsamples < 0) return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
-    hq_ctx::hq_spec_tracker* t = hq_output_find(c->specs, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->pts.np, nper = (size_t)t->nper;
-    t->nsamples = nsamples;
-    if (np == 0) return HQ_OK;
-    std::vector<double> s(HQ_SPEC_NSD * nper * np), o(HQ_SPEC_NOSC * nper * np), a(3 * np);
-    hq_peak_transpose(np, nper * HQ_SPEC_NSD, false, sd, s.data());
-    hq_peak_transpose(np, nper * HQ_SPEC_NOSC, false, osc, o.data());
-    hq_peak_transpose(np, (size_t)3, false, aprev, a.data());
-    HQ_HIP(hipMemcpyAsync(t->d_sd, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipMemcpyAsync(t->d_osc, o.data(), sizeof(double) * o.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipMemcpyAsync(t->d_aprev, a.data(), sizeof(double) * a.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    c->h2d_bytes += (int64_t)(sizeof(double) * (s.size() + o.size() + a.size()));
-    return HQ_OK;
+    hq_ctx::hq_spec_tracker* t;
+    HQ_TRY(hq_tracker_open(c, sd && osc && aprev && nsamples >= 0, "bad argument", &hq_ctx::specs, handle, &t));
+    return hq_tracker_load(c, *t, t->tables(sd, osc, aprev), nsamples);
 }
 
-extern "C" int hq_spec_reset(hq_ctx* c, int32_t handle)
-{
-    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_spec_tracker* t = hq_output_find(c->specs, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown spectrum tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    HQ_TRY(hq_spec_zero(c, *t));
-    t->nsamples = 0;
-    return HQ_OK;
-}
+extern "C" int hq_spec_reset(hq_ctx* c, int32_t handle) { return hq_tracker_reset(c, &hq_ctx::specs, handle, hq_spec_zero); }
 
 extern "C" int hq_spec_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::specs); }
 
@@ -909,10 +933,7 @@ extern "C" int hq_spec_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::sp
 extern "C" int hq_cum_add(hq_ctx* c, const hq_cum_desc* d, int32_t* handle)
 {
     if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    const int32_t all = HQ_PEAK_DISP | HQ_PEAK_VEL | HQ_PEAK_ACC;
-    const int32_t K = d->nodes_per_point;
-    if (d->npoints < 0 || (K != 1 && K != 8) || d->rate < 1 || d->quantities == 0 || (d->quantities & ~all) != 0 ||
-        (d->npoints > 0 && (!d->ids || (K == 8 && !d->phi))))
+    if (!hq_points_ok(d->npoints, d->nodes_per_point, d->ids, d->phi) || d->rate < 1 || !hq_quantities_ok(d->quantities))
         return hq_fail(HQ_ERR_ARG, "bad cumulative tracker description%s", "");
     if (!((d->husid_every == 0 && d->husid_slots == 0) || (d->husid_every >= 1 && d->husid_slots >= 1)))
         return hq_fail(HQ_ERR_ARG, "husid_every and husid_slots are both 0 or both >= 1%s", "");
@@ -920,97 +941,47 @@ extern "C" int hq_cum_add(hq_ctx* c, const hq_cum_desc* d, int32_t* handle)
     for (int32_t q = 0; q < nq; q++)                             /* finite and >= 0 (x - x is NaN for an infinity) */
         if (!(d->threshold[q] >= 0.0) || d->threshold[q] - d->threshold[q] != 0.0)
             return hq_fail(HQ_ERR_ARG, "a threshold of a cumulative tracker is not finite and >= 0%s", "");
-    if ((d->quantities & HQ_PEAK_ACC) && c->variant != HQ_VARIANT_PATCH)
-        return hq_fail(HQ_ERR_STATE, "u(t - 2 dt) is kept by the patch variant only%s", "");
+    HQ_TRY(hq_spare_check(c, (d->quantities & HQ_PEAK_ACC) != 0));
     HQ_HIP(hipSetDevice(c->device));
     hq_ctx::hq_cum_tracker t;
-    t.quantities = d->quantities; t.nq = nq; t.due = { d->rate, d->first_step };
+    t.quantities = d->quantities; t.nq = nq;
     t.husid_every = d->husid_every; t.husid_slots = d->husid_slots;
     for (int32_t b = 0, q = 0; b < HQ_PEAK_NQ; b++)              /* mask order -> quantity bit; squared once, here */
         if (d->quantities & (1 << b)) { t.thr2.v[b] = d->threshold[q] * d->threshold[q]; q++; }
     const size_t n = (size_t)nq * (size_t)d->npoints;
-    HQ_TRY(hq_points_build(c, d->npoints, K, d->ids, d->phi, &t.pts));
     HQ_TRY(t.d_sum.alloc(&c->bytes, HQ_CUM_NSUM * n));
     HQ_TRY(t.d_span.alloc(&c->bytes, HQ_CUM_NSPAN * n));
     HQ_TRY(t.d_curve.alloc(&c->bytes, HQ_CUM_NCURVE * n * (size_t)d->husid_slots));
-    HQ_TRY(hq_cum_zero(c, t));
-    c->h2d_bytes += t.pts.h2d();
-    t.id = c->cum_next_id++;
-    *handle = t.id;
-    c->cums.push_back(std::move(t));
-    return HQ_OK;
+    return hq_tracker_added(c, t, d, hq_cum_zero, &hq_ctx::cums, &hq_ctx::cum_next_id, handle);
 }
 
-/* the state crosses PCIe as the device keeps it ([nq][6][np], [nq][3][np], per slot [nq][3][np]); the caller's arrays are
- * [np][nq][6], [np][nq][3], per slot [np][nq][3].  Only the filled slots of the curve travel. */
+/* only the filled slots of the curve travel */
 extern "C" int hq_cum_fetch(hq_ctx* c, int32_t handle, double* sums, int32_t* span, double* curve, int32_t* curve_steps,
                             int32_t* nfilled, int64_t* nsamples)
 {
-    if (!c || !sums || !span || !nfilled || !nsamples) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_cum_tracker* t = hq_output_find(c->cums, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown cumulative tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq, nf = t->curve_steps.size();
-    *nsamples = t->nsamples;
-    *nfilled = (int32_t)nf;
+    hq_ctx::hq_cum_tracker* t;
+    HQ_TRY(hq_tracker_open(c, sums && span && nfilled && nsamples, "null argument", &hq_ctx::cums, handle, &t));
+    *nfilled = (int32_t)t->curve_steps.size();
     if (curve_steps) std::copy(t->curve_steps.begin(), t->curve_steps.end(), curve_steps);
-    if (n == 0) return HQ_OK;
-    std::vector<double> sm(HQ_CUM_NSUM * n), cv(curve ? HQ_CUM_NCURVE * n * nf : 0);
-    std::vector<int32_t> sp(HQ_CUM_NSPAN * n);
-    HQ_HIP(hipMemcpyAsync(sm.data(), t->d_sum, sizeof(double) * sm.size(), hipMemcpyDeviceToHost, c->stream));
-    HQ_HIP(hipMemcpyAsync(sp.data(), t->d_span, sizeof(int32_t) * sp.size(), hipMemcpyDeviceToHost, c->stream));
-    if (!cv.empty()) HQ_HIP(hipMemcpyAsync(cv.data(), t->d_curve, sizeof(double) * cv.size(), hipMemcpyDeviceToHost, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    hq_peak_transpose(np, nq * HQ_CUM_NSUM, true, sm.data(), sums);
-    hq_peak_transpose(np, nq * HQ_CUM_NSPAN, true, sp.data(), span);
-    for (size_t k = 0; k < nf && curve; k++)
-        hq_peak_transpose(np, nq * HQ_CUM_NCURVE, true, cv.data() + k * HQ_CUM_NCURVE * n, curve + k * HQ_CUM_NCURVE * n);
-    c->d2h_bytes += (int64_t)(sizeof(double) * (sm.size() + cv.size()) + sizeof(int32_t) * sp.size());
-    return HQ_OK;
+    return hq_tracker_fetch(c, *t, t->tables(sums, span, curve, t->curve_steps.size()), nsamples);
 }
 
 extern "C" int hq_cum_load(hq_ctx* c, int32_t handle, const double* sums, const int32_t* span, const double* curve,
                            const int32_t* curve_steps, int32_t nfilled, int64_t nsamples)
 {
-    if (!c || !sums || !span || nsamples < 0 || nfilled < 0 || (nfilled > 0 && (!curve || !curve_steps)))
-        return hq_fail(HQ_ERR_ARG, "bad argument%s", "");
-    hq_ctx::hq_cum_tracker* t = hq_output_find(c->cums, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown cumulative tracker handle%s", "");
+    hq_ctx::hq_cum_tracker* t;
+    HQ_TRY(hq_tracker_find(c, sums && span && nsamples >= 0 && nfilled >= 0 && (nfilled == 0 || (curve && curve_steps)), "bad argument",
+                           &hq_ctx::cums, handle, &t));
     /* the slots that nsamples due samples fill: the accounting of hq_cum_launch goes on from nsamples alone */
     const int64_t filled = t->husid_every > 0 ? std::min<int64_t>(nsamples / t->husid_every, t->husid_slots) : 0;
     if (nfilled != filled) return hq_fail(HQ_ERR_ARG, "nfilled is not what nsamples due samples fill of this tracker's curve%s", "");
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
-    const size_t np = (size_t)t->pts.np, nq = (size_t)t->nq, n = np * nq, nf = (size_t)nfilled;
-    t->nsamples = nsamples;
-    t->curve_steps.assign(curve_steps, curve_steps + nf);
-    if (n == 0) return HQ_OK;
-    std::vector<double> sm(HQ_CUM_NSUM * n), cv(HQ_CUM_NCURVE * n * nf);
-    std::vector<int32_t> sp(HQ_CUM_NSPAN * n);
-    hq_peak_transpose(np, nq * HQ_CUM_NSUM, false, sums, sm.data());
-    hq_peak_transpose(np, nq * HQ_CUM_NSPAN, false, span, sp.data());
-    for (size_t k = 0; k < nf; k++)
-        hq_peak_transpose(np, nq * HQ_CUM_NCURVE, false, curve + k * HQ_CUM_NCURVE * n, cv.data() + k * HQ_CUM_NCURVE * n);
-    HQ_HIP(hipMemcpyAsync(t->d_sum, sm.data(), sizeof(double) * sm.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipMemcpyAsync(t->d_span, sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, c->stream));
-    if (!cv.empty()) HQ_HIP(hipMemcpyAsync(t->d_curve, cv.data(), sizeof(double) * cv.size(), hipMemcpyHostToDevice, c->stream));
-    HQ_HIP(hipStreamSynchronize(c->stream));
-    c->h2d_bytes += (int64_t)(sizeof(double) * (sm.size() + cv.size()) + sizeof(int32_t) * sp.size());
-    return HQ_OK;
+    t->curve_steps.assign(curve_steps, curve_steps + nfilled);
+    return hq_tracker_load(c, *t, t->tables(sums, span, curve, (size_t)nfilled), nsamples);
 }
 
-extern "C" int hq_cum_reset(hq_ctx* c, int32_t handle)
-{
-    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
-    hq_ctx::hq_cum_tracker* t = hq_output_find(c->cums, handle);
-    if (!t) return hq_fail(HQ_ERR_ARG, "unknown cumulative tracker handle%s", "");
-    HQ_HIP(hipSetDevice(c->device));
-    HQ_HIP(hq_quiesce(c));
-    HQ_TRY(hq_cum_zero(c, *t));
-    t->nsamples = 0;
-    return HQ_OK;
-}
+extern "C" int hq_cum_reset(hq_ctx* c, int32_t handle) { return hq_tracker_reset(c, &hq_ctx::cums, handle, hq_cum_zero); }
 
 extern "C" int hq_cum_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::cums); }
 

@@ -582,6 +582,7 @@ def _solver_from_desc(d, ntable, variant, device, tm1, tm2, options, precision):
     s._lib = capi.load_library(precision=precision)
     s.real = real
     s._h = ctypes.c_void_p()
+    s._trackers = capi._no_trackers()
     s.N, s.E = d.nharbored, d.lenum
     if isinstance(options, dict):
         options = capi.Options(**options)
