@@ -658,6 +658,12 @@ static void hq_patch_candidates(int64_t E, const int32_t* lnid, const hq_danglin
     for (auto& v : part) cand.insert(cand.end(), v.begin(), v.end());
 }
 
+/* LDS: the image (6 nlmax doubles) and the accumulators (3 (pmax + vmax)) of hq_k_patch_step must fit 160 KiB */
+static bool hq_patch_cfg_fits(const hq_patch_cfg& c)
+{
+    return (6 * (size_t)c.nlmax + 3 * (size_t)(c.pmax + c.vmax)) * 8 <= 160 * 1024;
+}
+
 /* the planner's configuration out of the options, as hq_create and the plan checks use it: `hanging` = the mesh has
  * hanging nodes the patches distribute themselves, `have_xyz` = the caller passed node coordinates.  *want_lattice: plan
  * with lattice patches (hq_patch_build asks in addition whether a persistent kernel can run them). */
@@ -682,9 +688,20 @@ static hq_patch_cfg hq_patch_cfg_of(const hq_options& o, bool hanging, bool have
     if (hanging && c.vmax == 0) c.vmax = 384;
     /* LDS: (6 nlmax + 3 (pmax + vmax)) doubles must fit 160 KiB (the hanging nodes' accumulators, where the mesh has
      * any, count against it too) */
-    while ((6 * (size_t)c.nlmax + 3 * (size_t)(c.pmax + c.vmax)) * 8 > 160 * 1024) c.nlmax -= 8;
+    while (!hq_patch_cfg_fits(c) && c.nlmax >= 16) c.nlmax -= 8;    /* (no image below 8 rows: hq_patch_cfg_refusal) */
     *want_lattice = !hq_set(o.patch_no_lattice) && have_xyz && c.pmax >= HQ_LAT_ACC;
     return c;
+}
+
+/* nullptr, or why no plan can be made with this configuration: the accumulators of patch_pmax owned nodes and patch_vmax
+ * hanging nodes leave no room for an image of even 8 rows.  hq_patch_build and the plan checks refuse it with this text. */
+static const char* hq_patch_cfg_refusal(const hq_patch_cfg& c)
+{
+    static thread_local char msg[200];
+    if (hq_patch_cfg_fits(c)) return nullptr;
+    snprintf(msg, sizeof msg, "patch_pmax = %d and patch_vmax = %d need %zu bytes of accumulators: with an image of %d rows that "
+             "exceeds the LDS budget of %d bytes", c.pmax, c.vmax, 3 * (size_t)(c.pmax + c.vmax) * 8, c.nlmax, 160 * 1024);
+    return msg;
 }
 
 static int hq_patch_plan_host(const hq_options& o, const hq_patch_cfg& cfg, int64_t E, int64_t N, const int32_t* lnid,
@@ -2179,6 +2196,7 @@ static int hq_patch_build(const hq_options& o, hq_patch_plan* P, int64_t E, int6
     P->n0 = n0;
     bool want_lattice = false;
     P->cfg = hq_patch_cfg_of(o, dn.n > 0, xyz != nullptr, &want_lattice);
+    if (const char* why = hq_patch_cfg_refusal(P->cfg)) return hq_fail(HQ_ERR_ARG, "patch plan: %s", why);
     /* 6 (default) = hq_k_patch_seed where the plan fits it (else hq_k_patch_pers, else hq_k_patch_step), 4 = hq_k_patch_pers
      * where it fits, 0 = hq_k_patch_step always */
     P->pipe = hq_value_or(o.patch_pipe, 6);

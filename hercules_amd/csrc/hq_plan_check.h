@@ -25,6 +25,7 @@ extern "C" int hq_plan_check(const hq_desc* d, int64_t report[8])
     const hq_dangling& dn = prep.dn;
     bool want_lattice = false;
     const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, d->node_xyz != nullptr, &want_lattice);
+    if (const char* why = hq_patch_cfg_refusal(cfg)) return hq_fail(HQ_ERR_ARG, "patch plan: %s", why);
     hq_patch_host H;
     if (hq_patch_plan_host(opts, cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
         return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
@@ -129,6 +130,7 @@ extern "C" int hq_stencil_plan_check(const hq_desc* d, int64_t report[6])
     const hq_dangling& dn = prep.dn;
     bool want_lattice = false;
     const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, true, &want_lattice);
+    if (const char* why = hq_patch_cfg_refusal(cfg)) return hq_fail(HQ_ERR_ARG, "patch plan: %s", why);
     hq_patch_host H;
     if (hq_patch_plan_host(opts, cfg, E, N, d->lnid, d->node_xyz, dn, want_lattice, &H) != 0)
         return hq_fail(HQ_ERR_ARG, "patch plan: %s", hq_patch_error());
@@ -417,6 +419,7 @@ static int hq_brick_plan_check_impl(const hq_desc* d, int64_t report[HQ_BRICK_RE
         const hq_dangling& dn = prep.dn;
         bool want_lattice = false;                   /* (not asked for: behind bricks the shell is planned without) */
         const hq_patch_cfg cfg = hq_patch_cfg_of(opts, dn.n > 0, true, &want_lattice);
+        if (const char* why = hq_patch_cfg_refusal(cfg)) return hq_fail(HQ_ERR_ARG, "patch plan: %s", why);
         hq_patch_host Ha, Hb;
         std::vector<int32_t> all((size_t)E);
         for (int64_t e = 0; e < E; e++) all[(size_t)e] = (int32_t)e;

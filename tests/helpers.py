@@ -328,7 +328,8 @@ def solver_desc(p, pack=False, precision="f64"):
         d.variant = capi.HQ_VARIANT_PATCH
         return d
     keep = [np.ascontiguousarray(p["lnid"], np.int32), np.ascontiguousarray(p["etable"], np.float64),
-            np.ascontiguousarray(p["ntable"], np.float64), np.ascontiguousarray(p["node_xyz"], np.int32)]
+            np.ascontiguousarray(p["ntable"], np.float64),
+            None if p["node_xyz"] is None else np.ascontiguousarray(p["node_xyz"], np.int32)]    # (None: hq_desc.node_xyz = NULL)
     d.lenum, d.nharbored = len(keep[0]), len(keep[2])
     d.lnid, d.eTable, d.nTable, d.node_xyz = [capi._ptr(a) for a in keep]
     if p["dangling"] is not None:

@@ -65,7 +65,13 @@ reference).  Worst |got - ref| / (2^-53 T) per kernel family (the bound is 64), 
     same nodes 2.07 (bricks) / 2.30 (patches only); window 1.87 / 2.81; duplicate 2.05 / 2.98 / 1.38 (scatter)
     float state, all 47 twins: mismatches 0; got != float32(ref) inside the band 0; undetermined 0 in 23 of them, 1 of 58 149
     (box70x20x12 and het70x20x12 under Rayleigh and mass damping) or 1 of 107 811 (box32) in the others -- the reference side's own
-    counts; 0.979 - 0.998 of the additive f32 bound."""
+    counts; 0.979 - 0.998 of the additive f32 bound.
+The geometry keys of tests/test_gpu_step_terms.py (patch plans off the default geometry, 58 with the float twins) ride in
+phase "all"; worst |got - ref| / (2^-53 T): hq_k_patch_stencil on box32 1.52 (psplit100 2.50); hq_k_patch_step big 1.50 / 1.55 /
+2.68 / 2.19 (box32 / two_level / c5_gradient_branch / het70x20x12), threads64 and threads192 1.55 / 2.56, pmax8-step 1.46 / 2.56;
+hq_k_patch_seed two_level 1.86 - 2.22, c5_gradient_branch 4.40, het70x20x12 4.32; float twins: mismatches 0, off float32(ref) 0,
+undetermined 0, or 1 of 107 811 (box32) and 1 of 58 149 (het70x20x12) as at the default geometry; 0.979 - 0.995 of the f32 bound.
+175 cases in 14.9 s with them (117 in 11.0 s before; the 58 alone 5.3 s, the slowest 1.1 s)."""
 import functools
 
 import numpy as np

@@ -83,7 +83,23 @@ undetermined 0 of 17 550 and 1 of 28 611 (the reference side's own count), 0.997
 routes between processes carry the same d_iforce records whatever filled them; the unloaded cases cover them.
 68 cases in 26 s on the device, the nine loaded ones 1.6 s of it (59 in 26 s before them; 50 in 25 s before the nine float twins, which take 0.1 - 0.7 s each); the slowest are the
 four between processes (2.6 - 3.9 s: five processes start), of the others the first of a problem (2.1 s with its
-reference), then 0.2 - 0.7 s each."""
+reference), then 0.2 - 0.7 s each.
+
+Patch plans off the default geometry (ST.GEOMETRY with no_bricks = 1, overlap 1).  At the defaults a rank of
+c5_gradient_branch on 8 has 2 - 3 patches and one of two_level on 5 has 1: the interface ordering d_order[nb | ne | nr | ns]
+and the persistent queue are stepped with almost nothing in them.  c5-8-pmax8 gives every rank 140 - 175 patches (two_level-5-
+pmax8: 41 - 57; the stencil box on 2 ranks: 1 296 and 1 352 subsets of 2 x 2 x 2 nodes), c5-8-pmax8-patch_step one workgroup of
+64 threads per patch, c5-8-pmax27-pmerge1 59 - 70 cubes that are never merged, c5-8-nlmax776 a smaller image, c5-8-big ONE patch
+per rank (interface and interior work in it, hq_k_patch_step), c5-8-vmax16 halving for the hanging-node accumulators; float
+twins f32-c5-8-pmax8 and f32-box-2-stencil-pmax8-ov0, and loaded-c5-8-pmax8.  check_route asserts for every case without
+bricks that each rank's npatches is hq_plan_check's on that rank's description (rank_plans; the plans and what they mean
+without a device: tests/test_patch_geometry_cpu.py).  Finding: none.  Measured on an MI355X (all | owned interface = non-owned |
+hanging, x 2^-53 T): c5-8-pmax8, -pmax27-pmerge1, -nlmax776, -vmax16 6.55 | 2.47 | 4.53 -- the default plan's figures to the
+digit; c5-8-pmax8-patch_step and c5-8-big 2.55 | 2.47 | 2.07; two_level-5-pmax8 1.62 | 1.27 | 1.23; box-2-stencil-pmax8-ov0
+1.73 | 1.14; loaded-c5-8-pmax8 5.09 | 1.94 | 4.19; the float twins 0 mismatches, 0 off float32(ref), undetermined 0 of 17 550 and
+1 of 55 539 (the reference side's own count), 0.992 and 0.997 of the f32 bound.
+79 cases in 33 s with them (68 in 26 s before; the 11 alone take 3.4 s, 0.1 - 0.3 s each -- the rest of the difference is the
+four cases between processes, 3.8 - 4.9 s each in that run)."""
 import numpy as np
 import pytest
 
@@ -177,6 +193,28 @@ CASES.update({
                                      route=NOBRICKS + (("kernel", "hq_k_patch_pers"),)),
 })
 
+
+def _geometry(g, **more):
+    """no_bricks = 1 and the fields of a geometry of tests/test_gpu_step_terms.py (ST.GEOMETRY)."""
+    return dict(ST.NB, **dict(ST.GEOMETRY[g], **more))
+
+
+STEP = (("kernel", "hq_k_patch_step"),)
+CASES.update({
+    # patch plans off the default geometry: 140 - 175 patches per rank instead of 2 - 3, one workgroup per patch, cubes that are
+    # never merged, a smaller image, ONE patch per rank (interface and interior work in it), halving for the hanging nodes
+    "c5-8-pmax8": _oct(C5, 8, 1, options=_geometry("pmax8"), route=NOBRICKS),
+    "c5-8-pmax8-patch_step": _oct(C5, 8, 1, options=_geometry("pmax8-step"), route=NOBRICKS + STEP),
+    "c5-8-pmax27-pmerge1": _oct(C5, 8, 1, options=_geometry("pmax27-pmerge1"), route=NOBRICKS),
+    "c5-8-nlmax776": _oct(C5, 8, 1, options=_geometry("nlmax776"), route=NOBRICKS),
+    "c5-8-big": _oct(C5, 8, 1, options=_geometry("big"), route=NOBRICKS + STEP),
+    "c5-8-vmax16": _oct(C5, 8, 1, options=_geometry("vmax16"), route=NOBRICKS),
+    "two_level-5-pmax8": _oct("two_level", 5, 1, options=_geometry("pmax8"), route=NOBRICKS),
+    "box-2-stencil-pmax8-ov0": _box(2, 0, _geometry("pmax8")),
+    "f32-c5-8-pmax8": _oct(C5, 8, 1, options=_geometry("pmax8"), precision="f32", route=NOBRICKS),
+    "f32-box-2-stencil-pmax8-ov0": _box(2, 0, _geometry("pmax8"), precision="f32"),
+})
+
 # ranks in processes of their own (tests/_hq_rank_worker.py, kind "step"): c5_gradient_branch on 5 ranks
 PROCESS_CASES = {
     "ipc-fused": dict(mesh=C5, nranks=5, transport="ipc", precision="f64", env={"HQ_OVERLAP": "1"}),
@@ -189,9 +227,25 @@ PROCESS_CASES = {
 # ---------------------------------------------------------------------------------------------
 # the route a case is about, from every rank's counters and resolved options
 # ---------------------------------------------------------------------------------------------
-def check_route(c, solvers, q):
+def rank_plans(c, q, boxes=()):
+    """hq_plan_check's report of every rank of a case whose contexts have no bricks, under the HQ_PATCH_* equivalents of the
+    case's options (ST.plan_environment): what hq_create plans there.  Boxes: their own plan_check()."""
+    from hercules_amd import capi
+    with pytest.MonkeyPatch.context() as mp:
+        ST.plan_environment(mp, c["options"])
+        if c["kind"] == "box":
+            return [b.plan_check() for b in boxes]
+        return [capi.plan_check(H.rank_desc(q, r)) for r in range(c["nranks"])]
+
+
+def check_route(c, solvers, q, boxes=()):
     """On the linked contexts, before the step."""
     infos = [s.info() for s in solvers]
+    if "no_bricks" in c["route"] or "box_stencil" in c["route"]:  # patches alone: the plan is the host-only check's
+        plans = rank_plans(c, q, boxes)
+        assert [p["faults"] for p in plans] == [0] * c["nranks"], plans
+        assert [i["npatches"] for i in infos] == [p["patches"] for p in plans], (infos, plans)
+        print("\n[partition-step] patches per rank %s" % [i["npatches"] for i in infos])
     for r, (s, info) in enumerate(zip(solvers, infos)):
         o, kernel = s.options(), s.dominant_kernel()
         assert info["transport"] == 4 and info["variant"] == c["variant"] and info["nranks"] == c["nranks"], (r, info)
@@ -326,7 +380,7 @@ def test_one_step_from_independent_fields_on_partitions(case):
     solvers, boxes = make_solvers(c, q)
     try:
         capi.group_link(solvers)
-        infos = check_route(c, solvers, q)
+        infos = check_route(c, solvers, q, boxes)
         family = (sorted({s.dominant_kernel() for s in solvers}),) + tuple(
             "%s=%d" % (k, sum(i[k] for i in infos)) for k in ("brick_units", "brick_units_het", "brick_units_packed", "npatches", "stencil_patches"))
         capi.group_run(solvers, 1)
@@ -351,6 +405,7 @@ LOADED_CASES = {
     "loaded-box-2-stencil": _box(2, 0, {"no_bricks": 1}),
     "loaded-f32-c5-8-patch": _oct(C5, 8, 1, precision="f32", route=NOBRICKS),
     "loaded-f32-box-2": _box(2, 1, precision="f32"),
+    "loaded-c5-8-pmax8": _oct(C5, 8, 1, options=_geometry("pmax8"), route=NOBRICKS),
 }
 LOADED_SEED = 31000                                              # rank r: H.rest_forces(..., LOADED_SEED + r), as tests/test_gpu_sources.py
 _LOADED = {}
@@ -410,7 +465,7 @@ def test_one_loaded_step_on_partitions(case):
         for r, s in enumerate(solvers):
             s.set_source(np.arange(len(q["gid"][r]), dtype=np.int32), L["Fr"][r][None])
         capi.group_link(solvers)
-        infos = check_route(c, solvers, q)
+        infos = check_route(c, solvers, q, boxes)
         family = (sorted({s.dominant_kernel() for s in solvers}),) + tuple(
             "%s=%d" % (k, sum(i[k] for i in infos)) for k in ("brick_units", "brick_units_het", "brick_units_packed", "npatches", "stencil_patches"))
         capi.group_run(solvers, 1)

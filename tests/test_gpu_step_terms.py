@@ -61,7 +61,33 @@ take 2.7 s, the slowest 1.1 s; 49 cases took 6.3 s before the f32 twins):
     hq_k_patch_step, hq_k_patch_pers (w form and patch_wform = 0): het70x20x12 2.7, two_level 1.2 - 1.4
     hq_k_patch_seed, patch_no_iso / _ntsame / _dedup / _lattice: het70x20x12 5.3 (mass 6.1, none 5.8), two_level 3.0
     scatter: het70x20x12 2.6 - 2.7, two_level 1.2
-    float state: 0.997 (brick) and 0.995 (unpacked het) of the f32 bound at plain nodes"""
+    float state: 0.997 (brick) and 0.995 (unpacked het) of the f32 bound at plain nodes
+
+Patch plans off the default geometry (GEOMETRY: hq_options.patch_threads / _pmax / _pmerge / _psplit / _nlmax / _vmax, each
+with no_bricks = 1; 29 f64 keys "<geometry>-<mesh>" and their f32 twins; the plans without a device:
+tests/test_patch_geometry_cpu.py).  Everything above runs the patch kernels at the planner's defaults (512 threads, pmax 768,
+pmerge 512, nlmax 1024, vmax 384); the geometry decides what they index by -- the strided loops of hq_k_patch_step against 64
+and 192 threads, the image size and o2off of the w form, hstride, the halving path, whether the persistent kernels take the
+plan (nlmax <= 1024), thousands of 8-node patches in the work queue or fewer than the 8 XCD slots, hq_k_patch_stencil's shape
+tables of 2 x 2 x 2 cubes, contexts without coordinates.  The criterion, reference, fields and bound are the ones above.  The
+"geometry" check asserts on the context that npatches and patch_pairs are hq_plan_check's under the HQ_PATCH_* equivalents,
+that the plan is not the default one, the kernel (hq_dominant_kernel names hq_k_patch_stencil where stencil patches are the
+majority, so the kernel of the element-form patches is seen only where they are) and stencil_patches against
+hq_stencil_plan_check's tables -- equal on box32 and two_level; 0 on het70x20x12 and c5_gradient_branch, where every element
+has its own material, no patch has uniform coefficients and `tables` counts shapes alone (2 726 of them under pmax8).
+Three settings the planner refuses (REFUSED) raise HqError at hq_create_opts, and a default context created next passes.
+Finding: none in the kernels; every device plan was the host-only check's.  hq_patch_cfg_of's loop had no lower end (a
+geometry whose accumulators alone exceed LDS was refused by accident, through an unsigned wrap-around): repaired, with a
+refusal of its own.  Measured on an MI355X, worst |got - ref| / (2^-53 T), unloaded (loaded: tests/test_gpu_loaded_step.py):
+    hq_k_patch_stencil on box32: pmax8, pmax27-pmerge1, pmax728, nlmax776 1.79; psplit100 (with element-form patches) 2.39
+    hq_k_patch_step: big 1.29 (box32) / 1.38 (two_level) / 2.55 (c5_gradient_branch) / 2.65 (het70x20x12); threads64 and
+      threads192 1.38 / 2.55; pmax8-step 1.56 (two_level) / 2.55
+    hq_k_patch_seed: two_level pmax8 and nlmax72 1.88 (beside the stencil majority), vmax8 2.28, noxyz-pmerge100 2.98;
+      c5_gradient_branch pmax8, pmax27-pmerge1, psplit100, pmax1016, vmax40, noxyz-pmerge37-pmax64 6.55;
+      het70x20x12 pmax8, nlmax72, nlmax776, noxyz-pmerge100 5.30
+    float twins, all 29: mismatches 0, undetermined 0, got != float32(ref) inside the band 0; 0.971 - 1.000 of the f32 bound
+154 cases in 11.8 s with the geometry keys and the three refusals (61 more than the 93 in 7.4 s; alone they take 4.6 s, the
+slowest pmax8-box32 1.4 s with its 4 880 patches planned twice, on the host and for the device, then pmax8-het70x20x12 0.6 s)."""
 import functools
 
 import numpy as np
@@ -149,14 +175,152 @@ def _chk_patches(kernel, **opts):
     return chk
 
 
-CHECKS = {"brick": lambda: S._chk_brick, "brick_cz": lambda: S._chk_brick_cz, "bycomp": lambda: S._chk_bycomp,
+# ---------------------------------------------------------------------------------------------
+# patch plans off the default geometry (the planner's defaults: 512 threads, pmax 768, pmerge 512, nlmax 1024, vmax 384)
+# ---------------------------------------------------------------------------------------------
+GEOMETRY = {
+    "threads64": dict(patch_pipe=0, patch_threads=64), "threads192": dict(patch_pipe=0, patch_threads=192),
+    "pmax8": dict(patch_pmax=8), "pmax8-step": dict(patch_pmax=8, patch_pipe=0, patch_threads=64),
+    "pmax27-pmerge1": dict(patch_pmax=27, patch_pmerge=1), "nlmax72": dict(patch_pmax=64, patch_nlmax=72),
+    "psplit100": dict(patch_pmax=343, patch_psplit=100), "pmax728": dict(patch_pmax=728), "nlmax776": dict(patch_nlmax=776),
+    "pmax1016": dict(patch_pmax=1016, patch_nlmax=1024), "big": dict(patch_pmax=1500, patch_nlmax=2400),
+    "vmax8": dict(patch_vmax=8), "vmax16": dict(patch_vmax=16), "vmax40": dict(patch_vmax=40),
+    "noxyz-pmerge100": dict(patch_pmerge=100), "noxyz-pmerge37-pmax64": dict(patch_pmerge=37, patch_pmax=64),
+}
+GEOMETRY_MESHES = {                                              # het70x20x12: Rayleigh only (the damping kinds are covered at the default geometry)
+    "box32": ("pmax8", "pmax27-pmerge1", "psplit100", "pmax728", "nlmax776", "big"),
+    "two_level": ("threads64", "threads192", "pmax8", "pmax8-step", "nlmax72", "big", "vmax8", "noxyz-pmerge100"),
+    "c5_gradient_branch": ("threads64", "threads192", "pmax8", "pmax8-step", "pmax27-pmerge1", "psplit100", "pmax1016", "big", "vmax40",
+                           "noxyz-pmerge37-pmax64"),
+    "het70x20x12": ("pmax8", "nlmax72", "nlmax776", "big", "noxyz-pmerge100"),
+}
+GEOMETRY_PAIRS = [(m, g) for m, gs in GEOMETRY_MESHES.items() for g in gs]
+# settings the planner refuses: one node's neighbours (the hanging-node accumulators among them) do not fit what is left
+REFUSED = [("two_level", dict(patch_vmax=1)), ("c5_gradient_branch", dict(patch_vmax=8)),
+           ("c5_gradient_branch", dict(patch_pmax=64, patch_nlmax=72))]
+REFUSAL = "a single node reaches more neighbours than LDS can stage"
+_GEOMETRY_FIELDS = ("patch_pipe", "patch_threads", "patch_pmax", "patch_pmerge", "patch_psplit", "patch_nlmax", "patch_vmax")
+HQ_PERS_THREADS, HQ_LAT_ACC, LDS_BUDGET = 1024, 729, 160 * 1024  # hq_patch.h
+
+
+def geometry_has_xyz(g):
+    return not g.startswith("noxyz")
+
+
+def patch_cfg(options, hanging):
+    """hq_patch_cfg_of restated: the geometry the planner works with, out of the options (-1 or absent = the default)."""
+    o = {k: v for k, v in (options or {}).items() if v != -1}
+    threads = (min(max(o.get("patch_threads", 512), 64), 1024)) & ~63
+    pmax = max(o.get("patch_pmax", 768), 8)
+    pmerge = max(min(o.get("patch_pmerge", 512), pmax), 1)
+    psplit = o.get("patch_psplit", 0)
+    psplit = pmax if psplit > pmax or psplit < 8 else psplit
+    nlmax = min(max(o.get("patch_nlmax", 1024), pmax + 8), 0x7fff)
+    vmax = o.get("patch_vmax", 0)
+    if hanging and vmax == 0:
+        vmax = 384
+    while (6 * nlmax + 3 * (pmax + vmax)) * 8 > LDS_BUDGET and nlmax >= 16:
+        nlmax -= 8
+    return dict(threads=threads, pmax=pmax, pmerge=pmerge, psplit=psplit, nlmax=nlmax, vmax=vmax, pipe=o.get("patch_pipe", 6))
+
+
+def steps_per_patch(options, hanging):
+    """hq_patch_uses_pers, as far as the options decide it: hq_k_patch_step runs the element-form patches where patch_pipe
+    is 0 or the image exceeds the persistent kernels' 1024 rows (a patch of more than 1024 elements or an LDS budget
+    exceeded would also send a plan there: the geometries here keep pmax + vmax far below the 2 718 at which 12 x 1024 rows
+    and the accumulators no longer fit)."""
+    cfg = patch_cfg(options, hanging)
+    assert cfg["nlmax"] > HQ_PERS_THREADS or (12 * max(cfg["nlmax"], 1000) + 3 * (cfg["pmax"] + cfg["vmax"]) + 36) * 8 <= LDS_BUDGET, cfg
+    return cfg["pipe"] not in (4, 6) or cfg["nlmax"] > HQ_PERS_THREADS
+
+
+def plan_environment(mp, options):
+    """The HQ_PATCH_* equivalents of a case's geometry on a pytest.MonkeyPatch: hq_plan_check and its kin take no options
+    and read the environment (HQ_ALLOW_ENV = 1, tests/conftest.py).  Every geometry variable the case does not name is unset."""
+    for k in _GEOMETRY_FIELDS:
+        mp.delenv("HQ_" + k.upper(), raising=False)
+    for k, v in (options or {}).items():
+        if k in _GEOMETRY_FIELDS:
+            mp.setenv("HQ_" + k.upper(), str(v))
+
+
+@functools.lru_cache(maxsize=None)
+def host_plans(mesh, damping, g):
+    """The host-only checks of a step_mesh under the geometry g (a GEOMETRY key, or None = the defaults) -> (hq_plan_check's
+    report, hq_stencil_plan_check's or None without coordinates).  They plan what hq_create plans under no_bricks = 1."""
+    from hercules_amd import capi
+    p = H.step_mesh(mesh, damping)
+    xyz = g is None or geometry_has_xyz(g)
+    with pytest.MonkeyPatch.context() as mp:
+        plan_environment(mp, GEOMETRY[g] if g else {})
+        d = H.solver_desc(p if xyz else dict(p, node_xyz=None))
+        return capi.plan_check(d), (capi.stencil_plan_check(d) if xyz else None)
+
+
+def single_element_nodes(p):
+    """The nodes of a mesh that lie in exactly one element (the corners of the domain, and hanging nodes on its edges)."""
+    return int((np.bincount(np.asarray(p["lnid"]).ravel(), minlength=p["N"]) == 1).sum())
+
+
+def _chk_geometry(g):
+    """The plan on the device is the one the host-only check reports, it is not the default plan, and the kernel and the
+    counter the geometry is about.  hq_dominant_kernel names hq_k_patch_stencil where more than half the patches are stencil
+    patches, else the kernel of the element-form ones: hq_k_patch_step where steps_per_patch() says so, else
+    hq_k_patch_seed.  A stencil patch needs a lattice-subset shape table AND one (c1, c2, beta) for all its elements:
+    hq_stencil_plan_check's `tables` counts the shapes whatever the coefficients, so stencil_patches == tables holds where a
+    level has one material (box32, two_level); with a material of its own in every element (branch_materials:
+    het70x20x12, c5_gradient_branch, no two eTable rows equal) only a patch of ONE element can be one, and the nodes of such
+    a patch lie in no other element."""
+    opts, xyz = GEOMETRY[g], geometry_has_xyz(g)
+
+    def chk(s, p, name):
+        info, o = s.info(), s.options()
+        assert info["brick_nodes"] == 0 and o["no_bricks"] == 1, info
+        for k, v in opts.items():
+            assert o[k] == v, (k, o[k], v)
+        plan, st = host_plans(name, p["damping"], g)
+        default = host_plans(name, p["damping"], None)[0]
+        assert plan["faults"] == 0 and (st is None or st["faults"] == 0), (plan, st)
+        print("\n[geometry] %-24s %-20s device: patches %d pairs %d lattice %d stencil %d ragged %d %s | host: patches %d pairs %d lattice %d tables %s | default %d"
+              % (g, name, info["npatches"], info["patch_pairs"], info["lattice_patches"], info["stencil_patches"], info["ragged_patches"],
+                 s.dominant_kernel(), plan["patches"], plan["pairs"], plan["lattice_patches"], st and st["tables"], default["patches"]))
+        assert (info["npatches"], info["patch_pairs"]) == (plan["patches"], plan["pairs"]), (info, plan)
+        if (name, g) == ("box32", "pmax728"):                     # one below HQ_LAT_ACC: no lattice rows, stencil tables still made
+            assert info["lattice_patches"] == 0 < info["stencil_patches"] and default["lattice_patches"] > 0, (info, default)
+        elif g == "pmax1016":                                    # the same cubes, merged otherwise: the pairs differ
+            assert info["patch_pairs"] != default["pairs"], (info, default)
+        elif g.startswith("threads"):                            # the workgroup changes (asserted above), the plan is the default one
+            assert (info["npatches"], info["patch_pairs"]) == (default["patches"], default["pairs"]), (info, default)
+        else:
+            assert info["npatches"] != default["patches"], (info, default)
+        element = "hq_k_patch_step" if steps_per_patch(opts, p["dangling"] is not None and len(p["dangling"][0]) > 0) else "hq_k_patch_seed"
+        kernel = "hq_k_patch_stencil" if 2 * info["stencil_patches"] > info["npatches"] else element
+        assert s.dominant_kernel() == kernel, (s.dominant_kernel(), kernel, info)
+        if (name, g) == ("box32", "big"):                        # an image over 1024 rows: no persistent kernel, no stencil patch
+            assert info["stencil_patches"] == st["tables"] == 0 and s.dominant_kernel() == "hq_k_patch_step", (info, st)
+        elif name == "box32" and g in ("pmax8", "pmax27-pmerge1", "pmax728", "nlmax776"):
+            assert info["stencil_patches"] == info["npatches"] == st["tables"] and s.dominant_kernel() == "hq_k_patch_stencil", (info, st)
+        elif not xyz:                                            # no coordinates: no lattice, no stencil
+            assert info["stencil_patches"] == info["lattice_patches"] == 0, info
+        elif "labels" in p:
+            assert len(np.unique(p["etable"][:, :3], axis=0)) == p["E"]
+            assert info["stencil_patches"] <= min(st["tables"], single_element_nodes(p)), (info, st)
+            assert info["npatches"] > info["stencil_patches"] and s.dominant_kernel() == element, info
+        else:                                                    # (hq_k_patch_stencil has launches of its own, whatever steps the others)
+            assert info["stencil_patches"] == st["tables"], (info, st)
+    return chk
+
+
+CHECKS = {"geometry": _chk_geometry,
+          "brick": lambda: S._chk_brick, "brick_cz": lambda: S._chk_brick_cz, "bycomp": lambda: S._chk_bycomp,
           "pernode": lambda: S._chk_pernode, "stencil_all": lambda: S._chk_stencil_all, "stencil_full": lambda: S._chk_stencil_full,
           "no_stencil": lambda: S._chk_no_stencil, "scatter": lambda: S._chk_scatter, "het": _chk_het, "gradient": _chk_gradient,
           "patches": lambda kernel, opts: _chk_patches(kernel, **opts)}
 
 
-def _case(mesh, check, damping="rayleigh", variant=PATCH, options=None, precision="f64", pack=False):
-    return dict(mesh=mesh, check=check, damping=damping, variant=variant, options=options, precision=precision, pack=pack)
+def _case(mesh, check, damping="rayleigh", variant=PATCH, options=None, precision="f64", pack=False, xyz=True):
+    """xyz = False: the context is created without node coordinates (hq_desc.node_xyz = NULL)."""
+    return dict(mesh=mesh, check=check, damping=damping, variant=variant, options=options, precision=precision, pack=pack, xyz=xyz)
 
 
 DAMPINGS = ("rayleigh", "mass", "none")
@@ -196,6 +360,8 @@ CASES.update({
     "f32-patch_seed-two_level": _case("two_level", ("patches", "hq_k_patch_seed", dict(patch_pipe=6)), options=dict(NB, patch_pipe=6),
                                       precision="f32"),
 })
+for _m, _g in GEOMETRY_PAIRS:                                    # "<geometry>-<mesh>": no_bricks = 1 on top of the geometry's fields
+    CASES["%s-%s" % (_g, _m)] = _case(_m, ("geometry", _g), options=dict(NB, **GEOMETRY[_g]), xyz=geometry_has_xyz(_g))
 
 
 def float_rows_pack(damping):
@@ -225,7 +391,7 @@ for _k in [k for k, c in CASES.items() if c["precision"] == "f64"]:
 
 def make(c, p, nt, u1, u2):
     kw = dict(edata=p["edata"], material=p["material"]) if c["pack"] else {}
-    return ha.Solver(p["lnid"], p["etable"], nt, p["dt"], tm1=u1, tm2=u2, dangling=p["dangling"], node_xyz=p["node_xyz"],
+    return ha.Solver(p["lnid"], p["etable"], nt, p["dt"], tm1=u1, tm2=u2, dangling=p["dangling"], node_xyz=p["node_xyz"] if c["xyz"] else None,
                      variant=c["variant"], options=c["options"], precision=c["precision"], **kw)
 
 
@@ -392,3 +558,26 @@ def test_one_step_from_independent_fields(case):
         print("[step-terms] %-48s float32(double step): mismatches %d, undetermined %d of %d, got != float32(ref) inside the band %d; %s"
               % (case, r["mismatches"], r["undetermined"], r["plain"], r["off_centre"], family[0]))
         assert_rounded_step(case, r, family, branch_of(p, r["first"][0]) if r["first"] else None)
+
+
+@pytest.mark.parametrize("mesh,options", REFUSED, ids=["%s-%s" % (m, "-".join("%s%d" % (k[6:], v) for k, v in o.items())) for m, o in REFUSED])
+def test_a_refused_geometry_leaves_the_next_context_whole(mesh, options):
+    """A geometry the planner cannot serve is refused at hq_create_opts with HQ_ERR_ARG and its message (never stepped
+    wrongly); a default-geometry context of the same mesh created next in the same process passes its per-node step."""
+    p = H.step_mesh(mesh)
+    nt, u1, u2, ref, T, _ = reference(mesh)
+    B = bound_factor(mesh, "rayleigh")
+    with pytest.raises(ha.HqError, match=r"hq error -1: .*" + REFUSAL):
+        make(_case(mesh, None, options=dict(NB, **options)), p, nt, u1, u2).close()
+    s = make(_case(mesh, None, options=dict(NB)), p, nt, u1, u2)
+    try:
+        info = s.info()
+        assert info["brick_nodes"] == 0 and info["npatches"] == host_plans(mesh, "rayleigh", None)[0]["patches"], info
+        s.run(1)
+        got, _ = s.download()
+        nonfinite = s.check_finite()
+    finally:
+        s.close()
+    w = worst(got, ref, T, B)
+    print("\n[step-terms] refused %s on %s, then the defaults: worst %.3f of the bound = %.2f x 2^-53 T" % (options, mesh, w[0], w[3]))
+    assert nonfinite == 0 and w[0] <= 1.0, w

@@ -220,7 +220,8 @@ def _plans(monkeypatch, c):
 
 
 # (the f32 cases with their n_t rows rounded to float, as the float library's planner gets them: NTSAME and packing read them)
-_PLANNED = [k for k, c in G.CASES.items() if c["variant"] == G.PATCH]
+# (the geometry cases' plans: tests/test_patch_geometry_cpu.py)
+_PLANNED = [k for k, c in G.CASES.items() if c["variant"] == G.PATCH and c["check"][0] != "geometry"]
 
 
 @pytest.mark.parametrize("case", _PLANNED, ids=_PLANNED)
