@@ -25,10 +25,13 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_snapshot_add", "hq_snapshot_pending", "hq_snapshot_fetch", "hq_snapshot_clear",
            "hq_peak_add", "hq_peak_fetch", "hq_peak_load", "hq_peak_reset", "hq_peak_clear",
            "hq_spec_add", "hq_spec_coefficients", "hq_spec_fetch", "hq_spec_load", "hq_spec_reset", "hq_spec_clear",
-           "hq_cum_add", "hq_cum_fetch", "hq_cum_load", "hq_cum_reset", "hq_cum_clear"]
+           "hq_cum_add", "hq_cum_fetch", "hq_cum_load", "hq_cum_reset", "hq_cum_clear",
+           "hq_deform_add", "hq_deform_fetch", "hq_deform_load", "hq_deform_reset", "hq_deform_clear"]
 HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
 HQ_PEAK_DISP, HQ_PEAK_VEL, HQ_PEAK_ACC = 1, 2, 4
 HQ_SPEC_MAX_PERIODS, HQ_SPEC_NVAL = 32, 4
+HQ_DEFORM_STRAIN, HQ_DEFORM_STRAIN_RATE, HQ_DEFORM_STRESS, HQ_DEFORM_ROTATION, HQ_DEFORM_ROTATION_RATE = 1, 2, 4, 8, 16
+HQ_DEFORM_ALL = 31
 
 
 class HqError(RuntimeError):
@@ -93,6 +96,12 @@ class _CumDesc(ctypes.Structure):
                 ("phi", ctypes.c_void_p), ("rate", ctypes.c_int32), ("first_step", ctypes.c_int32),
                 ("quantities", ctypes.c_int32), ("husid_every", ctypes.c_int32), ("husid_slots", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("threshold", ctypes.c_double * 3)]
+
+
+class _DeformDesc(ctypes.Structure):
+    _fields_ = [("npoints", ctypes.c_int32), ("ids", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("lame", ctypes.c_void_p),
+                ("rate", ctypes.c_int32), ("first_step", ctypes.c_int32), ("quantities", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class _Info(ctypes.Structure):
@@ -202,7 +211,7 @@ def _ptr_or_pad(a):
 
 
 # the trackers' kinds: the prefix of their entry points -> the word of their error texts
-_TRACKER_KINDS = {"peak": "peak", "spec": "spectrum", "cum": "cumulative"}
+_TRACKER_KINDS = {"peak": "peak", "spec": "spectrum", "cum": "cumulative", "deform": "deformation"}
 
 
 def _no_trackers():
@@ -656,6 +665,57 @@ class Solver:
     def cum_clear(self):
         """hq_cum_clear: drop every cumulative tracker of the context and its device memory."""
         self._tracker_clear("cum")
+
+    def deform_add(self, ids, grad, lame=None, rate=1, first_step=0, quantities=HQ_DEFORM_STRAIN):
+        """hq_deform_add: a deformation tracker.  ids [n,8] and grad [n,3,8] as Box.station_gradients returns them; lame
+        [n,2] = lambda, mu per point (Box.station_moduli), needed with HQ_DEFORM_STRESS only.  At the head of every step s >=
+        first_step with s % rate == 0 the displacement gradient at every point (and, with a rate bit, the velocity's) is
+        formed and the strain, strain rate, stress, rotation and rotation rate of the mask are folded into running peaks.
+        Returns its handle."""
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1, 8), np.int32)
+        grad = np.ascontiguousarray(np.asarray(grad, np.float64).reshape(-1, 3, 8))
+        if len(ids) != len(grad):
+            raise HqError("deform_add: %d rows of ids, %d of grad" % (len(ids), len(grad)))
+        if lame is not None:
+            lame = np.ascontiguousarray(np.asarray(lame, np.float64).reshape(-1, 2))
+            if len(lame) != len(ids):
+                raise HqError("deform_add: %d rows of ids, %d of lame" % (len(ids), len(lame)))
+        q = int(quantities)
+        d = _DeformDesc(len(ids), _ptr_or_pad(ids), _ptr_or_pad(grad), _ptr_or_pad(lame), int(rate), int(first_step), q, 0)
+        nt, nv = bin(q & 7).count("1"), bin(q & 24).count("1")
+        return self._tracker_add("deform", d, (len(ids), 10 * nt + 5 * nv, 2 * (nt + nv)))
+
+    def deform_fetch(self, handle):
+        """hq_deform_fetch: (vals [npoints, 10 nt + 5 nv] float64, when [npoints, 2 (nt + nv)] int32, nsamples) -- one block
+        per set bit of the mask, in the order of the bits.  A tensor's block (strain, strain rate, stress): max |xx|, |yy|,
+        |zz|, |xy|, |yz|, |xz|, max |xx + yy + zz|, max 6 J2, the horizontal engineering shear SQUARED, max |xx + yy|, and in
+        `when` the steps 6 J2 and the volumetric measure were last raised at (-1: never).  A vector's block (rotation,
+        rotation rate): peak_fetch's five values and two steps, the tilt in the horizontal slot.  Waits for the enqueued
+        steps; the state stays on the device."""
+        npoints, nvals, nwhen = self._tracker_shape("deform", handle)
+        vals = np.zeros((npoints, nvals))
+        when = np.full((npoints, nwhen), -1, np.int32)
+        n = ctypes.c_int64()
+        _check(self._lib.hq_deform_fetch(self._h, ctypes.c_int32(handle), _ptr_or_pad(vals), _ptr_or_pad(when), ctypes.byref(n)), self._lib)
+        return vals, when, int(n.value)
+
+    def deform_load(self, handle, vals, when, nsamples):
+        """hq_deform_load: put back what deform_fetch returned (a run that restarts from a checkpoint)."""
+        npoints, nvals, nwhen = self._tracker_shape("deform", handle)
+        vals = np.ascontiguousarray(vals, np.float64)
+        when = np.ascontiguousarray(when, np.int32)
+        if vals.shape != (npoints, nvals) or when.shape != (npoints, nwhen):
+            raise HqError("deform_load: the arrays are not those of deform_fetch")
+        _check(self._lib.hq_deform_load(self._h, ctypes.c_int32(handle), _ptr_or_pad(vals), _ptr_or_pad(when),
+                                        ctypes.c_int64(int(nsamples))), self._lib)
+
+    def deform_reset(self, handle):
+        """hq_deform_reset: values 0, when -1, nsamples 0."""
+        self._tracker_reset("deform", handle)
+
+    def deform_clear(self):
+        """hq_deform_clear: drop every deformation tracker of the context and its device memory."""
+        self._tracker_clear("deform")
 
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)

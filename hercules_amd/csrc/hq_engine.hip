@@ -45,6 +45,7 @@
 #include "hq_cadence.h"
 #include "hq_peak.h"
 #include "hq_cumul.h"
+#include "hq_deform.h"
 #include "hq_sdof.h"
 #define HQ_SAMPLE_REAL hq_real
 #include "hq_sample.h"
@@ -240,8 +241,8 @@ struct hq_ctx {
     double clk_us[5] = { 0, 0, 0, 0, 0 };   /* step, shell, interior, chain, chain behind the interior's end */
     int64_t clk_steps = 0;
     /* device outputs (recorders, trackers, snapshots).  hq_outputs.h, included ahead of hq_phase, DEFINES the structs: no code
-     * above that include may touch recs, peaks, specs, cums or snaps.  ev_output: recorded behind a due step's launches for the streams to wait on */
-    struct hq_output; struct hq_recorder; struct hq_tracker; struct hq_peak_tracker; struct hq_spec_tracker; struct hq_cum_tracker; struct hq_snapshot;
+     * above that include may touch recs, peaks, specs, cums, deforms or snaps.  ev_output: recorded behind a due step's launches for the streams to wait on */
+    struct hq_output; struct hq_recorder; struct hq_tracker; struct hq_peak_tracker; struct hq_spec_tracker; struct hq_cum_tracker; struct hq_deform_tracker; struct hq_snapshot;
     std::vector<hq_recorder> recs;
     int32_t rec_next_id = 0;
     std::vector<hq_peak_tracker> peaks;
@@ -250,6 +251,8 @@ struct hq_ctx {
     int32_t spec_next_id = 0;
     std::vector<hq_cum_tracker> cums;
     int32_t cum_next_id = 0;
+    std::vector<hq_deform_tracker> deforms;
+    int32_t deform_next_id = 0;
     std::vector<hq_snapshot> snaps;
     int32_t snap_next_id = 0;
     hipStream_t sstream = nullptr;              /* the snapshots' copy stream: from the first hq_snapshot_add on */

@@ -36,6 +36,7 @@
 #include "hq_cadence.h"
 #include "hq_peak.h"
 #include "hq_cumul.h"
+#include "hq_deform.h"
 #include "hq_sdof.h"
 #include "hq_sample.h"
 
@@ -61,6 +62,7 @@ struct hqh_box {
     int32_t ncls;                   /* lateral classes (1: the material depends on depth only) */
     float *k_vp, *k_vs, *k_rho;
     double *k_c1, *k_c2, *k_c3, *k_c4, *k_a, *k_M;
+    double *k_lam, *k_mu;           /* mu_and_lambda's own results (hqh_station_moduli) */
     /* schedule */
     int32_t nc, ns;
     hq_messenger *mc, *ms;
@@ -286,6 +288,7 @@ static int depth_constants(hqh_box* b)
         if (zeta > p->threshold_damping) zeta = p->threshold_damping;
         double a = zeta * aBase, bb = zeta * bBase;
         b->k_vp[m] = Vp; b->k_vs[m] = Vs; b->k_rho[m] = rho;
+        b->k_lam[m] = lambda; b->k_mu[m] = mu;
         b->k_c1[m] = dt2 * h * mu / 9;
         b->k_c2[m] = dt2 * h * lambda / 9;
         b->k_c3[m] = bb * dt * h * mu / 9;
@@ -788,6 +791,7 @@ void hqh_box_destroy(hqh_box* b)
     free(b->etable); free(b->ntable);
     free(b->k_vp); free(b->k_vs); free(b->k_rho);
     free(b->k_c1); free(b->k_c2); free(b->k_c3); free(b->k_c4); free(b->k_a); free(b->k_M);
+    free(b->k_lam); free(b->k_mu);
     free(b->mc); free(b->ms); free(b->cmap); free(b->smap);
     free(b->layer_store);
     free(b->zx); free(b->zy); free(b->zz);
@@ -846,7 +850,8 @@ int hqh_box_create(const hqh_box_params* p, hqh_box** out)
     b->k_rho = (float*)malloc(nz * sizeof(float));
     b->k_c1 = (double*)malloc(nz * 8); b->k_c2 = (double*)malloc(nz * 8); b->k_c3 = (double*)malloc(nz * 8);
     b->k_c4 = (double*)malloc(nz * 8); b->k_a = (double*)malloc(nz * 8); b->k_M = (double*)malloc(nz * 8);
-    if (!b->k_vp || !b->k_vs || !b->k_rho || !b->k_c1 || !b->k_c2 || !b->k_c3 || !b->k_c4 || !b->k_a || !b->k_M) {
+    b->k_lam = (double*)malloc(nz * 8); b->k_mu = (double*)malloc(nz * 8);
+    if (!b->k_vp || !b->k_vs || !b->k_rho || !b->k_c1 || !b->k_c2 || !b->k_c3 || !b->k_c4 || !b->k_a || !b->k_M || !b->k_lam || !b->k_mu) {
         hqh_box_destroy(b); return HQ_ERR_NOMEM;
     }
     if (depth_constants(b) != 0) { hqh_box_destroy(b); return HQ_ERR_ARG; }
@@ -1178,6 +1183,53 @@ int hqh_stations(const hqh_box* b, int32_t n, const double* xyz, int32_t* ids, d
     return HQ_OK;
 }
 
+/* d phi_c / d x_b of hqh_stations' phi: phi_c = prod_a (1 + s_a(c) lc[a]) / 8 with lc[a] = 2 off[a] / h.  The product of the
+ * two other axes is formed first and the sign put on last, so the two corners that differ in axis b alone hold the same
+ * magnitude bit for bit: a constant field has gradient 0 exactly, pair by pair. */
+int hqh_gradient_weights(double h, const double lc[3], double grad[3][8])
+{
+    if (!lc || !grad || !(h > 0.0) || h - h != 0.0) return HQ_ERR_ARG;
+    for (int a = 0; a < 3; a++)
+        if (lc[a] - lc[a] != 0.0) return HQ_ERR_ARG;
+    for (int b = 0; b < 3; b++) {
+        const int a1 = (b + 1) % 3, a2 = (b + 2) % 3;
+        for (int c = 0; c < 8; c++) {
+            const double f1 = 1 + ((c & (1 << a1)) ? 1 : -1) * lc[a1], f2 = 1 + ((c & (1 << a2)) ? 1 : -1) * lc[a2];
+            const double m = f1 * f2 / (4 * h);
+            grad[b][c] = (c & (1 << b)) ? m : -m;
+        }
+    }
+    return HQ_OK;
+}
+
+int hqh_station_gradients(const hqh_box* b, int32_t n, const double* xyz, int32_t* ids, double* grad, int32_t* mine)
+{
+    if (!b || n < 0 || (n && (!xyz || !ids || !grad || !mine))) return HQ_ERR_ARG;
+    for (int32_t s = 0; s < n; s++) {
+        int32_t e[3];
+        double off[3];
+        if (locate(b, xyz[3 * s], xyz[3 * s + 1], xyz[3 * s + 2], e, off) != 0) return HQ_ERR_ARG;
+        mine[s] = local_element(b, e, &ids[8 * s]);
+        double lc[3] = { 2 * off[0] / b->p.h, 2 * off[1] / b->p.h, 2 * off[2] / b->p.h };     /* (hqh_stations' lc) */
+        if (hqh_gradient_weights(b->p.h, lc, (double (*)[8])(grad + 24 * (size_t)s)) != HQ_OK) return HQ_ERR_ARG;
+    }
+    return HQ_OK;
+}
+
+int hqh_station_moduli(const hqh_box* b, int32_t n, const double* xyz, double* lame)
+{
+    if (!b || n < 0 || (n && (!xyz || !lame))) return HQ_ERR_ARG;
+    for (int32_t s = 0; s < n; s++) {
+        int32_t e[3];
+        double off[3];
+        if (locate(b, xyz[3 * s], xyz[3 * s + 1], xyz[3 * s + 2], e, off) != 0) return HQ_ERR_ARG;
+        const int64_t mi = mat_index(b, e[0], e[1], e[2]);
+        lame[2 * s] = b->k_lam[mi];
+        lame[2 * s + 1] = b->k_mu[mi];
+    }
+    return HQ_OK;
+}
+
 /* ------------------------------------------------------------------------ */
 /* solver_run                                                               */
 /* ------------------------------------------------------------------------ */
@@ -1469,6 +1521,29 @@ int hqh_cum_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const in
                 hq_cum_fold(v[3 * q], v[3 * q + 1], v[3 * q + 2], steps[k], thr2[m++], sm, 1, w, 1);
                 sm += HQ_CUM_NSUM; w += HQ_CUM_NSPAN;
             }
+        }
+    return HQ_OK;
+}
+
+int hqh_deform_fold(int32_t npoints, int32_t quantities, const double* lame, int32_t nsamples, const int32_t* steps,
+                    const double* gsamples, double* vals, int32_t* when)
+{
+    if (npoints < 0 || nsamples < 0 || quantities == 0 || (quantities & ~HQ_DEFORM_ALL) != 0) return HQ_ERR_ARG;
+    const int stress = (quantities & HQ_DEFORM_STRESS) != 0;
+    if (npoints == 0) return HQ_OK;
+    if (stress) {
+        if (!lame) return HQ_ERR_ARG;
+        for (int64_t i = 0; i < 2 * (int64_t)npoints; i++)      /* finite (x - x is NaN for an infinity), mu >= 0 */
+            if (lame[i] - lame[i] != 0.0 || ((i & 1) && !(lame[i] >= 0.0))) return HQ_ERR_ARG;
+    }
+    if (nsamples == 0) return HQ_OK;
+    if (!steps || !gsamples || !vals || !when) return HQ_ERR_ARG;
+    const int32_t nv = hq_deform_nvals(quantities), nw = hq_deform_nwhen(quantities);
+    for (int32_t k = 0; k < nsamples; k++)
+        for (int32_t p = 0; p < npoints; p++) {
+            const double* G = gsamples + ((int64_t)k * npoints + p) * 18;
+            hq_deform_point(quantities, G, G + 9, stress ? lame[2 * (int64_t)p] : 0.0, stress ? lame[2 * (int64_t)p + 1] : 0.0,
+                            steps[k], vals + (int64_t)p * nv, 1, when + (int64_t)p * nw, 1);
         }
     return HQ_OK;
 }

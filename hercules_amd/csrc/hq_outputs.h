@@ -1,10 +1,10 @@
 /*
- * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion, response-spectrum
- * and cumulative-intensity trackers, field snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at
- * the head of a step and the hq_record_* / hq_peak_* / hq_spec_* / hq_cum_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
- * The three tracker kinds keep state in place and share everything around it: hq_tracker (points, nsamples), hq_points_ok,
+ * hq_outputs.h -- the device-side outputs of a context (include/hq_solver.h): sample recorders, peak-motion, response-spectrum,
+ * cumulative-intensity and deformation trackers, field snapshots -- their kernels, their state (the structs hq_ctx declares), the launches at
+ * the head of a step and the hq_record_* / hq_peak_* / hq_spec_* / hq_cum_* / hq_deform_* / hq_snapshot_* entry points.  Included once by hq_engine.hip, behind hq_ctx and its helpers, ahead of hq_phase.
+ * The tracker kinds keep state in place and share everything around it: hq_tracker (points, nsamples), hq_points_ok,
  * hq_quantities_ok, hq_spare_check, hq_tracker_open / _added / _zero / _fetch / _load and hq_trackers_launch.  A new kind
- * provides its kernel, its fold header (as hq_peak.h, hq_sdof.h, hq_cumul.h), its struct with reads_spare() and tables()
+ * provides its kernel, its fold header (as hq_peak.h, hq_sdof.h, hq_cumul.h, hq_deform.h), its struct with reads_spare() and tables()
  * (hq_state_table.h), its *_zero, and the check of its description in its *_add.
  */
 #ifndef HQ_OUTPUTS_H
@@ -173,6 +173,70 @@ hq_k_cum(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__
         hq_sample_acc(K, w, row, u2, u3, d);
         fold(d[0] / dt2, d[1] / dt2, d[2] / dt2, thr2.v[2]);
     }
+}
+
+/*
+ * One due step of a deformation tracker (hq_deform_add): the displacement gradient G[b][a] = sum_c g[b][c] u_a[c] over the
+ * eight nodes of the point's element -- row b is hq_sample_disp with w = g[b], the sample hq_k_record takes with phi = g[b],
+ * every value widened to double first -- and, with a rate bit, the rate gradient: the same accumulators on through
+ * hq_sample_vel on u2, / dt, that recorder's velocity column.  Strain, stress and rotation of them are folded into the
+ * point's running state in place (hq_deform.h, the text hqh_deform_fold compiles).
+ * One lane per point, no atomics, no LDS: a point belongs to one lane, and the launches of one stream are ordered.
+ * ids [8][np], the weights [3][8][np], the moduli [2][np] (lambda, mu; read only with HQ_DEFORM_STRESS) and the state
+ * [rows][np] doubles / int32 (rows = hq_deform_nvals / _nwhen of the mask, the blocks in the order of its bits) are
+ * transposed: consecutive lanes on consecutive addresses, so a wave reads every row in whole lines.
+ * Each of the eight node rows is gathered ONCE per field into registers (`ub`, in hq_real, read by hq_sample.h through the
+ * constant offsets `at`: every index is a constant once the loops are unrolled) and feeds all three axis sums from there --
+ * 8 gathers of 24 (12) bytes per field, not 24.  u2 is gathered into the same registers behind u1's sums, and only if a
+ * rate bit is set.  The state is walked as hq_k_peak walks it: a lane reads the rows and writes only what it raised.
+ * Registers: 24 weights, 24 gathered values and up to 18 sums are live at once, of the 512 VGPRs a lane of a 256-thread
+ * workgroup may have; compiled for gfx950 (-O3, kernel-resource-usage) the kernel takes 130 VGPRs in the f64 library (3
+ * waves per SIMD) and 124 in the f32 library (4), no AGPRs, nothing spilled, 0 bytes of scratch.
+ * Bytes per point and due step, full mask, f64 (a model, not a measurement): 32 of ids + 192 of weights + 16 of moduli +
+ * 384 of gathers (u1, u2; 192 in the f32 library) + 320 of state read (`when` is only ever written) = 944, plus 8 or 12
+ * per value raised.  HQ_DEFORM_STRAIN alone: 32 + 192 + 192 + 80 = 496.
+ */
+__global__ void __launch_bounds__(256)
+hq_k_deform(int32_t np, const int32_t* __restrict__ ids, const double* __restrict__ grad, const double* __restrict__ lame,
+            const hq_real* __restrict__ u1, const hq_real* __restrict__ u2, double dt, int32_t quantities, int32_t step,
+            double* __restrict__ vals, int32_t* __restrict__ when)
+{
+#pragma clang fp contract(off)
+    const int32_t p = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+    if (p >= np) return;
+    const bool rate = (quantities & (HQ_DEFORM_STRAIN_RATE | HQ_DEFORM_ROTATION_RATE)) != 0;
+    const int64_t at[8] = { 0, 3, 6, 9, 12, 15, 18, 21 };        /* a point's nodes in `ub`, a contiguous [8][3] block */
+    int64_t row[8];
+    double g[3][8];
+#pragma unroll
+    for (int c = 0; c < 8; c++) row[c] = 3 * (int64_t)ids[(int64_t)c * np + p];
+#pragma unroll
+    for (int b = 0; b < 3; b++)
+#pragma unroll
+        for (int c = 0; c < 8; c++) g[b][c] = grad[(int64_t)(8 * b + c) * np + p];
+    hq_real ub[24];
+    auto gather = [&](const hq_real* __restrict__ u) {
+#pragma unroll
+        for (int c = 0; c < 8; c++)
+#pragma unroll
+            for (int a = 0; a < 3; a++) ub[3 * c + a] = u[row[c] + a];
+    };
+    double G[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, R[9];
+    gather(u1);
+#pragma unroll
+    for (int b = 0; b < 3; b++) hq_sample_disp(8, g[b], at, ub, G + 3 * b);
+    if (rate) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = G[i];
+        gather(u2);
+#pragma unroll
+        for (int b = 0; b < 3; b++) hq_sample_vel(8, g[b], at, ub, R + 3 * b);
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = R[i] / dt;
+    }
+    double lambda = 0.0, mu = 0.0;
+    if (quantities & HQ_DEFORM_STRESS) { lambda = lame[p]; mu = lame[(int64_t)np + p]; }
+    hq_deform_point(quantities, G, R, lambda, mu, step, vals + p, np, when + p, np);
 }
 
 /*
@@ -434,6 +498,23 @@ struct hq_ctx::hq_cum_tracker : hq_ctx::hq_tracker {
                       hq_table(d_span, span, (size_t)nq * HQ_CUM_NSPAN, 0xff) } };
     }
 };
+/* deformation trackers (hq_deform_add): the running peaks of strain, strain rate, stress, rotation and rotation rate per
+ * point, updated in place by hq_k_deform.  The points are elements with gradient weights in place of phi (pts.d_phi stays
+ * empty).  Only u1 and u2 are read: no stream is ever held back, and every variant has them */
+struct hq_ctx::hq_deform_tracker : hq_ctx::hq_tracker {
+    static constexpr const char* kind = "deformation";
+    int32_t quantities = 0;
+    hq_dbuf<double> d_grad;       /* [3][8][np] */
+    hq_dbuf<double> d_lame;       /* [2][np] lambda, mu; NULL without HQ_DEFORM_STRESS */
+    hq_dbuf<double> d_vals;       /* [10 nt + 5 nv][np]; 0 before the first sample */
+    hq_dbuf<int32_t> d_when;      /* [2 (nt + nv)][np]; -1 (every byte 0xff) */
+    bool reads_spare() const { return false; }
+    hq_state_tables tables(const double* vals = nullptr, const int32_t* when = nullptr) const
+    {
+        return { 2, { hq_table(d_vals, vals, (size_t)hq_deform_nvals(quantities), 0),
+                      hq_table(d_when, when, (size_t)hq_deform_nwhen(quantities), 0xff), {} } };
+    }
+};
 /* field snapshots (hq_snapshot_add): per snapshot a ring of `slots` staging slots in device memory and their mirrors in
  * pinned host memory.  A slot holds the fields one behind the other,
  * each at a 256-byte boundary (off[]; the same layout on both sides, so one copy carries a slot).  sstream, the copy
@@ -529,6 +610,7 @@ static int hq_tracker_zero(hq_ctx* c, hq_ctx::hq_tracker& t, const hq_state_tabl
 }
 static int hq_peak_zero(hq_ctx* c, hq_ctx::hq_peak_tracker& t) { return hq_tracker_zero(c, t, t.tables()); }
 static int hq_spec_zero(hq_ctx* c, hq_ctx::hq_spec_tracker& t) { return hq_tracker_zero(c, t, t.tables()); }
+static int hq_deform_zero(hq_ctx* c, hq_ctx::hq_deform_tracker& t) { return hq_tracker_zero(c, t, t.tables()); }
 
 /* the state crosses PCIe as the device keeps it, one copy per table, to or from the caller's array in the caller's layout
  * (hq_state_table.h).  A table without bytes -- no points, no filled slot -- does not travel. */
@@ -640,18 +722,24 @@ static int hq_cum_zero(hq_ctx* c, hq_ctx::hq_cum_tracker& t)
 }
 
 /* what hq_peak_add, hq_spec_add and hq_cum_add end with, the description checked and the tables allocated: the points, the
- * state as it is before the first sample, the cadence and a handle */
+ * state as it is before the first sample, the cadence and a handle.  hq_deform_add builds its own tables -- gradient weights
+ * in place of phi -- and ends with hq_tracker_enlist, `h2d` the bytes its uploads carried */
 template <typename T, typename D>
-static int hq_tracker_added(hq_ctx* c, T& t, const D* d, int (*zero)(hq_ctx*, T&), std::vector<T> hq_ctx::*outs, int32_t hq_ctx::*next_id, int32_t* handle)
+static int hq_tracker_enlist(hq_ctx* c, T& t, const D* d, int64_t h2d, int (*zero)(hq_ctx*, T&), std::vector<T> hq_ctx::*outs, int32_t hq_ctx::*next_id, int32_t* handle)
 {
-    HQ_TRY(hq_points_build(c, d->npoints, d->nodes_per_point, d->ids, d->phi, &t.pts));
     HQ_TRY(zero(c, t));
-    c->h2d_bytes += t.pts.h2d();
+    c->h2d_bytes += h2d;
     t.due = { d->rate, d->first_step };
     t.id = (c->*next_id)++;
     *handle = t.id;
     (c->*outs).push_back(std::move(t));
     return HQ_OK;
+}
+template <typename T, typename D>
+static int hq_tracker_added(hq_ctx* c, T& t, const D* d, int (*zero)(hq_ctx*, T&), std::vector<T> hq_ctx::*outs, int32_t hq_ctx::*next_id, int32_t* handle)
+{
+    HQ_TRY(hq_points_build(c, d->npoints, d->nodes_per_point, d->ids, d->phi, &t.pts));
+    return hq_tracker_enlist(c, t, d, t.pts.h2d(), zero, outs, next_id, handle);
 }
 
 /* hq_peak_reset, hq_spec_reset, hq_cum_reset */
@@ -683,6 +771,16 @@ static void hq_cum_launch(hq_ctx* c, hq_ctx::hq_cum_tracker& t)
     k<<<hq_blocks(t.pts.np, 256), 256, 0, c->stream>>>(t.pts.np, t.pts.d_ids, t.pts.d_phi, c->d_u[c->now], c->d_u[c->prev], u3,
                                                         c->dt, c->dt2, t.quantities, c->step, t.thr2, t.d_sum, t.d_span,
                                                         t.d_curve, slot);
+}
+
+/* head of a step, where hq_peak_launch sits and behind the same waits: one hq_k_deform launch per due tracker on the compute
+ * stream.  It reads d_u[now] and, with a rate bit, d_u[prev], which this step only reads: nothing is ever held back. */
+static void hq_deform_launch(hq_ctx* c, hq_ctx::hq_deform_tracker& t)
+{
+    t.nsamples++;
+    if (t.pts.np <= 0) return;
+    hq_k_deform<<<hq_blocks(t.pts.np, 256), 256, 0, c->stream>>>(t.pts.np, t.pts.d_ids, t.d_grad, t.d_lame, c->d_u[c->now], c->d_u[c->prev],
+                                                                  c->dt, t.quantities, c->step, t.d_vals, t.d_when);
 }
 
 /* what of a snapshot is not device memory: the pinned mirror and the slots' events */
@@ -757,6 +855,7 @@ static int hq_outputs_enqueue(hq_ctx* c, bool brick_stream)
     }
     hq_trackers_launch(c, c->peaks, false, hq_peak_launch);     /* the other trackers: no stream waits for them */
     hq_trackers_launch(c, c->cums, false, hq_cum_launch);
+    hq_trackers_launch(c, c->deforms, false, hq_deform_launch);
     return HQ_OK;
 }
 
@@ -984,6 +1083,63 @@ extern "C" int hq_cum_load(hq_ctx* c, int32_t handle, const double* sums, const 
 extern "C" int hq_cum_reset(hq_ctx* c, int32_t handle) { return hq_tracker_reset(c, &hq_ctx::cums, handle, hq_cum_zero); }
 
 extern "C" int hq_cum_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::cums); }
+
+/* ---- deformation trackers: entry points (include/hq_solver.h) ---- */
+
+extern "C" int hq_deform_add(hq_ctx* c, const hq_deform_desc* d, int32_t* handle)
+{
+    if (!c || !d || !handle) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    const bool stress = (d->quantities & HQ_DEFORM_STRESS) != 0;
+    if (d->npoints < 0 || d->rate < 1 || d->quantities == 0 || (d->quantities & ~HQ_DEFORM_ALL) != 0 ||
+        (d->npoints > 0 && (!d->ids || !d->grad || (stress && !d->lame))))
+        return hq_fail(HQ_ERR_ARG, "bad deformation tracker description%s", "");
+    const size_t np = (size_t)d->npoints;
+    for (size_t i = 0; i < 8 * np; i++)
+        if (d->ids[i] < 0 || d->ids[i] >= c->N) return hq_fail(HQ_ERR_ARG, "node id out of range%s", "");
+    for (size_t i = 0; stress && i < 2 * np; i++)                /* finite (x - x is NaN for an infinity), mu >= 0 */
+        if (d->lame[i] - d->lame[i] != 0.0 || ((i & 1) && !(d->lame[i] >= 0.0)))
+            return hq_fail(HQ_ERR_ARG, "a modulus of a deformation tracker is not finite, or mu < 0%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    hq_ctx::hq_deform_tracker t;
+    t.quantities = d->quantities;
+    /* device numbering; every table transposed so that consecutive lanes read consecutive addresses */
+    std::vector<int32_t> ids(8 * np);
+    std::vector<double> grad(24 * np), lame(stress ? 2 * np : 0);
+    for (size_t p = 0; p < np; p++) {
+        for (size_t k = 0; k < 8; k++) {
+            const int32_t id = d->ids[8 * p + k];
+            ids[k * np + p] = c->perm.empty() ? id : c->perm[(size_t)id];
+        }
+        for (size_t k = 0; k < 24; k++) grad[k * np + p] = d->grad[24 * p + k];
+        for (size_t k = 0; stress && k < 2; k++) lame[k * np + p] = d->lame[2 * p + k];
+    }
+    t.pts.np = d->npoints; t.pts.K = 8;
+    HQ_TRY(t.pts.d_ids.put(&c->bytes, ids, c->stream));
+    HQ_TRY(t.d_grad.put(&c->bytes, grad, c->stream));
+    if (stress) HQ_TRY(t.d_lame.put(&c->bytes, lame, c->stream));
+    HQ_TRY(t.d_vals.alloc(&c->bytes, (size_t)hq_deform_nvals(d->quantities) * np));
+    HQ_TRY(t.d_when.alloc(&c->bytes, (size_t)hq_deform_nwhen(d->quantities) * np));
+    const int64_t h2d = (int64_t)(sizeof(int32_t) * ids.size() + sizeof(double) * (grad.size() + lame.size()));
+    return hq_tracker_enlist(c, t, d, h2d, hq_deform_zero, &hq_ctx::deforms, &hq_ctx::deform_next_id, handle);
+}
+
+extern "C" int hq_deform_fetch(hq_ctx* c, int32_t handle, double* vals, int32_t* when, int64_t* nsamples)
+{
+    hq_ctx::hq_deform_tracker* t;
+    HQ_TRY(hq_tracker_open(c, vals && when && nsamples, "null argument", &hq_ctx::deforms, handle, &t));
+    return hq_tracker_fetch(c, *t, t->tables(vals, when), nsamples);
+}
+
+extern "C" int hq_deform_load(hq_ctx* c, int32_t handle, const double* vals, const int32_t* when, int64_t nsamples)
+{
+    hq_ctx::hq_deform_tracker* t;
+    HQ_TRY(hq_tracker_open(c, vals && when && nsamples >= 0, "bad argument", &hq_ctx::deforms, handle, &t));
+    return hq_tracker_load(c, *t, t->tables(vals, when), nsamples);
+}
+
+extern "C" int hq_deform_reset(hq_ctx* c, int32_t handle) { return hq_tracker_reset(c, &hq_ctx::deforms, handle, hq_deform_zero); }
+
+extern "C" int hq_deform_clear(hq_ctx* c) { return hq_outputs_clear(c, &hq_ctx::deforms); }
 
 /* ---- field snapshots: entry points (include/hq_solver.h) ---- */
 

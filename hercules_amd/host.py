@@ -18,6 +18,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_forcefile_info", "hqh_forcefile_read", "hqh_forcefile_write",
            "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
+           "hqh_gradient_weights", "hqh_station_gradients", "hqh_station_moduli", "hqh_deform_fold",
            "hqh_station_kinematics", "hqh_peak_fold", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
            "hqh_cvm_open", "hqh_cvm_close", "hqh_cvm_info", "hqh_cvm_query", "hqh_cvm_grid"]
@@ -324,6 +325,31 @@ class Box:
         if rc != 0:
             raise capi.HqError("hqh_stations failed: %d" % rc)
         return ids, phi, mine
+
+    def station_gradients(self, xyz):
+        """hqh_station_gradients: (ids [n,8], grad [n,3,8], mine [n]) -- the containing elements, as stations() finds them,
+        and the gradient weights grad[p][b][c] = d phi_c / d x_b at the points: what Solver.deform_add takes."""
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        n = len(xyz)
+        ids = np.zeros((n, 8), np.int32)
+        grad = np.zeros((n, 3, 8))
+        mine = np.zeros(n, np.int32)
+        rc = self._lib.hqh_station_gradients(self._h, ctypes.c_int32(n), xyz.ctypes.data_as(ctypes.c_void_p),
+                                             ids.ctypes.data_as(ctypes.c_void_p), grad.ctypes.data_as(ctypes.c_void_p),
+                                             mine.ctypes.data_as(ctypes.c_void_p))
+        if rc != 0:
+            raise capi.HqError("hqh_station_gradients failed: %d" % rc)
+        return ids, grad, mine
+
+    def station_moduli(self, xyz):
+        """hqh_station_moduli: lame [n,2] = (lambda, mu) of the elements that contain the points."""
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        lame = np.zeros((len(xyz), 2))
+        rc = self._lib.hqh_station_moduli(self._h, ctypes.c_int32(len(xyz)), xyz.ctypes.data_as(ctypes.c_void_p),
+                                          lame.ctypes.data_as(ctypes.c_void_p))
+        if rc != 0:
+            raise capi.HqError("hqh_station_moduli failed: %d" % rc)
+        return lame
 
     def run_params(self, *args, **kw):
         """See host.run_params."""
@@ -872,6 +898,47 @@ def cum_fold(steps, samples, quantities, threshold=0.0, sums=None, span=None):
                                             ctypes.c_void_p(thr.ctypes.data), ctypes.c_void_p(sums.ctypes.data),
                                             ctypes.c_void_p(span.ctypes.data)))
     return sums, span
+
+
+def gradient_weights(h, lc):
+    """hqh_gradient_weights: grad [3, 8], grad[b][c] = d phi_c / d x_b at the local coordinate lc (in [-1, 1]^3) of an
+    element of edge h."""
+    lc = np.ascontiguousarray(lc, np.float64).reshape(3)
+    grad = np.zeros((3, 8))
+    capi._check(load_library().hqh_gradient_weights(ctypes.c_double(h), ctypes.c_void_p(lc.ctypes.data),
+                                                    ctypes.c_void_p(grad.ctypes.data)))
+    return grad
+
+
+def deform_fold(steps, gsamples, quantities, lame=None, vals=None, when=None):
+    """hqh_deform_fold: gradient samples [k, npoints, 2, 3, 3] taken at `steps` [k] -- per sample and point G[b][a] =
+    d u_a / d x_b of the displacement, then of the velocity: gsamples[:, :, :, b, :] are columns 0..5 of a derivs = 1 recorder
+    whose phi is grad[:, b, :] -- folded into (vals [npoints, 10 nt + 5 nv], when [npoints, 2 (nt + nv)]), the state
+    Solver.deform_fetch returns.  lame [npoints, 2] = (lambda, mu) with HQ_DEFORM_STRESS.  vals / when None: a fresh state
+    (0 / -1); given, they are folded into in place (float64 / int32, C-contiguous) -- two calls in sequence equal one on the
+    concatenation.  Returns (vals, when)."""
+    quantities = int(quantities)
+    nt, nv = bin(quantities & 7).count("1"), bin(quantities & 24).count("1")
+    nvals, nwhen = 10 * nt + 5 * nv, 2 * (nt + nv)
+    steps = np.ascontiguousarray(steps, np.int32).reshape(-1)
+    gsamples = np.ascontiguousarray(gsamples, np.float64)
+    if gsamples.ndim != 5 or gsamples.shape[0] != len(steps) or gsamples.shape[2:] != (2, 3, 3):
+        raise capi.HqError("deform_fold: gsamples %r are not %d steps of [npoints, 2, 3, 3]" % (gsamples.shape, len(steps)))
+    npoints = gsamples.shape[1]
+    if lame is not None:
+        lame = np.ascontiguousarray(lame, np.float64)
+        if lame.shape != (npoints, 2):
+            raise capi.HqError("deform_fold: lame %r is not [%d, 2]" % (lame.shape, npoints))
+    if vals is None:
+        vals = np.zeros((npoints, nvals))
+        when = np.full((npoints, nwhen), -1, np.int32)
+    if (vals.dtype != np.float64 or when.dtype != np.int32 or vals.shape != (npoints, nvals) or when.shape != (npoints, nwhen)
+            or not vals.flags.c_contiguous or not when.flags.c_contiguous):
+        raise capi.HqError("deform_fold: vals / when are not a state of %d points and mask %d" % (npoints, quantities))
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data if a is not None and a.size else None)
+    capi._check(load_library().hqh_deform_fold(ctypes.c_int32(npoints), ctypes.c_int32(quantities), ptr(lame),
+                                               ctypes.c_int32(len(steps)), ptr(steps), ptr(gsamples), ptr(vals), ptr(when)))
+    return vals, when
 
 
 def husid_cross(curve_steps, curve, total, fracs, step0=0.0):

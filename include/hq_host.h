@@ -119,6 +119,20 @@ HQ_API int hqh_point_source(const hqh_box* box, double x, double y, double z, do
 HQ_API int hqh_stations(const hqh_box* box, int32_t n, const double* xyz, int32_t* ids, double* phi,
                         int32_t* mine);
 
+/* The gradient weights of a point in an element of edge h, what hq_deform_desc.grad holds (the shape-function derivatives
+ * point_strain sums, nonlinear.c:873-905): grad[b][c] = d phi_c / d x_b = s_b(c) prod_{a != b} (1 + s_a(c) lc[a]) / (4 h),
+ * sign s_a(c) = +1 if bit a of c is set else -1 and corner order as hqh_stations'; lc is the local coordinate in [-1, 1]
+ * (0: the element's centre).  The two corners that differ in axis b alone get the same magnitude bit for bit.
+ * HQ_ERR_ARG for null pointers, an h that is not finite and positive, an lc that is not finite. */
+HQ_API int hqh_gradient_weights(double h, const double lc[3], double grad[3][8]);
+/* hqh_stations for deformation trackers: the containing element -- the same location step -- and the gradient weights at
+ * the point.  ids [n][8], grad [n][3][8], mine[s] = 1 if the element is local.  Element centres give a strain map. */
+HQ_API int hqh_station_gradients(const hqh_box* box, int32_t n, const double* xyz, int32_t* ids, double* grad,
+                                 int32_t* mine);
+/* The moduli of the containing elements, lame [n][2] = lambda, mu as this library's restatement of mu_and_lambda
+ * (psolve.c:3236-3272) computes them for the element tables: what hq_deform_desc.lame holds. */
+HQ_API int hqh_station_moduli(const hqh_box* box, int32_t n, const double* xyz, double* lame);
+
 /* Called at every station print step with the interpolated displacements [n][3] -- or, with
  * station_derivs = 1 | 2, [n][6] | [n][9]: displacement, velocity (u1 - u2) / dt and acceleration
  * (u1 - 2 u2 + u3) / dt^2 as print_station_velocities / print_station_accelerations add them
@@ -310,6 +324,17 @@ HQ_API int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, 
  * counts, quantities 0 or with unknown bits, a threshold that is negative or not finite. */
 HQ_API int hqh_cum_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps,
                         const double* samples, const double* threshold, double* sums, int32_t* span);
+/* The deformation fold on the host (csrc/hq_deform.h, the text hq_k_deform compiles): gradient samples folded into the state
+ * hq_deform_fetch delivers -- the route of a caller without device trackers.  gsamples [nsamples][npoints][2][3][3]: per
+ * sample and point G[b][a] = d u_a / d x_b of the displacement, then of the velocity -- what three recorders with phi =
+ * grad[:, b, :] and derivs = 1 deliver, recorder b's columns 0..2 and 3..5 being rows b of the two gradients; steps[k] is
+ * the step of sample k.  `quantities` is a mask of HQ_DEFORM_*; lame [npoints][2] = lambda, mu is read only with
+ * HQ_DEFORM_STRESS.  vals [npoints][10 nt + 5 nv] and when [npoints][2 (nt + nv)] are folded INTO: the caller starts them at
+ * 0 and -1, and two calls in sequence equal one call on the concatenation.  HQ_ERR_ARG for null pointers (where there is
+ * something to read), negative counts, quantities 0 or with unknown bits, HQ_DEFORM_STRESS without lame or with a modulus
+ * that is not finite or a mu < 0. */
+HQ_API int hqh_deform_fold(int32_t npoints, int32_t quantities, const double* lame, int32_t nsamples, const int32_t* steps,
+                           const double* gsamples, double* vals, int32_t* when);
 /* Where Husid curves cross fractions of their totals (significant durations: D5-95 is the difference of the crossings of
  * 0.05 and 0.95, times dt).  curve [nslots][nseries] holds the running sum of every series as it stood at curve_steps[k]
  * (increasing) -- hq_cum_fetch's curve seen as [nfilled][np nq 3] -- and total [nseries] the final sums; (step0, 0) stands

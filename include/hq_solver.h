@@ -686,6 +686,80 @@ HQ_API int hq_cum_reset(hq_ctx* ctx, int32_t handle);
 HQ_API int hq_cum_clear(hq_ctx* ctx);
 
 /*
+ * Deformation trackers (additive under ABI 6): the running peaks of the ground's DEFORMATION -- peak ground strain for
+ * pipelines and tunnels, peak dynamic stress (von Mises, volumetric) for triggering studies, tilt and torsion for rotational
+ * seismology -- kept ON THE DEVICE.  A peak of strain is a reduction over time in the sense a peak of motion is: a state of
+ * fixed size per point folded in place, no ring, no batch cut, nothing over PCIe until it is fetched.  The other route is
+ * three recorders at rate 1 whose phi tables are the gradient weights, nine columns per point and step over PCIe, and a
+ * fold on the host (hqh_deform_fold, hq_host.h).
+ * A point lies in an element: ids are its eight nodes and grad[b][c] = d phi_c / d x_b the derivatives of their trilinear
+ * shape functions at the point (hqh_gradient_weights, hqh_station_gradients; point_strain, nonlinear.c:873-905, evaluates
+ * the same sums).  At the head of every step s >= first_step with s % rate == 0 -- where hq_k_record sits, before any of that
+ * step's kernels, on exactly the state hq_gather documents -- one launch of hq_k_deform forms the displacement gradient
+ * G[b][a] = d u_a / d x_b = sum_c grad[b][c] u_a[c]: row b is the sample hq_k_record would take with phi = grad[b] (every
+ * value widened to double first, csrc/hq_sample.h's order of operations, no contraction), bit for bit, and the rate
+ * gradient is that recorder's velocity column, (sum_c grad[b][c] u1 - grad[b][c] u2) / dt.  From them (csrc/hq_deform.h):
+ *   strain    (xx, yy, zz, xy, yz, xz), the reference's tensor order: xx = G[0][0], yy = G[1][1], zz = G[2][2],
+ *             xy = 0.5 (G[1][0] + G[0][1]), yz = 0.5 (G[2][1] + G[1][2]), xz = 0.5 (G[2][0] + G[0][2]) -- tensor shear, half
+ *             the engineering shear
+ *   rotation  half the curl: wx = 0.5 (G[1][2] - G[2][1]), wy = 0.5 (G[2][0] - G[0][2]), wz = 0.5 (G[0][1] - G[1][0])
+ *   stress    of the displacement's strain and the point's moduli, point_stress's order of operations (nonlinear.c:
+ *             907-924): mu2 = 2 mu, lkk = lambda ((xx + yy) + zz), s_aa = mu2 e_aa + lkk, s_ab = mu2 e_ab, products
+ *             rounded first
+ * The state of a point is one block per set bit of `quantities`, in the order of the bits: ten doubles and two int32 per
+ * tensor (HQ_DEFORM_STRAIN, _STRAIN_RATE, _STRESS), then five doubles and two int32 per vector (HQ_DEFORM_ROTATION,
+ * _ROTATION_RATE) -- vals [np][10 nt + 5 nv], when [np][2 (nt + nv)], nt and nv the set bits among the first three and the
+ * last two.  A tensor's block:
+ *   vals[0..5] = max |xx|, |yy|, |zz|, |xy|, |yz|, |xz|
+ *   vals[6]    = max |(xx + yy) + zz|     the volumetric measure (3 x the mean stress, for a stress)
+ *   vals[7]    = max 6 J2 = ((dxy dxy + dyz dyz) + dzx dzx) + 6.0 ((xy xy + yz yz) + xz xz) with dxy = xx - yy, dyz = yy - zz,
+ *                dzx = zz - xx, summed in this order: the caller divides by 6, or takes sqrt(vals[7] / 2) of a stress
+ *                block for the peak von Mises stress
+ *   vals[8]    = max hd hd + 4.0 (xy xy), hd = xx - yy: the largest engineering shear in the horizontal plane, SQUARED
+ *   vals[9]    = max |xx + yy|            the areal strain
+ *   when[0]    = the step at which vals[7] was last raised, when[1] the same for vals[6]; -1 = never
+ * A vector's block is a peak tracker's (csrc/hq_peak.h): max |wx|, |wy|, |wz|, max (wx wx + wy wy) -- the tilt, SQUARED --
+ * max (wx wx + wy wy) + wz wz, and the steps the last two were last raised at; the torsion is the z slot.
+ * Always double, in both libraries.  A value enters only if it is strictly greater: the first occurrence of a maximum is
+ * kept, a sample of exactly 0 leaves `when` at -1, a NaN never enters.  The device takes no root, so the state equals
+ * hqh_deform_fold of three recorders' samples of the same run bit for bit.  Step 0 samples the initial state; as with
+ * recorders, the state after the last step is not sampled until a further step begins.
+ * hq_deform_fetch waits for the enqueued work (as hq_peak_fetch does), copies the state out and leaves it in place;
+ * *nsamples counts the due steps folded so far, accounted on the host from the step counter.  It adds exactly the fetched
+ * bytes, np (88 nt + 48 nv), to hq_info.pcie_d2h_bytes; between fetches a tracker moves nothing.  hq_deform_load puts
+ * fetched values back (a run that restarts from a checkpoint); hq_deform_reset zeroes the state, sets `when` to -1 and
+ * nsamples to 0.  hq_upload keeps trackers and their state; the due steps follow the new step number.  hq_deform_clear drops
+ * every deformation tracker of the context and its memory (hq_destroy does, too); handles are not reused.  hq_record_clear,
+ * hq_snapshot_clear, hq_peak_clear, hq_spec_clear, hq_cum_clear and the hqh_solver_run* runners leave them alone, and no
+ * run call has anything to count for them.  The device memory -- np (32 of ids + 192 of weights [+ 16 of moduli]) of
+ * tables and np (88 nt + 48 nv) of state -- counts in hq_info.device_bytes.
+ * The launch reads u(t) and u(t - dt) only (the latter only with a rate bit), which the step's own kernels only read: it
+ * holds no stream back, and every variant has it, the scatter variant included.
+ * Errors: HQ_ERR_ARG for null pointers, npoints < 0, rate < 1, quantities 0 or with unknown bits, HQ_DEFORM_STRESS without
+ * lame, a modulus that is NaN or infinite or mu < 0, an id outside [0, nharbored), an unknown handle; HQ_ERR_NOMEM if the
+ * device memory cannot be allocated -- nothing is kept then.  npoints == 0 is valid.
+ * A context without deformation trackers enqueues exactly what it did before they existed.
+ */
+#ifndef HQ_DEFORM_QUANTITIES
+#define HQ_DEFORM_QUANTITIES
+enum { HQ_DEFORM_STRAIN = 1, HQ_DEFORM_STRAIN_RATE = 2, HQ_DEFORM_STRESS = 4, HQ_DEFORM_ROTATION = 8, HQ_DEFORM_ROTATION_RATE = 16 };
+#endif
+typedef struct {
+    int32_t        npoints;
+    const int32_t* ids;              /* [npoints][8] local node ids (octor numbering), as hqh_station_gradients returns them */
+    const double*  grad;             /* [npoints][3][8] grad[p][b][c] = d phi_c / d x_b at the point */
+    const double*  lame;             /* [npoints][2] lambda, mu of the point's element; NULL unless HQ_DEFORM_STRESS */
+    int32_t        rate, first_step; /* a sample at the head of every step s >= first_step with s % rate == 0 */
+    int32_t        quantities;       /* mask of HQ_DEFORM_*; non-zero, no unknown bits */
+    int32_t        reserved;
+} hq_deform_desc;
+HQ_API int hq_deform_add(hq_ctx* ctx, const hq_deform_desc* desc, int32_t* handle);
+HQ_API int hq_deform_fetch(hq_ctx* ctx, int32_t handle, double* vals, int32_t* when, int64_t* nsamples);
+HQ_API int hq_deform_load(hq_ctx* ctx, int32_t handle, const double* vals, const int32_t* when, int64_t nsamples);
+HQ_API int hq_deform_reset(hq_ctx* ctx, int32_t handle);
+HQ_API int hq_deform_clear(hq_ctx* ctx);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
