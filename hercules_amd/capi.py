@@ -26,7 +26,9 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_peak_add", "hq_peak_fetch", "hq_peak_load", "hq_peak_reset", "hq_peak_clear",
            "hq_spec_add", "hq_spec_coefficients", "hq_spec_fetch", "hq_spec_load", "hq_spec_reset", "hq_spec_clear",
            "hq_cum_add", "hq_cum_fetch", "hq_cum_load", "hq_cum_reset", "hq_cum_clear",
-           "hq_deform_add", "hq_deform_fetch", "hq_deform_load", "hq_deform_reset", "hq_deform_clear"]
+           "hq_deform_add", "hq_deform_fetch", "hq_deform_load", "hq_deform_reset", "hq_deform_clear",
+           "hq_attenuation_set", "hq_attenuation_info", "hq_attenuation_fetch", "hq_attenuation_load", "hq_attenuation_clear",
+           "hq_attenuation_plan_check"]
 HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
 HQ_PEAK_DISP, HQ_PEAK_VEL, HQ_PEAK_ACC = 1, 2, 4
 HQ_SPEC_MAX_PERIODS, HQ_SPEC_NVAL = 32, 4
@@ -66,6 +68,10 @@ class _Desc(ctypes.Structure):
                 ("variant", ctypes.c_int32), ("reserved", ctypes.c_int32), ("node_gnid", ctypes.c_void_p),
                 ("edata", ctypes.c_void_p), ("mat_bbase", ctypes.c_double), ("mat_threshold_damping", ctypes.c_double),
                 ("mat_threshold_vpvs", ctypes.c_double)]
+
+
+class _AttenuationDesc(ctypes.Structure):
+    _fields_ = [("coef", ctypes.c_void_p), ("freq", ctypes.c_double)]
 
 
 class _RecorderDesc(ctypes.Structure):
@@ -717,6 +723,42 @@ class Solver:
         """hq_deform_clear: drop every deformation tracker of the context and its device memory."""
         self._tracker_clear("deform")
 
+    def set_attenuation(self, coef, freq):
+        """hq_attenuation_set: BKT constant-Q attenuation from the ten floats per element coef [E, 10] (edata_t's order:
+        a0_shear, a1_shear, b_shear, g0_shear, g1_shear, then the same for kappa) and Param.theFreq.  Scatter variant, double
+        library; the memory variables start at 0."""
+        coef = np.ascontiguousarray(coef, np.float32)
+        if coef.shape != (self.E, 10):
+            raise HqError("set_attenuation: coef %r is not [%d, 10]" % (coef.shape, self.E))
+        d = _AttenuationDesc(_ptr(coef), float(freq))
+        _check(self._lib.hq_attenuation_set(self._h, ctypes.byref(d)), self._lib)
+
+    def attenuation_info(self):
+        """hq_attenuation_info -> dict(classes, slots, device_bytes); all 0 without attenuation."""
+        out = (ctypes.c_int64 * 4)()
+        _check(self._lib.hq_attenuation_info(self._h, out), self._lib)
+        return dict(classes=int(out[0]), slots=int(out[1]), device_bytes=int(out[2]))
+
+    def attenuation_state(self):
+        """hq_attenuation_fetch -> (shear1, shear2, kappa1, kappa2), each [E * 8, 3] in the reference's layout
+        (cindex = eindex * 8 + i)."""
+        out = [np.empty((self.E * 8, 3)) for _ in range(4)]
+        _check(self._lib.hq_attenuation_fetch(self._h, *[_ptr(a) for a in out]), self._lib)
+        return tuple(out)
+
+    def load_attenuation_state(self, shear1, shear2, kappa1, kappa2):
+        """hq_attenuation_load: four arrays [E * 8, 3] as attenuation_state returns them; corners that share a (node, class)
+        slot must agree bit for bit."""
+        arrs = [np.ascontiguousarray(a, np.float64) for a in (shear1, shear2, kappa1, kappa2)]
+        for a in arrs:
+            if a.shape != (self.E * 8, 3):
+                raise HqError("load_attenuation_state: an array of shape %r is not [%d, 3]" % (a.shape, self.E * 8))
+        _check(self._lib.hq_attenuation_load(self._h, *[_ptr(a) for a in arrs]), self._lib)
+
+    def clear_attenuation(self):
+        """hq_attenuation_clear: back to the Rayleigh step of the context's eTable."""
+        _check(self._lib.hq_attenuation_clear(self._h), self._lib)
+
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)
 
@@ -760,6 +802,19 @@ def brick_plan_check(desc):
     rep = (ctypes.c_int64 * len(BRICK_PLAN_REPORT))()
     _check(load_library().hq_brick_plan_check_n(ctypes.byref(desc), rep, ctypes.c_int32(len(BRICK_PLAN_REPORT))))
     return dict(zip(BRICK_PLAN_REPORT, [int(v) for v in rep]))
+
+
+ATTENUATION_PLAN_REPORT = ("classes", "slots", "device_bytes", "faults")
+
+
+def attenuation_plan_check(desc, coef):
+    """hq_attenuation_plan_check on a filled _Desc and coef [E, 10] float32: the slot plan, host only (no device needed)."""
+    coef = np.ascontiguousarray(coef, np.float32)
+    if coef.shape != (desc.lenum, 10):
+        raise HqError("attenuation_plan_check: coef %r is not [%d, 10]" % (coef.shape, desc.lenum))
+    rep = (ctypes.c_int64 * 4)()
+    _check(load_library().hq_attenuation_plan_check(ctypes.byref(desc), _ptr(coef), rep))
+    return dict(zip(ATTENUATION_PLAN_REPORT, [int(v) for v in rep]))
 
 
 def comm_unique_id():

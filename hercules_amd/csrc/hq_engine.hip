@@ -47,6 +47,7 @@
 #include "hq_cumul.h"
 #include "hq_deform.h"
 #include "hq_sdof.h"
+#include "hq_atten.h"
 #define HQ_SAMPLE_REAL hq_real
 #include "hq_sample.h"
 #include "hq_patch.h"
@@ -108,9 +109,25 @@ static int hq_rccl_load(void)
         if (r_ != ncclSuccess) return hq_fail(HQ_ERR_COMM, "%s: %s", #call, g_rccl.GetErrorString(r_)); \
     } while (0)
 
+#include "hq_atten_plan.h"
+
 /* ------------------------------------------------------------------------ */
 /* context                                                                  */
 /* ------------------------------------------------------------------------ */
+
+/* BKT attenuation of a scatter context (hq_attenuation_set; hq_atten.h, hq_atten_plan.h): the slot plan and the state on the
+ * device, the plan's corner table on the host for fetch / load in the reference's per-corner layout */
+struct hq_atten_dev {
+    bool on = false;
+    int32_t nclasses = 0, nslots = 0;
+    hq_dbuf<int32_t> d_eslot;        /* [8][Epad]                                          */
+    hq_dbuf<int32_t> d_slot_node;    /* [nslots]                                           */
+    hq_dbuf<int32_t> d_slot_class;   /* [nslots]                                           */
+    hq_dbuf<double> d_ktab;          /* [nclasses][HQ_ATTEN_NCOEF]                         */
+    hq_dbuf<double> d_mv;            /* [HQ_ATTEN_NSTATE][nslots] memory variables         */
+    hq_dbuf<double> d_w;             /* [HQ_ATTEN_NW][nslots] damping vectors of this step */
+    std::vector<int32_t> h_eslot, h_slot_node;
+};
 
 struct hq_dev_messenger {
     int32_t procid, nodecount;
@@ -167,6 +184,8 @@ struct hq_ctx {
     int32_t Epad = 0;
     hq_dbuf<int32_t> d_lnid;        /* [8][Epad] */
     hq_dbuf<double> d_c1, d_c2, d_beta;
+    bool etable_damped = false;     /* some c3 or c4 of the caller's eTable is not 0 (scatter variant) */
+    hq_atten_dev att;
     /* node data */
     double* d_nt = nullptr;         /* [N][7]; behind bricks only the rows of the nodes nt_first .. N - 1 exist (d_nt_rows), */
     hq_dbuf<double> d_nt_rows;      /* d_nt = d_nt_rows - 7 nt_first: no kernel reads a brick node's 7-double row */
@@ -352,6 +371,78 @@ hq_k_element_scatter(int32_t E, int32_t Epad, const int32_t* __restrict__ lnid,
 #pragma unroll
     for (int n = 0; n < 8; n++) {
         double* f = force + 3 * (int64_t)id[n];
+        unsafeAtomicAdd(f + 0, X[n]);
+        unsafeAtomicAdd(f + 1, Y[n]);
+        unsafeAtomicAdd(f + 2, Z[n]);
+    }
+}
+
+/*
+ * BKT attenuation, first half (calc_conv and the damping vectors of constant_Q_addforce, damping.c:110-371; the text is
+ * hq_atten.h's): one thread per (node, class) slot.  State and damping vectors are SoA [row][nslots], so a wave reads and
+ * writes 512-byte rows; slots are node-major, so the six field values of consecutive slots are consecutive (or the same)
+ * 24-byte rows.  Per slot: 48 B of fields, 96 B of memory variables read and written, 48 B of damping vectors written.
+ * The class's 18 doubles come through the scalar cache where the whole wave is of one class (nearly every wave).
+ */
+static __device__ __forceinline__ void hq_atten_slot(int32_t s, int64_t nslots, const double* __restrict__ k,
+                                                     const hq_real* __restrict__ p1, const hq_real* __restrict__ p2,
+                                                     double* __restrict__ mv, double* __restrict__ w)
+{
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        double f[HQ_ATTEN_NVAR], ws, wk;
+#pragma unroll
+        for (int v = 0; v < HQ_ATTEN_NVAR; v++) f[v] = mv[(int64_t)(3 * v + d) * nslots + s];
+        hq_atten_advance((double)p1[d], (double)p2[d], k, f, 1, &ws, &wk);
+#pragma unroll
+        for (int v = 0; v < HQ_ATTEN_NVAR; v++) mv[(int64_t)(3 * v + d) * nslots + s] = f[v];
+        w[(int64_t)d * nslots + s] = ws;
+        w[(int64_t)(3 + d) * nslots + s] = wk;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+hq_k_atten_advance(int32_t nslots, const int32_t* __restrict__ slot_node, const int32_t* __restrict__ slot_class,
+                   const double* __restrict__ ktab, const hq_real* __restrict__ u1, const hq_real* __restrict__ u2,
+                   double* __restrict__ mv, double* __restrict__ w)
+{
+    const int32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nslots) return;
+    const int64_t row = 3 * (int64_t)slot_node[s];
+    const int32_t cls = slot_class[s];
+    const int32_t cls0 = __builtin_amdgcn_readfirstlane(cls);
+    if (__all(cls == cls0)) hq_atten_slot(s, nslots, ktab + HQ_ATTEN_NCOEF * cls0, u1 + row, u2 + row, mv, w);
+    else hq_atten_slot(s, nslots, ktab + HQ_ATTEN_NCOEF * cls, u1 + row, u2 + row, mv, w);
+}
+
+/*
+ * BKT attenuation, second half (damping.c:373-410): one thread per element gathers the shear and dilatation damping
+ * vectors at its eight slots (SoA rows: neighbouring elements share cache lines as they do in the node arrays), runs the
+ * fused butterfly and adds the 24 force components with fp64 hardware atomics, as hq_k_element_scatter does.  beta is
+ * not read: under BKT c3 = c4 = 0 (compute_setab, psolve.c:5869).
+ */
+__global__ void __launch_bounds__(256)
+hq_k_element_bkt(int32_t E, int32_t Epad, int32_t nslots, const int32_t* __restrict__ lnid, const int32_t* __restrict__ eslot,
+                 const double* __restrict__ c1v, const double* __restrict__ c2v, const double* __restrict__ w,
+                 double* __restrict__ force)
+{
+    int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double X[8], Y[8], Z[8], P[8], Q[8], R[8];
+#pragma unroll
+    for (int n = 0; n < 8; n++) {
+        const double* ws = w + eslot[(int64_t)n * Epad + e];
+        X[n] = ws[0];
+        Y[n] = ws[(int64_t)nslots];
+        Z[n] = ws[2 * (int64_t)nslots];
+        P[n] = ws[3 * (int64_t)nslots];
+        Q[n] = ws[4 * (int64_t)nslots];
+        R[n] = ws[5 * (int64_t)nslots];
+    }
+    hq_element_force_bkt(X, Y, Z, P, Q, R, c1v[e], c2v[e]);
+#pragma unroll
+    for (int n = 0; n < 8; n++) {
+        double* f = force + 3 * (int64_t)lnid[(int64_t)n * Epad + e];
         unsafeAtomicAdd(f + 0, X[n]);
         unsafeAtomicAdd(f + 1, Y[n]);
         unsafeAtomicAdd(f + 2, Z[n]);
@@ -981,6 +1072,16 @@ static int hq_launch_source(hq_ctx* c)
 
 static int hq_launch_element_scatter(hq_ctx* c)
 {
+    if (c->att.on) {                                         /* BKT: calc_conv, then constant_Q_addforce (psolve.c:3995-3999) */
+        const hq_atten_dev& A = c->att;
+        hq_k_atten_advance<<<hq_blocks(A.nslots, 256), 256, 0, c->stream>>>(
+            A.nslots, A.d_slot_node, A.d_slot_class, A.d_ktab, c->d_u[c->now], c->d_u[c->prev], A.d_mv, A.d_w);
+        hq_mark(c);                                          /* (hq_run_timed brackets the dominant kernel: hq_k_element_bkt) */
+        hq_k_element_bkt<<<hq_blocks(c->E, 256), 256, 0, c->stream>>>(
+            c->E, c->Epad, A.nslots, c->d_lnid, A.d_eslot, c->d_c1, c->d_c2, A.d_w, c->d_force);
+        hq_mark(c);
+        return HQ_OK;
+    }
     hq_mark(c);
     hq_k_element_scatter<<<hq_blocks(c->E, 256), 256, 0, c->stream>>>(
         c->E, c->Epad, c->d_lnid, c->d_c1, c->d_c2, c->d_beta, c->d_u[c->now], c->d_u[c->prev], c->d_force);
@@ -1676,6 +1777,8 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
     if (variant == HQ_VARIANT_SCATTER) {
         if ((rc = c->d_force.alloc(&c->bytes, n3)) != HQ_OK || (rc = c->d_force.fill(0, c->stream)) != HQ_OK) return bail(rc);
         c->Epad = (c->E + 63) & ~63;
+        for (int64_t e = 0; e < c->E && !c->etable_damped; e++)
+            c->etable_damped = d->eTable[4 * e + 2] != 0.0 || d->eTable[4 * e + 3] != 0.0;
         std::vector<int32_t> soa((size_t)8 * c->Epad, 0);
         for (int64_t e = 0; e < c->E; e++)
             for (int n = 0; n < 8; n++) soa[(size_t)n * c->Epad + e] = d->lnid[8 * e + n];
@@ -2435,6 +2538,7 @@ extern "C" int hq_run_timed(hq_ctx* c, int32_t nsteps, double* total_ms, double*
 
 extern "C" const char* hq_dominant_kernel(hq_ctx* c)
 {
+    if (c && c->att.on) return "hq_k_element_bkt";
     if (!c || c->variant != HQ_VARIANT_PATCH) return "hq_k_element_scatter";
     if (2 * c->bricks.nb > (int64_t)c->N) return "hq_k_brick";
     if (2 * c->plan.nstencil > c->plan.npatches) return "hq_k_patch_stencil";
@@ -2525,7 +2629,150 @@ extern "C" int hq_upload(hq_ctx* c, const hq_real* tm1, const hq_real* tm2, int3
         HQ_HIP(hipMemsetAsync(c->d_u[c->spare], 0, bytes, c->stream));
         HQ_HIP(hipStreamSynchronize(c->stream));
     }
+    /* the memory variables after a restart: calloc, psolve.c:3322-3325 (io_checkpoint.c carries tm1 / tm2 only); an exact
+     * restart follows with hq_attenuation_load */
+    if (c->att.on) HQ_TRY(c->att.d_mv.fill(0, c->stream));
     c->step = step;
+    return HQ_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+/* BKT attenuation (hq_atten.h, hq_atten_plan.h)                            */
+/* ------------------------------------------------------------------------ */
+
+extern "C" int hq_attenuation_set(hq_ctx* c, const hq_attenuation_desc* a)
+{
+    if (!c || !a || !a->coef) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (sizeof(hq_real) != sizeof(double))
+        return hq_fail(HQ_ERR_STATE, "attenuation: not in the float library (the memory variables are double state)%s", "");
+    if (c->variant != HQ_VARIANT_SCATTER)
+        return hq_fail(HQ_ERR_STATE, "attenuation runs in the scatter variant only: create the context with HQ_VARIANT_SCATTER%s", "");
+    if (!(a->freq > 0.0) || !std::isfinite(a->freq)) return hq_fail(HQ_ERR_ARG, "attenuation: freq must be finite and > 0%s", "");
+    if (c->etable_damped)
+        return hq_fail(HQ_ERR_ARG, "attenuation: the eTable has c3 or c4 != 0; under BKT compute_setab yields a = b = 0 (psolve.c:5869)%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    std::vector<int32_t> soa((size_t)8 * c->Epad);
+    HQ_TRY(hq_copy_wait(soa.data(), c->d_lnid, sizeof(int32_t) * soa.size(), hipMemcpyDeviceToHost, c->stream));
+    hq_atten_plan P;
+    HQ_TRY(hq_atten_plan_build(c->E, c->N, soa.data(), c->Epad, a->coef, &P));
+    std::vector<double> ktab((size_t)P.nclasses * HQ_ATTEN_NCOEF);
+    for (int32_t k = 0; k < P.nclasses; k++) {
+        hq_atten_class_coef(P.rows.data() + HQ_ATTEN_NROW * (size_t)k, a->freq, c->dt, ktab.data() + HQ_ATTEN_NCOEF * (size_t)k);
+        for (int j = 0; j < HQ_ATTEN_NCOEF; j++)
+            if (!std::isfinite(ktab[HQ_ATTEN_NCOEF * (size_t)k + j])) return hq_fail(HQ_ERR_ARG, "attenuation: a class coefficient is not finite%s", "");
+    }
+    /* everything is built beside the context's own and moved in at the end: a refusal leaves the context as it was */
+    hq_atten_dev A;
+    int rc;                                          /* (no ledger: the arrays move; hq_ctx.bytes takes their sum below) */
+    if ((rc = A.d_eslot.put(nullptr, P.eslot, c->stream)) != HQ_OK || (rc = A.d_slot_node.put(nullptr, P.slot_node, c->stream)) != HQ_OK ||
+        (rc = A.d_slot_class.put(nullptr, P.slot_class, c->stream)) != HQ_OK || (rc = A.d_ktab.put(nullptr, ktab, c->stream)) != HQ_OK ||
+        (rc = A.d_mv.alloc(nullptr, (size_t)HQ_ATTEN_NSTATE * P.nslots)) != HQ_OK || (rc = A.d_mv.fill(0, c->stream)) != HQ_OK ||
+        (rc = A.d_w.alloc(nullptr, (size_t)HQ_ATTEN_NW * P.nslots)) != HQ_OK || (rc = A.d_w.fill(0, c->stream)) != HQ_OK)
+        return rc;                                   /* (A's arrays go with it) */
+    const int64_t added = (int64_t)(A.d_eslot.bytes() + A.d_slot_node.bytes() + A.d_slot_class.bytes() + A.d_ktab.bytes() +
+                                    A.d_mv.bytes() + A.d_w.bytes());
+    if (added != hq_atten_bytes(P.nslots, P.Epad, P.nclasses)) return hq_fail(HQ_ERR_STATE, "attenuation: the device bytes are not the header's formula%s", "");
+    A.nclasses = P.nclasses; A.nslots = P.nslots;
+    A.h_eslot = std::move(P.eslot); A.h_slot_node = std::move(P.slot_node);
+    A.on = true;
+    hq_attenuation_clear(c);
+    c->att = std::move(A);
+    c->bytes += added;
+    return HQ_OK;
+}
+
+extern "C" int hq_attenuation_clear(hq_ctx* c)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (!c->att.on) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    c->bytes -= hq_atten_bytes(c->att.nslots, c->Epad, c->att.nclasses);
+    c->att = hq_atten_dev();
+    return HQ_OK;
+}
+
+extern "C" int hq_attenuation_info(hq_ctx* c, int64_t out[4])
+{
+    if (!c || !out) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    out[0] = c->att.nclasses; out[1] = c->att.nslots;
+    out[2] = c->att.on ? hq_atten_bytes(c->att.nslots, c->Epad, c->att.nclasses) : 0;
+    out[3] = 0;
+    return HQ_OK;
+}
+
+/* the four arrays of the reference's layout, [lenum * 8][3] each (cindex = eindex * 8 + i); a NULL one is left out */
+extern "C" int hq_attenuation_fetch(hq_ctx* c, double* shear1, double* shear2, double* kappa1, double* kappa2)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (!c->att.on) return hq_fail(HQ_ERR_STATE, "attenuation is not set on this context%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const hq_atten_dev& A = c->att;
+    const int64_t ns = A.nslots;
+    std::vector<double> mv((size_t)HQ_ATTEN_NSTATE * ns);
+    HQ_TRY(hq_copy_wait(mv.data(), A.d_mv, sizeof(double) * mv.size(), hipMemcpyDeviceToHost, c->stream));
+    c->d2h_bytes += (int64_t)(sizeof(double) * mv.size());
+    double* out[HQ_ATTEN_NVAR] = { shear1, shear2, kappa1, kappa2 };
+    for (int v = 0; v < HQ_ATTEN_NVAR; v++) {
+        if (!out[v]) continue;
+#pragma omp parallel for schedule(static)
+        for (int64_t e = 0; e < c->E; e++)
+            for (int i = 0; i < 8; i++) {
+                const int64_t s = A.h_eslot[(size_t)(i * (int64_t)c->Epad + e)];
+                for (int d = 0; d < 3; d++) out[v][3 * (8 * e + i) + d] = mv[(size_t)((3 * v + d) * ns + s)];
+            }
+    }
+    return HQ_OK;
+}
+
+extern "C" int hq_attenuation_load(hq_ctx* c, const double* shear1, const double* shear2, const double* kappa1, const double* kappa2)
+{
+    if (!c || !shear1 || !shear2 || !kappa1 || !kappa2) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (!c->att.on) return hq_fail(HQ_ERR_STATE, "attenuation is not set on this context%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const hq_atten_dev& A = c->att;
+    const int64_t ns = A.nslots;
+    const double* in[HQ_ATTEN_NVAR] = { shear1, shear2, kappa1, kappa2 };
+    std::vector<double> mv((size_t)HQ_ATTEN_NSTATE * ns);
+    std::vector<char> have((size_t)ns, 0);
+    for (int64_t e = 0; e < c->E; e++)
+        for (int i = 0; i < 8; i++) {
+            const int64_t s = A.h_eslot[(size_t)(i * (int64_t)c->Epad + e)];
+            for (int v = 0; v < HQ_ATTEN_NVAR; v++)
+                for (int d = 0; d < 3; d++) {
+                    const double x = in[v][3 * (8 * e + i) + d];
+                    double& slot = mv[(size_t)((3 * v + d) * ns + s)];
+                    if (!std::isfinite(x)) return hq_fail(HQ_ERR_ARG, "attenuation: a memory variable to load is not finite%s", "");
+                    if (have[(size_t)s] && memcmp(&slot, &x, sizeof x) != 0) {
+                        char node[32];
+                        snprintf(node, sizeof node, "%d", (int)A.h_slot_node[(size_t)s]);
+                        return hq_fail(HQ_ERR_ARG, "attenuation: corners of one class that share node %s carry different memory variables", node);
+                    }
+                    slot = x;
+                }
+            have[(size_t)s] = 1;
+        }
+    c->h2d_bytes += (int64_t)(sizeof(double) * mv.size());
+    return c->att.d_mv.upload(mv.data(), mv.size(), c->stream);
+}
+
+extern "C" int hq_attenuation_plan_check(const hq_desc* d, const float* coef, int64_t report[4])
+{
+    if (!d || !coef || !report) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_options opts;
+    hq_options_resolve(&opts, nullptr);
+    hq_prep prep;
+    HQ_TRY(hq_prepare(d, opts, 0, &prep));
+    hq_atten_plan P;
+    HQ_TRY(hq_atten_plan_build(d->lenum, d->nharbored, d->lnid, 0, coef, &P));
+    int64_t bad = hq_atten_plan_faults(d->lenum, d->lnid, P);
+    std::vector<char> has((size_t)d->nharbored, 0);
+    for (int32_t n : P.slot_node) has[(size_t)n] = 1;
+    for (int32_t k = 0; k < d->ldnnum; k++) bad += !has[(size_t)d->dn_ldnid[k]];      /* a hanging node is a node like any other */
+    report[0] = P.nclasses; report[1] = P.nslots; report[2] = hq_atten_bytes(P.nslots, P.Epad, P.nclasses); report[3] = bad;
     return HQ_OK;
 }
 

@@ -127,6 +127,52 @@ __host__ __device__ __forceinline__ void hq_element_force(double X[8], double Y[
 }
 
 /*
+ * The element force under BKT attenuation (constant_Q_addforce, damping.c:373-398): A (D_mu A^T ws + D_kappa A^T wk) with
+ * the damping vectors of hq_atten.h, shear in X, Y, Z and dilatation in P, Q, R; out: X, Y, Z = f_e (P, Q, R are spent).
+ * firstVector_mu (stiffness.c:351-379) is firstVector with a = 4b/3, c = -2b/3, b = mu; firstVector_kappa (:321-349) is
+ * firstVector with a = c = kappa, b = 0; mu = -0.5625 c1, kappa = -0.5625 (c2 + 2 c1 / 3).  Both inputs go through the
+ * forward butterfly, the two diagonal products are summed per mode, and ONE transposed butterfly expands the sum.
+ */
+__host__ __device__ __forceinline__ void hq_element_force_bkt(double X[8], double Y[8], double Z[8],
+                                                              double P[8], double Q[8], double R[8], double c1, double c2)
+{
+    const double mu = -0.5625 * c1;                               /* damping.c:374 */
+    const double kappa = -0.5625 * (c2 + 2. / 3. * c1);           /* damping.c:373 */
+    const double third = 1.0 / 3.0;
+    const double a = mu * (4.0 * third), c = -mu * (2.0 * third), b = mu;
+    const double b3 = b * third, c3 = c * third, ab3 = (a + b) * third;
+    const double a2b9 = (a + 2.0 * b) * (1.0 / 9.0);
+    const double k3 = kappa * third, k9 = kappa * (1.0 / 9.0);
+
+    hq_wht_fwd(X); hq_wht_fwd(Y); hq_wht_fwd(Z);
+    hq_wht_fwd(P); hq_wht_fwd(Q); hq_wht_fwd(R);
+
+    const double dil = kappa * (P[1] + Q[2] + R[4]);         /* the dilatation's only first-order mode */
+    const double sxy = b * (Y[1] + X[2]);
+    const double sxz = b * (Z[1] + X[4]);
+    const double syz = b * (Z[2] + Y[4]);
+    const double nx = a * X[1] + c * (Y[2] + Z[4]) + dil;
+    const double ny = a * Y[2] + c * (X[1] + Z[4]) + dil;
+    const double nz = a * Z[4] + c * (X[1] + Y[2]) + dil;
+    const double t = X[6] + Y[5] + Z[3];
+    const double gx6 = b3 * (t + X[6]);
+    const double gy5 = b3 * (t + Y[5]);
+    const double gz3 = b3 * (t + Z[3]);
+    const double gx5 = ab3 * X[5] + c3 * Y[6] + k3 * (P[5] + Q[6]);
+    const double gx3 = ab3 * X[3] + c3 * Z[6] + k3 * (P[3] + R[6]);
+    const double gy6 = ab3 * Y[6] + c3 * X[5] + k3 * (Q[6] + P[5]);
+    const double gy3 = ab3 * Y[3] + c3 * Z[5] + k3 * (Q[3] + R[5]);
+    const double gz6 = ab3 * Z[6] + c3 * X[3] + k3 * (R[6] + P[3]);
+    const double gz5 = ab3 * Z[5] + c3 * Y[3] + k3 * (R[5] + Q[3]);
+
+    X[0] = 0.0; X[1] = nx;  X[2] = sxy; X[3] = gx3; X[4] = sxz; X[5] = gx5; X[6] = gx6; X[7] = a2b9 * X[7] + k9 * P[7];
+    Y[0] = 0.0; Y[1] = sxy; Y[2] = ny;  Y[3] = gy3; Y[4] = syz; Y[5] = gy5; Y[6] = gy6; Y[7] = a2b9 * Y[7] + k9 * Q[7];
+    Z[0] = 0.0; Z[1] = sxz; Z[2] = syz; Z[3] = gz3; Z[4] = nz;  Z[5] = gz5; Z[6] = gz6; Z[7] = a2b9 * Z[7] + k9 * R[7];
+
+    hq_wht_inv(X); hq_wht_inv(Y); hq_wht_inv(Z);
+}
+
+/*
  * (c1, c2, beta) of an element from the three floats solver_init derived them from -- 12 bytes instead of 24, exactly:
  * mu_and_lambda (psolve.c:3236-3272) evaluates mu = rho Vs Vs in SINGLE precision (float operands), lambda as a
  * double difference, and solver_init (psolve.c:3387-3409) builds

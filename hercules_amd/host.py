@@ -19,7 +19,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
            "hqh_gradient_weights", "hqh_station_gradients", "hqh_station_moduli", "hqh_deform_fold",
-           "hqh_station_kinematics", "hqh_peak_fold", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
+           "hqh_station_kinematics", "hqh_peak_fold", "hqh_atten_class_coef", "hqh_atten_advance", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
            "hqh_cvm_open", "hqh_cvm_close", "hqh_cvm_info", "hqh_cvm_query", "hqh_cvm_grid"]
 
@@ -869,6 +869,40 @@ def peak_fold(steps, samples, quantities, peaks=None, when=None):
                                              ctypes.c_void_p(steps.ctypes.data), ctypes.c_void_p(samples.ctypes.data),
                                              ctypes.c_void_p(peaks.ctypes.data), ctypes.c_void_p(when.ctypes.data)))
     return peaks, when
+
+
+ATTEN_NROW, ATTEN_NCOEF, ATTEN_NSTATE, ATTEN_NW = 10, 18, 12, 6        # csrc/hq_atten.h
+
+
+def atten_class_coef(rows, freq, dt):
+    """hqh_atten_class_coef: the classes' ten floats [nclasses, 10] (edata_t's order) -> (k [nclasses, 18] in hq_atten.h's
+    layout, rmax = 2 pi freq dt)."""
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, ATTEN_NROW)
+    k = np.zeros((len(rows), ATTEN_NCOEF))
+    rmax = ctypes.c_double()
+    capi._check(load_library().hqh_atten_class_coef(ctypes.c_int32(len(rows)), ctypes.c_void_p(rows.ctypes.data), ctypes.c_double(freq),
+                                                    ctypes.c_double(dt), ctypes.c_void_p(k.ctypes.data), ctypes.byref(rmax)))
+    return k, rmax.value
+
+
+def atten_advance(slot_node, slot_class, k, u1, u2, mv, w=None):
+    """hqh_atten_advance: one step of the memory variables mv [12, nslots] (in place; float64, C-contiguous) and the damping
+    vectors w [6, nslots] of a slot plan (slot_node, slot_class [nslots]) with the class doubles k [nclasses, 18] and the
+    fields u1, u2 [N, 3].  Returns (mv, w)."""
+    slot_node = np.ascontiguousarray(slot_node, np.int32)
+    slot_class = np.ascontiguousarray(slot_class, np.int32)
+    k = np.ascontiguousarray(k, np.float64).reshape(-1, ATTEN_NCOEF)
+    u1, u2 = np.ascontiguousarray(u1, np.float64), np.ascontiguousarray(u2, np.float64)
+    ns = len(slot_node)
+    if w is None:
+        w = np.zeros((ATTEN_NW, ns))
+    if (mv.dtype != np.float64 or mv.shape != (ATTEN_NSTATE, ns) or not mv.flags.c_contiguous or w.dtype != np.float64
+            or w.shape != (ATTEN_NW, ns) or not w.flags.c_contiguous or u1.shape != u2.shape or len(slot_class) != ns):
+        raise capi.HqError("atten_advance: mv / w are not the state of %d slots" % ns)
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
+    capi._check(load_library().hqh_atten_advance(ctypes.c_int32(ns), ptr(slot_node), ptr(slot_class), ctypes.c_int32(len(k)), ptr(k),
+                                                 ctypes.c_int32(len(u1)), ptr(u1), ptr(u2), ptr(mv), ptr(w)))
+    return mv, w
 
 
 def cum_fold(steps, samples, quantities, threshold=0.0, sums=None, span=None):

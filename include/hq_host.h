@@ -316,6 +316,16 @@ HQ_API int hqh_station_kinematics(const double* phi, const double* tm1, const do
  * HQ_ERR_ARG for null pointers (where there is something to read), negative counts, quantities 0 or with unknown bits. */
 HQ_API int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps,
                          const double* samples, double* peaks, int32_t* when);
+/* BKT attenuation on the host (csrc/hq_atten.h, the text hq_attenuation_set and hq_k_atten_advance compile).
+ * hqh_atten_class_coef: the 18 doubles per class (k [nclasses][18], hq_atten.h's layout) from the classes' ten floats (rows
+ * [nclasses][10], edata_t's order), Param.theFreq and theDeltaT; *rmax (may be NULL) = 2 pi freq dt.
+ * hqh_atten_advance: one step of calc_conv and the damping vectors of constant_Q_addforce over a slot plan: slot s belongs to
+ * node slot_node[s] and class slot_class[s]; u1, u2 [nnodes][3]; mv [12][nslots] (row = variable * 3 + component; variables
+ * shear 1, 2, dilatation 1, 2) is advanced in place, w [6][nslots] (ws x y z, wk x y z) is written: the device's layout.
+ * HQ_ERR_ARG for null pointers (where there is something to read), negative counts, ids out of range, freq or dt not > 0. */
+HQ_API int hqh_atten_class_coef(int32_t nclasses, const float* rows, double freq, double dt, double* k, double* rmax);
+HQ_API int hqh_atten_advance(int32_t nslots, const int32_t* slot_node, const int32_t* slot_class, int32_t nclasses,
+                             const double* k, int32_t nnodes, const double* u1, const double* u2, double* mv, double* w);
 /* The cumulative-intensity fold on the host (csrc/hq_cumul.h, the text hq_k_cum compiles): recorder samples added into the
  * state hq_cum_fetch delivers -- the route of a caller without device trackers.  samples, steps and `quantities` as
  * hqh_peak_fold's; threshold [nq], per quantity of the mask in mask order, finite and >= 0, squared once here.  sums

@@ -760,6 +760,56 @@ HQ_API int hq_deform_reset(hq_ctx* ctx, int32_t handle);
 HQ_API int hq_deform_clear(hq_ctx* ctx);
 
 /*
+ * BKT constant-Q attenuation (type_of_damping = bkt: calc_conv and constant_Q_addforce, damping.c:110-416), scatter
+ * variant, double library.  With attenuation set the step is
+ *     hq_k_source -> hq_k_atten_advance -> hq_k_element_bkt -> (exchanges, hq_k_distribute) -> hq_k_update
+ * and everything but the two kernels in the middle runs as it does without.
+ *
+ * coef: the ten floats per element a0_shear, a1_shear, b_shear, g0_shear, g1_shear, a0_kappa, a1_kappa, b_kappa, g0_kappa,
+ * g1_kappa in edata_t's order (psolve.h:96) -- the caller's edata + 4; freq: Param.theFreq.  The library holds no Q table and
+ * no Qs(Vs) rule: those are mesh-time (mesh_correct_properties, psolve.c:7239-7329) and stay the caller's.
+ *
+ * State.  The reference keeps four memory variables per element corner (768 B per element).  A corner's variable depends
+ * on its element's ten floats and its node's history only, so the library keeps one copy per (node, class) SLOT, a class
+ * being one distinct row of the ten floats (bitwise): bit for bit the reference's values (csrc/hq_atten.h states why both
+ * of the reference's branches fall out of one formula).  Device bytes added, exactly (hq_info.device_bytes grows by it, and
+ * hq_attenuation_info / hq_attenuation_plan_check report it):
+ *     144 nslots  (12 rows of memory variables + 6 rows of damping vectors, double, SoA [row][nslots])
+ *   +  32 Epad    (the slot of every element corner, int32 [8][Epad], Epad = lenum rounded up to 64)
+ *   +   8 nslots  (every slot's node and class, int32)
+ *   + 144 nclasses (18 doubles per class)
+ * In a uniform region that is 152 B per node.
+ *
+ * hq_attenuation_set: between steps; the memory variables start at 0; set again replaces plan and state.  It refuses, with
+ * the context left as it was: a context of the patch variant (HQ_ERR_STATE: create with HQ_VARIANT_SCATTER), the float
+ * library (HQ_ERR_STATE), an eTable with any c3 or c4 != 0 (HQ_ERR_ARG: under BKT compute_setab yields a = b = 0,
+ * psolve.c:5869), freq <= 0 or not finite, a coefficient that is not finite (HQ_ERR_ARG).
+ * hq_attenuation_info: out = {classes, slots, device bytes added, 0}; all 0 on a context without attenuation.
+ * hq_attenuation_fetch / _load speak the reference's layout: four arrays [lenum * 8][3] (cindex = eindex * 8 + i) for
+ * conv_shear_1, conv_shear_2, conv_kappa_1, conv_kappa_2.  fetch leaves out an array passed as NULL; load needs all four
+ * and refuses (HQ_ERR_ARG, the text names the node) an input in which two corners of one slot differ, or a value that is
+ * not finite.  hq_upload zeroes the memory variables -- the reference's own restart (io_checkpoint.c carries tm1 / tm2
+ * only and the arrays are calloc'ed); an exact restart is hq_upload followed by hq_attenuation_load.
+ * hq_attenuation_clear: back to the Rayleigh step of the context's eTable; the added bytes go.
+ * hq_attenuation_plan_check: host only, no device -- the slot plan of `desc` (lnid, nharbored, the hanging-node table) under
+ * `coef`: report = {classes, slots, device bytes an attenuated context adds, faults}, faults counting element corners whose
+ * slot is not (their node, their class), slots out of node-major order and hanging nodes without a slot.
+ * On an attenuated context hq_dominant_kernel names hq_k_element_bkt, and hq_phase_force runs the two kernels (every call
+ * advances the memory variables one step, as calc_conv does).
+ * Not here: attenuation in the patch and brick kernels, the float library, the Q table and the velocity correction.
+ */
+typedef struct {
+    const float* coef;               /* [lenum][10], order above */
+    double freq;                     /* Param.theFreq            */
+} hq_attenuation_desc;
+HQ_API int hq_attenuation_set(hq_ctx* ctx, const hq_attenuation_desc* desc);
+HQ_API int hq_attenuation_info(hq_ctx* ctx, int64_t out[4]);
+HQ_API int hq_attenuation_fetch(hq_ctx* ctx, double* shear1, double* shear2, double* kappa1, double* kappa2);
+HQ_API int hq_attenuation_load(hq_ctx* ctx, const double* shear1, const double* shear2, const double* kappa1, const double* kappa2);
+HQ_API int hq_attenuation_clear(hq_ctx* ctx);
+HQ_API int hq_attenuation_plan_check(const hq_desc* desc, const float* coef, int64_t report[4]);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
