@@ -28,7 +28,8 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_cum_add", "hq_cum_fetch", "hq_cum_load", "hq_cum_reset", "hq_cum_clear",
            "hq_deform_add", "hq_deform_fetch", "hq_deform_load", "hq_deform_reset", "hq_deform_clear",
            "hq_attenuation_set", "hq_attenuation_info", "hq_attenuation_fetch", "hq_attenuation_load", "hq_attenuation_clear",
-           "hq_attenuation_plan_check"]
+           "hq_attenuation_plan_check", "hq_attenuation_set_split", "hq_attenuation_split_plan_check", "hq_attenuation_split_plan_tables",
+           "hq_attenuation_split_table_faults"]
 HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
 HQ_PEAK_DISP, HQ_PEAK_VEL, HQ_PEAK_ACC = 1, 2, 4
 HQ_SPEC_MAX_PERIODS, HQ_SPEC_NVAL = 32, 4
@@ -723,15 +724,23 @@ class Solver:
         """hq_deform_clear: drop every deformation tracker of the context and its device memory."""
         self._tracker_clear("deform")
 
-    def set_attenuation(self, coef, freq):
+    def set_attenuation(self, coef, freq, split=False):
         """hq_attenuation_set: BKT constant-Q attenuation from the ten floats per element coef [E, 10] (edata_t's order:
         a0_shear, a1_shear, b_shear, g0_shear, g1_shear, then the same for kappa) and Param.theFreq.  Scatter variant, double
-        library; the memory variables start at 0."""
+        library; the memory variables start at 0.  split: hq_attenuation_set_split, the correction pass beside the step of a
+        context of the patch variant."""
         coef = np.ascontiguousarray(coef, np.float32)
         if coef.shape != (self.E, 10):
             raise HqError("set_attenuation: coef %r is not [%d, 10]" % (coef.shape, self.E))
         d = _AttenuationDesc(_ptr(coef), float(freq))
-        _check(self._lib.hq_attenuation_set(self._h, ctypes.byref(d)), self._lib)
+        fn = self._lib.hq_attenuation_set_split if split else self._lib.hq_attenuation_set
+        _check(fn(self._h, ctypes.byref(d)), self._lib)
+
+    def attenuation_split(self):
+        """Is the context's attenuation the split form (hq_attenuation_info's out[3])?"""
+        out = (ctypes.c_int64 * 4)()
+        _check(self._lib.hq_attenuation_info(self._h, out), self._lib)
+        return bool(out[3])
 
     def attenuation_info(self):
         """hq_attenuation_info -> dict(classes, slots, device_bytes); all 0 without attenuation."""
@@ -815,6 +824,41 @@ def attenuation_plan_check(desc, coef):
     rep = (ctypes.c_int64 * 4)()
     _check(load_library().hq_attenuation_plan_check(ctypes.byref(desc), _ptr(coef), rep))
     return dict(zip(ATTENUATION_PLAN_REPORT, [int(v) for v in rep]))
+
+
+def attenuation_split_plan_check(desc, coef):
+    """hq_attenuation_split_plan_check on a filled _Desc and coef [E, 10] float32: slot plan, node -> (element, corner) table and
+    hanging-node lists of a split context, host only (no device needed)."""
+    coef = np.ascontiguousarray(coef, np.float32)
+    if coef.shape != (desc.lenum, 10):
+        raise HqError("attenuation_split_plan_check: coef %r is not [%d, 10]" % (coef.shape, desc.lenum))
+    rep = (ctypes.c_int64 * 4)()
+    _check(load_library().hq_attenuation_split_plan_check(ctypes.byref(desc), _ptr(coef), rep))
+    return dict(zip(ATTENUATION_PLAN_REPORT, [int(v) for v in rep]))
+
+
+def attenuation_split_plan_tables(desc):
+    """hq_attenuation_split_plan_tables -> (epos [E], nptr [N + 1], nent [8 E], sd [H, 3]) int32, in the numbering hq_create
+    gives desc."""
+    lib = load_library()
+    counts = (ctypes.c_int64 * 3)()
+    _check(lib.hq_attenuation_split_plan_tables(ctypes.byref(desc), None, None, None, None, counts))
+    epos = np.zeros(desc.lenum, np.int32)
+    nptr, nent, sd = np.zeros(counts[0], np.int32), np.zeros(counts[1], np.int32), np.zeros((counts[2], 3), np.int32)
+    _check(lib.hq_attenuation_split_plan_tables(ctypes.byref(desc), _ptr(epos), _ptr(nptr), _ptr(nent), _ptr(sd), counts))
+    return epos, nptr, nent, sd
+
+
+def attenuation_split_table_faults(desc, epos, nptr, nent, sd):
+    """hq_attenuation_split_table_faults: the faults the split plan check counts in the given tables."""
+    epos, nptr, nent = [np.ascontiguousarray(a, np.int32) for a in (epos, nptr, nent)]
+    sd = np.ascontiguousarray(sd, np.int32).reshape(-1, 3)
+    if len(nptr) != desc.nharbored + 1 or len(nent) != 8 * desc.lenum or len(epos) != desc.lenum:
+        raise HqError("attenuation_split_table_faults: tables of %d, %d entries for %d nodes, %d elements" % (len(nptr), len(nent), desc.nharbored, desc.lenum))
+    faults = ctypes.c_int64()
+    _check(load_library().hq_attenuation_split_table_faults(ctypes.byref(desc), _ptr(epos), _ptr(nptr), _ptr(nent), _ptr(sd) if len(sd) else None,
+                                                            ctypes.c_int64(len(sd)), ctypes.byref(faults)))
+    return int(faults.value)
 
 
 def comm_unique_id():

@@ -103,4 +103,31 @@ HQ_ATTEN_FN void hq_atten_advance(double u1, double u2, const double* k, double*
     *wk = w[1];
 }
 
+/*
+ * The same slot and component in DELTA form (hq_attenuation_set_split): the recurrence above operation for operation, so the
+ * memory variables it leaves are hq_atten_advance's bit for bit, and of the damping vectors the part that is not u1 itself,
+ *     ds, dk = bq (u1 - u2) - (a0 f0 + a1 f1)        (ws = ds + u1, wk = dk + u1: the final addition is left out).
+ * The BKT force is linear in the damping vectors, so mu K_mu ds + kappa K_kappa dk is what attenuation adds to the elastic
+ * force of u1.  A class with csum == 0 (a0 = a1 = bq = 0) yields 0 (u1 - u2) - (0 f0 + 0 f1) == +-0: nothing is added.
+ */
+HQ_ATTEN_FN void hq_atten_advance_delta(double u1, double u2, const double* k, double* f, int64_t fstride, double* ds, double* dk)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double d = u1 - u2;
+    double w[2];
+    for (int m = 0; m < 2; m++) {
+        const double* q = k + 9 * m;
+        double* fm = f + 2 * m * fstride;
+        const double f0 = (q[0] * u1 + q[1] * u2) + q[2] * fm[0];
+        const double f1 = (q[3] * u1 + q[4] * u2) + q[5] * fm[fstride];
+        fm[0] = f0;
+        fm[fstride] = f1;
+        w[m] = q[8] * d - (q[6] * f0 + q[7] * f1);
+    }
+    *ds = w[0];
+    *dk = w[1];
+}
+
 #endif /* HQ_ATTEN_H */

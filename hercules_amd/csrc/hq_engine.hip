@@ -110,16 +110,27 @@ static int hq_rccl_load(void)
     } while (0)
 
 #include "hq_atten_plan.h"
+#include "hq_atten_split.h"
 
 /* ------------------------------------------------------------------------ */
 /* context                                                                  */
 /* ------------------------------------------------------------------------ */
 
 /* BKT attenuation of a scatter context (hq_attenuation_set; hq_atten.h, hq_atten_plan.h): the slot plan and the state on the
- * device, the plan's corner table on the host for fetch / load in the reference's per-corner layout */
+ * device, the plan's corner table on the host for fetch / load in the reference's per-corner layout.  split: of a patch
+ * context (hq_attenuation_set_split; hq_atten_split.h) -- d_w then holds the delta vectors, and the tables below exist */
 struct hq_atten_dev {
-    bool on = false;
+    bool on = false, split = false;
     int32_t nclasses = 0, nslots = 0;
+    int64_t bytes = 0;               /* the device bytes of everything below (the header's formulas)   */
+    hq_dbuf<double> d_ef;            /* [3][8][Epad] corner forces of this step                         */
+    hq_dbuf<double> d_dF;            /* [N][3] their sums per node                                      */
+    hq_dbuf<double> d_mass;          /* [N] n_t[n][0], device numbering                                 */
+    hq_dbuf<double> d_c1, d_c2;      /* [E]                                                             */
+    hq_dbuf<int32_t> d_nptr, d_nent; /* [N + 1], [8 E] node -> (element, corner), element order         */
+    int32_t nSD = 0;                 /* hq_k_distribute's tables over ALL hanging nodes, on node ids    */
+    hq_dbuf<int32_t> d_sd_dst, d_sd_ptr, d_sd_src, d_sd_deps;
+    int64_t nanchors = 0, npairs = 0;
     hq_dbuf<int32_t> d_eslot;        /* [8][Epad]                                          */
     hq_dbuf<int32_t> d_slot_node;    /* [nslots]                                           */
     hq_dbuf<int32_t> d_slot_class;   /* [nslots]                                           */
@@ -184,8 +195,14 @@ struct hq_ctx {
     int32_t Epad = 0;
     hq_dbuf<int32_t> d_lnid;        /* [8][Epad] */
     hq_dbuf<double> d_c1, d_c2, d_beta;
-    bool etable_damped = false;     /* some c3 or c4 of the caller's eTable is not 0 (scatter variant) */
+    bool etable_damped = false;     /* some c3 or c4 of the caller's eTable is not 0 */
     hq_atten_dev att;
+    /* patch variant, for hq_attenuation_set_split (which gets no mesh): the element table in device numbering and the caller's
+     * element order, c1 / c2 and n_t[n][0], kept on the HOST (48 B per element + 8 B per node; nothing on the device) */
+    std::vector<int32_t> h_lnid;
+    std::vector<double> h_c1, h_c2, h_mass;
+    hipStream_t astream = nullptr;  /* the correction chain's head beside the step (from the first hq_attenuation_set_split on) */
+    hipEvent_t ev_att_fork = nullptr, ev_att_done = nullptr;
     /* node data */
     double* d_nt = nullptr;         /* [N][7]; behind bricks only the rows of the nodes nt_first .. N - 1 exist (d_nt_rows), */
     hq_dbuf<double> d_nt_rows;      /* d_nt = d_nt_rows - 7 nt_first: no kernel reads a brick node's 7-double row */
@@ -744,6 +761,7 @@ static int hq_build_schedule(hq_ctx* c, const hq_schedule* in, hq_dev_schedule* 
 static bool hq_ipc_ready(const hq_ctx* c);
 /* a transport that is in place (an IPC arena that was exported but never connected is none: bench.py falls back from it) */
 static bool hq_has_transport(const hq_ctx* c) { return c->comm || c->group || c->host_xchg || hq_ipc_ready(c); }
+static int hq_refuse_split(const hq_ctx* c, const char* what);
 
 static hq_dev_schedule* hq_peer_schedule(hq_ctx* peer, hq_ctx* me, hq_dev_schedule* mine)
 {
@@ -983,6 +1001,10 @@ static hipError_t hq_quiesce(hq_ctx* c)
     }
     if (c->bstream) {
         hipError_t e2 = hipStreamSynchronize(c->bstream);
+        if (e == hipSuccess) e = e2;
+    }
+    if (c->astream) {
+        hipError_t e2 = hipStreamSynchronize(c->astream);
         if (e == hipSuccess) e = e2;
     }
     return e;
@@ -1237,6 +1259,56 @@ static bool hq_use_brick_stream(hq_ctx* c)
 
 #include "hq_outputs.h"
 
+/*
+ * A split context's step (hq_atten_split.h).  Head: the delta advance and the correction force read u(t) and u(t - dt)
+ * only, so they fork onto the attenuation stream behind everything the compute stream has seen so far -- the last step's
+ * apply kernels, which read dF and wrote u(t) -- and run beside this step's patches and bricks.
+ */
+static int hq_atten_split_head(hq_ctx* c)
+{
+    const hq_atten_dev& A = c->att;
+#ifdef HQ_ATTEN_SPLIT_INLINE        /* profiles/tools/atten_split_step.py: the chain ON the compute stream, to price the overlap */
+    hipStream_t as = c->stream;
+#else
+    hipStream_t as = c->astream;
+    HQ_HIP(hipEventRecord(c->ev_att_fork, c->stream));
+    HQ_HIP(hipStreamWaitEvent(as, c->ev_att_fork, 0));
+#endif
+    hq_k_atten_advance_delta<<<hq_blocks(A.nslots, 256), 256, 0, as>>>(
+        A.nslots, A.d_slot_node, A.d_slot_class, A.d_ktab, c->d_u[c->now], c->d_u[c->prev], A.d_mv, A.d_w);
+    hq_k_atten_corner_force<<<hq_blocks(c->E, 256), 256, 0, as>>>(c->E, c->Epad, A.nslots, A.d_eslot, A.d_c1, A.d_c2, A.d_w, A.d_ef);
+    hq_k_atten_node_sum<<<hq_blocks(c->N, 256), 256, 0, as>>>(c->N, c->Epad, A.d_nptr, A.d_nent, A.d_ef, A.d_dF);
+#ifndef HQ_ATTEN_SPLIT_INLINE
+    HQ_HIP(hipEventRecord(c->ev_att_done, as));
+#endif
+    return HQ_OK;
+}
+
+/*
+ * Tail: behind every step kernel of this step -- the compute stream's own, and the bricks' where they run on their stream --
+ * and behind the head above: dF's hanging nodes to their anchors, un += dF / n_t[0], the hanging nodes of un assigned again.
+ * un is the buffer this step's head-of-step outputs read as u(t - 2 dt): the step kernels that wrote it waited for them
+ * (hq_outputs_enqueue), and these launches lie behind those kernels.
+ */
+static int hq_atten_split_tail(hq_ctx* c, hq_real* un)
+{
+    const hq_atten_dev& A = c->att;
+    if (c->bstream) HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_bricks, 0));
+#ifndef HQ_ATTEN_SPLIT_INLINE
+    HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_att_done, 0));
+#endif
+    if (A.nSD)
+        hq_k_distribute<<<hq_blocks(A.nSD * 3, 256), 256, 0, c->stream>>>(A.nSD, A.d_sd_dst, A.d_sd_ptr, A.d_sd_src, A.d_sd_deps, A.d_dF);
+    const int64_t n3 = 3 * (int64_t)c->N;
+    hq_k_atten_apply<<<hq_blocks(n3, 256), 256, 0, c->stream>>>(n3, A.d_mass, A.d_dF, un);
+    if (c->ldnnum)
+        hq_k_adjust_assign<<<hq_blocks(c->ldnnum * 3, 256), 256, 0, c->stream>>>(c->ldnnum, c->d_dn_id, c->d_dn_ptr, c->d_dn_anchor, un);
+    /* the next step's bricks, on their own stream, read and overwrite what these launches touch: the event they wait for
+     * must lie behind them (as behind the assignment of phase 6) */
+    if (c->bstream) HQ_HIP(hipEventRecord(c->ev_patches, c->stream));
+    return HQ_OK;
+}
+
 static int hq_phase(hq_ctx* c, int ph)
 {
     const bool patch = (c->variant == HQ_VARIANT_PATCH);
@@ -1265,6 +1337,7 @@ static int hq_phase(hq_ctx* c, int ph)
                 if (c->ev_shared) HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_shared, 0));
                 HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_patches, 0));
             }
+            if (c->att.split) HQ_TRY(hq_atten_split_head(c));
             HQ_TRY(hq_outputs_enqueue(c, bs));     /* solver_write_checkpoint / _output_wavefield / _planes / _stations, :4277-4280 */
             auto launch_bricks = [&]() {
                 if (c->bricks.nunits > 0)
@@ -1426,6 +1499,7 @@ static int hq_phase(hq_ctx* c, int ph)
     case 8:
         HQ_TRY(hq_xchg_recv(c, &c->dn, unew, false, false));
         if (patch) {
+            if (c->att.split) HQ_TRY(hq_atten_split_tail(c, unew));
             if (c->overlap) HQ_HIP(hipEventRecord(c->ev_shared, c->cstream));
             if (hq_has_transport(c)) hq_clock(c, hq_ctx::HQ_CLK_CHAIN1, c->overlap ? c->cstream : c->stream);
             int n = c->now, p = c->prev, sp = c->spare;
@@ -1802,6 +1876,17 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
         rc = hq_patch_build(opts, &c->plan, c->E, c->N, d->lnid, d->node_xyz, prep.c1.data(), prep.c2.data(), prep.beta.data(), ntab,
                             prep.dn, prep.seed0.data(), &c->bytes, c->stream, BH.nb);
         lap("patch plan");
+        if (rc == HQ_OK && sizeof(hq_real) == sizeof(double)) {   /* what hq_attenuation_set_split will need of the mesh */
+            for (int64_t e = 0; e < c->E && !c->etable_damped; e++)
+                c->etable_damped = d->eTable[4 * e + 2] != 0.0 || d->eTable[4 * e + 3] != 0.0;
+            if (!prep.p_lnid.empty()) c->h_lnid = std::move(prep.p_lnid);
+            else c->h_lnid.assign(d->lnid, d->lnid + 8 * (size_t)c->E);
+            prep.desc.lnid = c->h_lnid.data();            /* (d: the description reads the context's copy from here on) */
+            c->h_c1 = std::move(prep.c1); c->h_c2 = std::move(prep.c2);
+            c->h_mass.resize((size_t)c->N);
+#pragma omp parallel for schedule(static)
+            for (int64_t n = 0; n < c->N; n++) c->h_mass[(size_t)n] = ntab[7 * n];
+        }
         if (rc == HQ_OK && BH.nb > 0) rc = hq_brick_upload(&c->bricks, BH, &c->bytes, c->stream);
         c->bricks.mat = { 0.0, 0.0, d->deltaT, d->mat_bbase, d->mat_threshold_damping, d->mat_threshold_vpvs };
         lap("brick upload");
@@ -1847,6 +1932,9 @@ extern "C" int hq_destroy(hq_ctx* c)
     if (c->ev_output) hipEventDestroy(c->ev_output);
     if (c->cstream) { hipStreamSynchronize(c->cstream); hipStreamDestroy(c->cstream); }
     if (c->bstream) { hipStreamSynchronize(c->bstream); hipStreamDestroy(c->bstream); }
+    if (c->astream) { hipStreamSynchronize(c->astream); hipStreamDestroy(c->astream); }
+    if (c->ev_att_fork) hipEventDestroy(c->ev_att_fork);
+    if (c->ev_att_done) hipEventDestroy(c->ev_att_done);
     for (auto& sl : c->clock) for (hipEvent_t e : sl.e) if (e) hipEventDestroy(e);
     if (c->ev_patches) hipEventDestroy(c->ev_patches);
     if (c->ev_bricks) hipEventDestroy(c->ev_bricks);
@@ -1970,6 +2058,7 @@ extern "C" int hq_comm_unique_id(void* id128)
 extern "C" int hq_comm_init(hq_ctx* c, const void* id128)
 {
     if (!c || !id128) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    HQ_TRY(hq_refuse_split(c, "hq_comm_init"));
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
     HQ_TRY(hq_rccl_load());
     HQ_HIP(hipSetDevice(c->device));
@@ -2006,6 +2095,7 @@ extern "C" int hq_comm_selftest(hq_ctx* c, int32_t count)
 extern "C" int hq_comm_init_host(hq_ctx* c, hq_host_exchange_fn fn, void* user)
 {
     if (!c || !fn) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    HQ_TRY(hq_refuse_split(c, "hq_comm_init_host"));
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
     c->host_xchg = fn;
     c->host_user = user;
@@ -2234,6 +2324,7 @@ static int hq_ipc_connect(hq_ctx* c, const char* blobs)
 extern "C" int hq_comm_init_ipc(hq_ctx* c, const void* blobs)
 {
     if (!c || !blobs) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    HQ_TRY(hq_refuse_split(c, "hq_comm_init_ipc"));
     if (!c->ipc) return hq_fail(HQ_ERR_STATE, "hq_comm_init_ipc needs the blobs of hq_comm_ipc_export (this rank's among them)%s", "");
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
     HQ_HIP(hipSetDevice(c->device));
@@ -2250,6 +2341,7 @@ extern "C" int hq_comm_init_ipc_n(hq_ctx* c, const void* blobs, int32_t nblobs)
 extern "C" int hq_comm_init_loopback(hq_ctx* c)
 {
     if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    HQ_TRY(hq_refuse_split(c, "hq_comm_init_loopback"));
     HQ_TRY(hq_ipc_prepare(c));
     if (hq_has_transport(c)) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
     return hq_ipc_connect(c, nullptr);
@@ -2261,6 +2353,7 @@ extern "C" int hq_group_link(hq_ctx** ctxs, int32_t n)
     for (int32_t i = 0; i < n; i++) {
         if (!ctxs[i] || ctxs[i]->rank != i || ctxs[i]->nranks != n)
             return hq_fail(HQ_ERR_ARG, "group member %s must be the context of rank i of n", "i");
+        HQ_TRY(hq_refuse_split(ctxs[i], "hq_group_link"));
         if (hq_has_transport(ctxs[i])) return hq_fail(HQ_ERR_STATE, "context already has a transport%s", "");
         for (hq_dev_schedule* sc : { &ctxs[i]->an, &ctxs[i]->dn })
             for (auto* lst : { &sc->c, &sc->s })
@@ -2538,7 +2631,7 @@ extern "C" int hq_run_timed(hq_ctx* c, int32_t nsteps, double* total_ms, double*
 
 extern "C" const char* hq_dominant_kernel(hq_ctx* c)
 {
-    if (c && c->att.on) return "hq_k_element_bkt";
+    if (c && c->att.on && !c->att.split) return "hq_k_element_bkt";
     if (!c || c->variant != HQ_VARIANT_PATCH) return "hq_k_element_scatter";
     if (2 * c->bricks.nb > (int64_t)c->N) return "hq_k_brick";
     if (2 * c->plan.nstencil > c->plan.npatches) return "hq_k_patch_stencil";
@@ -2673,10 +2766,136 @@ extern "C" int hq_attenuation_set(hq_ctx* c, const hq_attenuation_desc* a)
     const int64_t added = (int64_t)(A.d_eslot.bytes() + A.d_slot_node.bytes() + A.d_slot_class.bytes() + A.d_ktab.bytes() +
                                     A.d_mv.bytes() + A.d_w.bytes());
     if (added != hq_atten_bytes(P.nslots, P.Epad, P.nclasses)) return hq_fail(HQ_ERR_STATE, "attenuation: the device bytes are not the header's formula%s", "");
-    A.nclasses = P.nclasses; A.nslots = P.nslots;
+    A.nclasses = P.nclasses; A.nslots = P.nslots; A.bytes = added;
     A.h_eslot = std::move(P.eslot); A.h_slot_node = std::move(P.slot_node);
     A.on = true;
     hq_attenuation_clear(c);
+    c->att = std::move(A);
+    c->bytes += added;
+    return HQ_OK;
+}
+
+/* the class doubles of a plan, refused where one is not finite */
+static int hq_atten_ktab(const hq_atten_plan& P, double freq, double dt, std::vector<double>* ktab)
+{
+    ktab->assign((size_t)P.nclasses * HQ_ATTEN_NCOEF, 0.0);
+    for (int32_t k = 0; k < P.nclasses; k++) {
+        hq_atten_class_coef(P.rows.data() + HQ_ATTEN_NROW * (size_t)k, freq, dt, ktab->data() + HQ_ATTEN_NCOEF * (size_t)k);
+        for (int j = 0; j < HQ_ATTEN_NCOEF; j++)
+            if (!std::isfinite((*ktab)[HQ_ATTEN_NCOEF * (size_t)k + j])) return hq_fail(HQ_ERR_ARG, "attenuation: a class coefficient is not finite%s", "");
+    }
+    return HQ_OK;
+}
+
+/* a split context steps alone: no partition, no transport (include/hq_solver.h) */
+static int hq_refuse_split(const hq_ctx* c, const char* what)
+{
+    if (c && c->att.split)
+        return hq_fail(HQ_ERR_STATE, "%s: the context carries split attenuation (hq_attenuation_set_split), which steps one context alone", what);
+    return HQ_OK;
+}
+
+extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
+{
+    if (!c || !a || !a->coef) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (sizeof(hq_real) != sizeof(double))
+        return hq_fail(HQ_ERR_STATE, "attenuation: not in the float library (the memory variables are double state)%s", "");
+    if (c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "split attenuation runs beside the patch variant's step: on a scatter context call hq_attenuation_set%s", "");
+    if (c->nranks > 1 || hq_has_transport(c) || c->group)
+        return hq_fail(HQ_ERR_STATE, "split attenuation: partitions and transports are out of scope (one context, nranks = 1)%s", "");
+    if (!(a->freq > 0.0) || !std::isfinite(a->freq)) return hq_fail(HQ_ERR_ARG, "attenuation: freq must be finite and > 0%s", "");
+    if (c->etable_damped)
+        return hq_fail(HQ_ERR_ARG, "attenuation: the eTable has c3 or c4 != 0; under BKT compute_setab yields a = b = 0 (psolve.c:5869)%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const int64_t E = c->E, N = c->N;
+    hq_atten_plan P;
+    HQ_TRY(hq_atten_plan_build(E, N, c->h_lnid.data(), 0, a->coef, &P));
+    std::vector<double> ktab;
+    HQ_TRY(hq_atten_ktab(P, a->freq, c->dt, &ktab));
+    /* the hanging-node table in device numbering: the context's own arrays */
+    std::vector<int32_t> dn_id((size_t)c->ldnnum), dn_ptr((size_t)c->ldnnum + 1, 0), dn_anchor;
+    if (c->ldnnum) {
+        HQ_TRY(hq_copy_wait(dn_id.data(), c->d_dn_id, sizeof(int32_t) * dn_id.size(), hipMemcpyDeviceToHost, c->stream));
+        HQ_TRY(hq_copy_wait(dn_ptr.data(), c->d_dn_ptr, sizeof(int32_t) * dn_ptr.size(), hipMemcpyDeviceToHost, c->stream));
+        dn_anchor.resize((size_t)dn_ptr[(size_t)c->ldnnum]);
+        HQ_TRY(hq_copy_wait(dn_anchor.data(), c->d_dn_anchor, sizeof(int32_t) * dn_anchor.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    hq_split_plan S;
+    HQ_TRY(hq_split_plan_build(E, N, P.Epad, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), &S));
+    if (hq_atten_plan_faults(E, c->h_lnid.data(), P) != 0 ||
+        hq_split_plan_faults(E, N, P.Epad, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), S.epos.data(),
+                             S.nptr.data(), S.nent.data(), S.sd.data(), (int64_t)(S.sd.size() / 3)) != 0)
+        return hq_fail(HQ_ERR_STATE, "split attenuation: the plan does not pass its own check%s", "");
+    if (!c->astream) {
+        hipStream_t st = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e0, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess) {
+            if (st) hipStreamDestroy(st);
+            if (e0) hipEventDestroy(e0);
+            return hq_fail(HQ_ERR_DEVICE, "split attenuation: no stream or event%s", "");
+        }
+        c->astream = st; c->ev_att_fork = e0; c->ev_att_done = e1;
+    }
+    /* everything is built beside the context's own and moved in at the end: a refusal leaves the context as it was */
+    hq_atten_dev A;
+    int rc;
+    std::vector<double> cc1((size_t)E), cc2((size_t)E);                 /* the device's element order (hq_split_plan.epos) */
+    std::vector<int32_t> eslot_dev(P.eslot.size(), 0);
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < E; e++) {
+        const size_t at = (size_t)S.epos[(size_t)e];
+        cc1[at] = c->h_c1[(size_t)e]; cc2[at] = c->h_c2[(size_t)e];
+        for (int i = 0; i < 8; i++) eslot_dev[(size_t)(i * P.Epad) + at] = P.eslot[(size_t)(i * P.Epad + e)];
+    }
+    if ((rc = A.d_eslot.put(nullptr, eslot_dev, c->stream)) != HQ_OK || (rc = A.d_slot_node.put(nullptr, P.slot_node, c->stream)) != HQ_OK ||
+        (rc = A.d_slot_class.put(nullptr, P.slot_class, c->stream)) != HQ_OK || (rc = A.d_ktab.put(nullptr, ktab, c->stream)) != HQ_OK ||
+        (rc = A.d_mv.alloc(nullptr, (size_t)HQ_ATTEN_NSTATE * P.nslots)) != HQ_OK || (rc = A.d_mv.fill(0, c->stream)) != HQ_OK ||
+        (rc = A.d_w.alloc(nullptr, (size_t)HQ_ATTEN_NW * P.nslots)) != HQ_OK || (rc = A.d_w.fill(0, c->stream)) != HQ_OK ||
+        (rc = A.d_ef.alloc(nullptr, (size_t)(24 * P.Epad))) != HQ_OK || (rc = A.d_ef.fill(0, c->stream)) != HQ_OK ||
+        (rc = A.d_dF.alloc(nullptr, 3 * (size_t)N)) != HQ_OK || (rc = A.d_dF.fill(0, c->stream)) != HQ_OK ||
+        (rc = A.d_mass.put(nullptr, c->h_mass, c->stream)) != HQ_OK ||
+        (rc = A.d_c1.put(nullptr, cc1, c->stream)) != HQ_OK || (rc = A.d_c2.put(nullptr, cc2, c->stream)) != HQ_OK ||
+        (rc = A.d_nptr.put(nullptr, S.nptr, c->stream)) != HQ_OK || (rc = A.d_nent.put(nullptr, S.nent, c->stream)) != HQ_OK)
+        return rc;
+    int64_t added = (int64_t)(A.d_eslot.bytes() + A.d_slot_node.bytes() + A.d_slot_class.bytes() + A.d_ktab.bytes() + A.d_mv.bytes() +
+                              A.d_w.bytes() + A.d_ef.bytes() + A.d_dF.bytes() + A.d_mass.bytes() + A.d_c1.bytes() + A.d_c2.bytes() +
+                              A.d_nptr.bytes() + A.d_nent.bytes());
+    if (!S.sd.empty()) {
+        /* hq_build_distribution's grouping by anchor, into A's own tables */
+        const size_t n = S.sd.size() / 3;
+        std::vector<int32_t> order(n);
+        for (size_t i = 0; i < n; i++) order[i] = (int32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return S.sd[3 * (size_t)x + 1] < S.sd[3 * (size_t)y + 1]; });
+        std::vector<int32_t> dst, ptr(1, 0), src, deps;
+        for (size_t k = 0; k < n; k++) {
+            const size_t i = (size_t)order[k];
+            if (dst.empty() || dst.back() != S.sd[3 * i + 1]) { if (!dst.empty()) ptr.push_back((int32_t)src.size()); dst.push_back(S.sd[3 * i + 1]); }
+            src.push_back(S.sd[3 * i]); deps.push_back(S.sd[3 * i + 2]);
+        }
+        ptr.push_back((int32_t)src.size());
+        if ((rc = A.d_sd_dst.put(nullptr, dst, c->stream)) != HQ_OK || (rc = A.d_sd_ptr.put(nullptr, ptr, c->stream)) != HQ_OK ||
+            (rc = A.d_sd_src.put(nullptr, src, c->stream)) != HQ_OK || (rc = A.d_sd_deps.put(nullptr, deps, c->stream)) != HQ_OK)
+            return rc;
+        A.nSD = (int32_t)dst.size();
+        added += (int64_t)(A.d_sd_dst.bytes() + A.d_sd_ptr.bytes() + A.d_sd_src.bytes() + A.d_sd_deps.bytes());
+    }
+    A.nanchors = S.nanchors; A.npairs = S.npairs;
+    if (added != hq_atten_bytes(P.nslots, P.Epad, P.nclasses) + hq_split_bytes(E, P.Epad, N, S.nanchors, S.npairs))
+        return hq_fail(HQ_ERR_STATE, "attenuation: the device bytes are not the header's formula%s", "");
+    A.nclasses = P.nclasses; A.nslots = P.nslots; A.bytes = added;
+    A.h_eslot = std::move(P.eslot);
+    A.h_slot_node = std::move(P.slot_node);
+    if (!c->perm.empty()) {                          /* fetch / load name nodes as the caller numbers them */
+        std::vector<int32_t> inv((size_t)N);
+        for (int64_t n = 0; n < N; n++) inv[(size_t)c->perm[(size_t)n]] = (int32_t)n;
+        for (int32_t& n : A.h_slot_node) n = inv[(size_t)n];
+    }
+    A.on = true; A.split = true;
+    hq_attenuation_clear(c);
+    c->Epad = (int32_t)P.Epad;                       /* (a patch context has no element SoA of its own: the stride of eslot and ef) */
     c->att = std::move(A);
     c->bytes += added;
     return HQ_OK;
@@ -2688,7 +2907,7 @@ extern "C" int hq_attenuation_clear(hq_ctx* c)
     if (!c->att.on) return HQ_OK;
     HQ_HIP(hipSetDevice(c->device));
     HQ_HIP(hq_quiesce(c));
-    c->bytes -= hq_atten_bytes(c->att.nslots, c->Epad, c->att.nclasses);
+    c->bytes -= c->att.bytes;
     c->att = hq_atten_dev();
     return HQ_OK;
 }
@@ -2697,8 +2916,8 @@ extern "C" int hq_attenuation_info(hq_ctx* c, int64_t out[4])
 {
     if (!c || !out) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
     out[0] = c->att.nclasses; out[1] = c->att.nslots;
-    out[2] = c->att.on ? hq_atten_bytes(c->att.nslots, c->Epad, c->att.nclasses) : 0;
-    out[3] = 0;
+    out[2] = c->att.on ? c->att.bytes : 0;
+    out[3] = c->att.split ? 1 : 0;
     return HQ_OK;
 }
 
@@ -2773,6 +2992,65 @@ extern "C" int hq_attenuation_plan_check(const hq_desc* d, const float* coef, in
     for (int32_t n : P.slot_node) has[(size_t)n] = 1;
     for (int32_t k = 0; k < d->ldnnum; k++) bad += !has[(size_t)d->dn_ldnid[k]];      /* a hanging node is a node like any other */
     report[0] = P.nclasses; report[1] = P.nslots; report[2] = hq_atten_bytes(P.nslots, P.Epad, P.nclasses); report[3] = bad;
+    return HQ_OK;
+}
+
+/* the description as hq_create would number it, and the split tables of it */
+static int hq_split_plan_of(const hq_desc* d, hq_prep* prep, int64_t* Epad, hq_split_plan* S)
+{
+    hq_options opts;
+    hq_options_resolve(&opts, nullptr);
+    HQ_TRY(hq_prepare(d, opts, d->eTable && d->nTable && d->node_xyz ? HQ_PREP_BRICKS : 0, prep));
+    const hq_desc& q = prep->desc;
+    *Epad = ((int64_t)q.lenum + 63) & ~(int64_t)63;
+    return hq_split_plan_build(q.lenum, q.nharbored, *Epad, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, S);
+}
+
+extern "C" int hq_attenuation_split_plan_check(const hq_desc* d, const float* coef, int64_t report[4])
+{
+    if (!d || !coef || !report) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (d->nranks > 1) return hq_fail(HQ_ERR_STATE, "split attenuation: partitions and transports are out of scope (one context, nranks = 1)%s", "");
+    hq_prep prep;
+    hq_split_plan S;
+    int64_t Epad = 0;
+    HQ_TRY(hq_split_plan_of(d, &prep, &Epad, &S));
+    const hq_desc& q = prep.desc;
+    hq_atten_plan P;
+    HQ_TRY(hq_atten_plan_build(q.lenum, q.nharbored, q.lnid, 0, coef, &P));
+    int64_t bad = hq_atten_plan_faults(q.lenum, q.lnid, P);
+    bad += hq_split_plan_faults(q.lenum, q.nharbored, Epad, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, S.epos.data(), S.nptr.data(),
+                                S.nent.data(), S.sd.data(), (int64_t)(S.sd.size() / 3));
+    report[0] = P.nclasses; report[1] = P.nslots;
+    report[2] = hq_atten_bytes(P.nslots, P.Epad, P.nclasses) + hq_split_bytes(q.lenum, Epad, q.nharbored, S.nanchors, S.npairs);
+    report[3] = bad;
+    return HQ_OK;
+}
+
+extern "C" int hq_attenuation_split_plan_tables(const hq_desc* d, int32_t* epos, int32_t* nptr, int32_t* nent, int32_t* sd, int64_t counts[3])
+{
+    if (!d || !counts) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_prep prep;
+    hq_split_plan S;
+    int64_t Epad = 0;
+    HQ_TRY(hq_split_plan_of(d, &prep, &Epad, &S));
+    counts[0] = (int64_t)S.nptr.size(); counts[1] = (int64_t)S.nent.size(); counts[2] = (int64_t)(S.sd.size() / 3);
+    if (epos) memcpy(epos, S.epos.data(), sizeof(int32_t) * S.epos.size());
+    if (nptr) memcpy(nptr, S.nptr.data(), sizeof(int32_t) * S.nptr.size());
+    if (nent) memcpy(nent, S.nent.data(), sizeof(int32_t) * S.nent.size());
+    if (sd && !S.sd.empty()) memcpy(sd, S.sd.data(), sizeof(int32_t) * S.sd.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_attenuation_split_table_faults(const hq_desc* d, const int32_t* epos, const int32_t* nptr, const int32_t* nent, const int32_t* sd,
+                                                 int64_t nsd, int64_t* faults)
+{
+    if (!d || !epos || !nptr || !nent || !faults || nsd < 0 || (nsd && !sd)) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_prep prep;
+    hq_split_plan S;
+    int64_t Epad = 0;
+    HQ_TRY(hq_split_plan_of(d, &prep, &Epad, &S));
+    const hq_desc& q = prep.desc;
+    *faults = hq_split_plan_faults(q.lenum, q.nharbored, Epad, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, epos, nptr, nent, sd, nsd);
     return HQ_OK;
 }
 

@@ -1527,6 +1527,24 @@ int hqh_atten_advance(int32_t nslots, const int32_t* slot_node, const int32_t* s
     return HQ_OK;
 }
 
+int hqh_atten_advance_delta(int32_t nslots, const int32_t* slot_node, const int32_t* slot_class, int32_t nclasses, const double* k,
+                      int32_t nnodes, const double* u1, const double* u2, double* mv, double* w)
+{
+    if (nslots < 0 || nclasses < 0 || nnodes < 0) return HQ_ERR_ARG;
+    if (nslots == 0) return HQ_OK;
+    if (!slot_node || !slot_class || !k || !u1 || !u2 || !mv || !w) return HQ_ERR_ARG;
+    for (int32_t s = 0; s < nslots; s++)
+        if (slot_node[s] < 0 || slot_node[s] >= nnodes || slot_class[s] < 0 || slot_class[s] >= nclasses) return HQ_ERR_ARG;
+    for (int32_t s = 0; s < nslots; s++) {
+        const int64_t row = 3 * (int64_t)slot_node[s];
+        const double* kc = k + (int64_t)HQ_ATTEN_NCOEF * slot_class[s];
+        for (int d = 0; d < 3; d++)
+            hq_atten_advance_delta(u1[row + d], u2[row + d], kc, mv + (int64_t)d * nslots + s, 3 * (int64_t)nslots,
+                             w + (int64_t)d * nslots + s, w + (int64_t)(3 + d) * nslots + s);
+    }
+    return HQ_OK;
+}
+
 int hqh_cum_fold(int32_t npoints, int32_t quantities, int32_t nsamples, const int32_t* steps, const double* samples,
                  const double* threshold, double* sums, int32_t* span)
 {

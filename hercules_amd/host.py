@@ -19,7 +19,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
            "hqh_gradient_weights", "hqh_station_gradients", "hqh_station_moduli", "hqh_deform_fold",
-           "hqh_station_kinematics", "hqh_peak_fold", "hqh_atten_class_coef", "hqh_atten_advance", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
+           "hqh_station_kinematics", "hqh_peak_fold", "hqh_atten_class_coef", "hqh_atten_advance", "hqh_atten_advance_delta", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
            "hqh_cvm_open", "hqh_cvm_close", "hqh_cvm_info", "hqh_cvm_query", "hqh_cvm_grid"]
 
@@ -885,10 +885,11 @@ def atten_class_coef(rows, freq, dt):
     return k, rmax.value
 
 
-def atten_advance(slot_node, slot_class, k, u1, u2, mv, w=None):
+def atten_advance(slot_node, slot_class, k, u1, u2, mv, w=None, delta=False):
     """hqh_atten_advance: one step of the memory variables mv [12, nslots] (in place; float64, C-contiguous) and the damping
     vectors w [6, nslots] of a slot plan (slot_node, slot_class [nslots]) with the class doubles k [nclasses, 18] and the
-    fields u1, u2 [N, 3].  Returns (mv, w)."""
+    fields u1, u2 [N, 3].  delta: hqh_atten_advance_delta -- w then holds ds, dk, the damping vectors without their + u1.
+    Returns (mv, w)."""
     slot_node = np.ascontiguousarray(slot_node, np.int32)
     slot_class = np.ascontiguousarray(slot_class, np.int32)
     k = np.ascontiguousarray(k, np.float64).reshape(-1, ATTEN_NCOEF)
@@ -900,8 +901,9 @@ def atten_advance(slot_node, slot_class, k, u1, u2, mv, w=None):
             or w.shape != (ATTEN_NW, ns) or not w.flags.c_contiguous or u1.shape != u2.shape or len(slot_class) != ns):
         raise capi.HqError("atten_advance: mv / w are not the state of %d slots" % ns)
     ptr = lambda a: ctypes.c_void_p(a.ctypes.data)
-    capi._check(load_library().hqh_atten_advance(ctypes.c_int32(ns), ptr(slot_node), ptr(slot_class), ctypes.c_int32(len(k)), ptr(k),
-                                                 ctypes.c_int32(len(u1)), ptr(u1), ptr(u2), ptr(mv), ptr(w)))
+    fn = load_library().hqh_atten_advance_delta if delta else load_library().hqh_atten_advance
+    capi._check(fn(ctypes.c_int32(ns), ptr(slot_node), ptr(slot_class), ctypes.c_int32(len(k)), ptr(k),
+                   ctypes.c_int32(len(u1)), ptr(u1), ptr(u2), ptr(mv), ptr(w)))
     return mv, w
 
 

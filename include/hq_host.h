@@ -326,6 +326,10 @@ HQ_API int hqh_peak_fold(int32_t npoints, int32_t quantities, int32_t nsamples, 
 HQ_API int hqh_atten_class_coef(int32_t nclasses, const float* rows, double freq, double dt, double* k, double* rmax);
 HQ_API int hqh_atten_advance(int32_t nslots, const int32_t* slot_node, const int32_t* slot_class, int32_t nclasses,
                              const double* k, int32_t nnodes, const double* u1, const double* u2, double* mv, double* w);
+/* hqh_atten_advance_delta: the same step in the delta form of hq_attenuation_set_split (hq_atten_advance_delta): mv comes out
+ * bit for bit as above, w [6][nslots] takes ds x y z, dk x y z = the damping vectors without their final + u1. */
+HQ_API int hqh_atten_advance_delta(int32_t nslots, const int32_t* slot_node, const int32_t* slot_class, int32_t nclasses,
+                                   const double* k, int32_t nnodes, const double* u1, const double* u2, double* mv, double* w);
 /* The cumulative-intensity fold on the host (csrc/hq_cumul.h, the text hq_k_cum compiles): recorder samples added into the
  * state hq_cum_fetch delivers -- the route of a caller without device trackers.  samples, steps and `quantities` as
  * hqh_peak_fold's; threshold [nq], per quantity of the mask in mask order, finite and >= 0, squared once here.  sums

@@ -784,7 +784,8 @@ HQ_API int hq_deform_clear(hq_ctx* ctx);
  * the context left as it was: a context of the patch variant (HQ_ERR_STATE: create with HQ_VARIANT_SCATTER), the float
  * library (HQ_ERR_STATE), an eTable with any c3 or c4 != 0 (HQ_ERR_ARG: under BKT compute_setab yields a = b = 0,
  * psolve.c:5869), freq <= 0 or not finite, a coefficient that is not finite (HQ_ERR_ARG).
- * hq_attenuation_info: out = {classes, slots, device bytes added, 0}; all 0 on a context without attenuation.
+ * hq_attenuation_info: out = {classes, slots, device bytes added, 0 (1: hq_attenuation_set_split)}; all 0 on a context without
+ * attenuation.
  * hq_attenuation_fetch / _load speak the reference's layout: four arrays [lenum * 8][3] (cindex = eindex * 8 + i) for
  * conv_shear_1, conv_shear_2, conv_kappa_1, conv_kappa_2.  fetch leaves out an array passed as NULL; load needs all four
  * and refuses (HQ_ERR_ARG, the text names the node) an input in which two corners of one slot differ, or a value that is
@@ -796,7 +797,8 @@ HQ_API int hq_deform_clear(hq_ctx* ctx);
  * slot is not (their node, their class), slots out of node-major order and hanging nodes without a slot.
  * On an attenuated context hq_dominant_kernel names hq_k_element_bkt, and hq_phase_force runs the two kernels (every call
  * advances the memory variables one step, as calc_conv does).
- * Not here: attenuation in the patch and brick kernels, the float library, the Q table and the velocity correction.
+ * Not here: attenuation INSIDE the patch and brick kernels (beside them: hq_attenuation_set_split, below), the float library, the
+ * Q table and the velocity correction.
  */
 typedef struct {
     const float* coef;               /* [lenum][10], order above */
@@ -808,6 +810,50 @@ HQ_API int hq_attenuation_fetch(hq_ctx* ctx, double* shear1, double* shear2, dou
 HQ_API int hq_attenuation_load(hq_ctx* ctx, const double* shear1, const double* shear2, const double* kappa1, const double* kappa2);
 HQ_API int hq_attenuation_clear(hq_ctx* ctx);
 HQ_API int hq_attenuation_plan_check(const hq_desc* desc, const float* coef, int64_t report[4]);
+
+/*
+ * BKT attenuation on a context of the PATCH variant: a correction pass beside the step (csrc/hq_atten_split.h), double library,
+ * one context alone.  Under BKT c3 = c4 = 0 and the patch and brick kernels apply mu K_mu + kappa K_kappa to u1; the BKT force
+ * is that elastic force plus dF = mu K_mu ds + kappa K_kappa dk, with ds, dk the damping vectors without their final + u1
+ * (hq_atten_advance_delta).  The rest of the step is linear in the force, so the attenuated step is the unchanged elastic step,
+ *     (patches, bricks)  ||  hq_k_atten_advance_delta -> hq_k_atten_corner_force -> hq_k_atten_node_sum   (a stream of its own)
+ * followed on the compute stream by
+ *     hq_k_distribute (dF's hanging nodes) -> hq_k_atten_apply (u_new += dF / n_t[0]) -> hq_k_adjust_assign (u_new).
+ * dF is summed per node through a host-built table in element order, without atomics: two runs give identical bits.  The
+ * result differs from the scatter variant's attenuated step by rounding only (two more roundings per node and component).
+ *
+ * hq_attenuation_set_split: desc, state and the rules of hq_attenuation_set; the memory variables are hq_attenuation_set's bit for
+ * bit.  It refuses, the context left as it was: a scatter context (HQ_ERR_STATE: call hq_attenuation_set), the float library
+ * (HQ_ERR_STATE), a context with nranks > 1, a linked group or any transport (HQ_ERR_STATE), an eTable with c3 or c4 != 0, a bad
+ * freq, a coefficient that is not finite (HQ_ERR_ARG).  On a split context hq_comm_init*, hq_group_link refuse (HQ_ERR_STATE).
+ * hq_attenuation_info: out[3] = 1.  _fetch / _load / _clear and hq_upload as on a scatter context (the per-corner layout in the
+ * caller's element order and node numbering).  hq_dominant_kernel keeps naming the step kernel.
+ * Device bytes added, exactly (N = nharbored, E = lenum, Epad = E rounded up to 64; A = distinct anchors, H = (hanging node,
+ * anchor) pairs of the hanging-node table):
+ *     144 nslots + 32 Epad + 8 nslots + 144 nclasses     (as hq_attenuation_set; the damping-vector rows hold ds, dk)
+ *   + 192 Epad            (corner forces, double [3][8][Epad])
+ *   +  48 E               (c1, c2 and the node -> (element, corner) entries)
+ *   +   4 (N + 1) + 32 N  (the table's row pointers; dF [N][3] and the mass row n_t[n][0])
+ *   +   8 A + 4 + 8 H     (dF's distribution tables; nothing where no node hangs)
+ * For this call every context of the patch variant keeps, on the HOST, its element table, c1 / c2 and the mass row: 48 B per
+ * element + 8 B per node.
+ * hq_attenuation_split_plan_check: host only -- report = {classes, slots, the bytes above, faults}; faults add to
+ * hq_attenuation_plan_check's those of the node -> (element, corner) table (every corner exactly once, under its own node, in
+ * the caller's element order; the device's own element order a permutation) and of the hanging-node lists (every (node, anchor) pair once, with the node's number of anchors).
+ * hq_attenuation_split_plan_tables hands out the tables of `desc` in the numbering hq_create gives it (counts = {N + 1, 8 E, H};
+ * epos [E] = the place the device gives the caller's element (the elements sorted by their lowest device node, for locality),
+ * nptr [N + 1], nent [8 E] with entry = corner * Epad + epos[element], per node in the CALLER's element order, sd [H][3] =
+ * {hanging node, anchor, anchors of the node}; a NULL array is left out), and hq_attenuation_split_table_faults counts the
+ * faults of tables given to it: the same check.
+ * Not here: partitions and transports, the float library, folding the correction into the brick and patch kernels, the Q
+ * table and the velocity correction, the reference-link stub.
+ */
+HQ_API int hq_attenuation_set_split(hq_ctx* ctx, const hq_attenuation_desc* desc);
+HQ_API int hq_attenuation_split_plan_check(const hq_desc* desc, const float* coef, int64_t report[4]);
+HQ_API int hq_attenuation_split_plan_tables(const hq_desc* desc, int32_t* epos, int32_t* nptr, int32_t* nent, int32_t* sd,
+                                            int64_t counts[3]);
+HQ_API int hq_attenuation_split_table_faults(const hq_desc* desc, const int32_t* epos, const int32_t* nptr, const int32_t* nent,
+                                             const int32_t* sd, int64_t nsd, int64_t* faults);
 
 /*
  * Single phases, for per-function parity tests against the reference loops
