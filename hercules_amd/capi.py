@@ -29,12 +29,15 @@ EXPORTS = ["hq_device_count", "hq_last_error", "hq_create", "hq_destroy", "hq_ge
            "hq_deform_add", "hq_deform_fetch", "hq_deform_load", "hq_deform_reset", "hq_deform_clear",
            "hq_attenuation_set", "hq_attenuation_info", "hq_attenuation_fetch", "hq_attenuation_load", "hq_attenuation_clear",
            "hq_attenuation_plan_check", "hq_attenuation_set_split", "hq_attenuation_split_plan_check", "hq_attenuation_split_plan_tables",
-           "hq_attenuation_split_table_faults"]
+           "hq_attenuation_split_table_faults",
+           "hq_nonlinear_set", "hq_nonlinear_info", "hq_nonlinear_fetch", "hq_nonlinear_load", "hq_nonlinear_clear", "hq_nonlinear_plan_check",
+           "hq_nonlinear_plan_tables", "hq_nonlinear_table_faults"]
 HQ_SNAP_TM1, HQ_SNAP_TM2, HQ_SNAP_VEL = 1, 2, 4
 HQ_PEAK_DISP, HQ_PEAK_VEL, HQ_PEAK_ACC = 1, 2, 4
 HQ_SPEC_MAX_PERIODS, HQ_SPEC_NVAL = 32, 4
 HQ_DEFORM_STRAIN, HQ_DEFORM_STRAIN_RATE, HQ_DEFORM_STRESS, HQ_DEFORM_ROTATION, HQ_DEFORM_ROTATION_RATE = 1, 2, 4, 8, 16
 HQ_DEFORM_ALL = 31
+HQ_NL_VONMISES, HQ_NL_DRUCKERPRAGER = 1, 2
 
 
 class HqError(RuntimeError):
@@ -73,6 +76,21 @@ class _Desc(ctypes.Structure):
 
 class _AttenuationDesc(ctypes.Structure):
     _fields_ = [("coef", ctypes.c_void_p), ("freq", ctypes.c_double)]
+
+
+class _NonlinearDesc(ctypes.Structure):
+    _fields_ = [("model", ctypes.c_int32), ("nelems", ctypes.c_int32), ("elems", ctypes.c_void_p), ("cons", ctypes.c_void_p)]
+
+
+def _nonlinear_desc(model, elems, cons, who):
+    """hq_nonlinear_desc of elems [n] and cons [n, 6]; the arrays are kept alive on the returned object."""
+    elems = np.ascontiguousarray(elems, np.int32).reshape(-1)
+    cons = np.ascontiguousarray(cons, np.float64).reshape(-1, 6)
+    if len(cons) != len(elems):
+        raise HqError("%s: cons %r is not [%d, 6]" % (who, cons.shape, len(elems)))
+    d = _NonlinearDesc(int(model), len(elems), _ptr(elems) if len(elems) else None, _ptr(cons) if len(elems) else None)
+    d._keep = (elems, cons)
+    return d
 
 
 class _RecorderDesc(ctypes.Structure):
@@ -768,6 +786,40 @@ class Solver:
         """hq_attenuation_clear: back to the Rayleigh step of the context's eTable."""
         _check(self._lib.hq_attenuation_clear(self._h), self._lib)
 
+    def set_nonlinear(self, model, elems, cons):
+        """hq_nonlinear_set: rate-independent plasticity (HQ_NL_VONMISES, HQ_NL_DRUCKERPRAGER) at the quadrature points of the
+        elements `elems` [n] (the caller's numbering, strictly ascending) with cons [n, 6] = h, mu, lambda, alpha, k, hardening
+        modulus (host.nonlinear_constants): a correction pass beside the step of a context of the patch variant, double
+        library.  The plastic strains start at 0."""
+        d = _nonlinear_desc(model, elems, cons, "set_nonlinear")
+        _check(self._lib.hq_nonlinear_set(self._h, ctypes.byref(d)), self._lib)
+
+    def nonlinear_info(self):
+        """hq_nonlinear_info -> dict(elements, touched_nodes, device_bytes); all 0 without."""
+        out = (ctypes.c_int64 * 4)()
+        _check(self._lib.hq_nonlinear_info(self._h, out), self._lib)
+        return dict(elements=int(out[0]), touched_nodes=int(out[1]), device_bytes=int(out[2]))
+
+    def nonlinear_fetch(self):
+        """hq_nonlinear_fetch -> (pstrain [n, 8, 6], ep [n, 8]): the caller's element order, the reference's quadrature order
+        and tensor order (xx yy zz xy yz xz)."""
+        n = self.nonlinear_info()["elements"]
+        pstrain, ep = np.zeros((n, 8, 6)), np.zeros((n, 8))
+        _check(self._lib.hq_nonlinear_fetch(self._h, _ptr_or_pad(pstrain), _ptr_or_pad(ep)), self._lib)
+        return pstrain, ep
+
+    def nonlinear_load(self, pstrain, ep):
+        """hq_nonlinear_load: the two arrays as nonlinear_fetch returns them."""
+        n = self.nonlinear_info()["elements"]
+        pstrain, ep = np.ascontiguousarray(pstrain, np.float64), np.ascontiguousarray(ep, np.float64)
+        if pstrain.shape != (n, 8, 6) or ep.shape != (n, 8):
+            raise HqError("nonlinear_load: arrays of shape %r, %r are not [%d, 8, 6], [%d, 8]" % (pstrain.shape, ep.shape, n, n))
+        _check(self._lib.hq_nonlinear_load(self._h, _ptr_or_pad(pstrain), _ptr_or_pad(ep)), self._lib)
+
+    def clear_nonlinear(self):
+        """hq_nonlinear_clear: the context steps as it did before; the added bytes go."""
+        _check(self._lib.hq_nonlinear_clear(self._h), self._lib)
+
     def phase_force(self):
         _check(self._lib.hq_phase_force(self._h), self._lib)
 
@@ -858,6 +910,45 @@ def attenuation_split_table_faults(desc, epos, nptr, nent, sd):
     faults = ctypes.c_int64()
     _check(load_library().hq_attenuation_split_table_faults(ctypes.byref(desc), _ptr(epos), _ptr(nptr), _ptr(nent), _ptr(sd) if len(sd) else None,
                                                             ctypes.c_int64(len(sd)), ctypes.byref(faults)))
+    return int(faults.value)
+
+
+NONLINEAR_PLAN_REPORT = ("elements", "touched_nodes", "device_bytes", "faults")
+
+
+def nonlinear_plan_check(desc, model, elems, cons):
+    """hq_nonlinear_plan_check on a filled _Desc: the touched-node list and the node -> (element, corner) table of a nonlinear
+    context, host only (no device needed)."""
+    nl = _nonlinear_desc(model, elems, cons, "nonlinear_plan_check")
+    rep = (ctypes.c_int64 * 4)()
+    _check(load_library().hq_nonlinear_plan_check(ctypes.byref(desc), ctypes.byref(nl), rep))
+    return dict(zip(NONLINEAR_PLAN_REPORT, [int(v) for v in rep]))
+
+
+def nonlinear_plan_tables(desc, model, elems, cons):
+    """hq_nonlinear_plan_tables -> (tnode [T], epos [n], nptr [T + 1], nent [8 n], sd [H, 3]) int32: the touched nodes in the
+    numbering hq_create gives desc, the tables on touched-node indices."""
+    lib = load_library()
+    nl = _nonlinear_desc(model, elems, cons, "nonlinear_plan_tables")
+    counts = (ctypes.c_int64 * 4)()
+    _check(lib.hq_nonlinear_plan_tables(ctypes.byref(desc), ctypes.byref(nl), None, None, None, None, None, counts))
+    tnode, epos = np.zeros(counts[0], np.int32), np.zeros(nl.nelems, np.int32)
+    nptr, nent, sd = np.zeros(counts[1], np.int32), np.zeros(counts[2], np.int32), np.zeros((counts[3], 3), np.int32)
+    _check(lib.hq_nonlinear_plan_tables(ctypes.byref(desc), ctypes.byref(nl), _ptr_or_pad(tnode), _ptr_or_pad(epos), _ptr_or_pad(nptr),
+                                        _ptr_or_pad(nent), _ptr_or_pad(sd), counts))
+    return tnode, epos, nptr, nent, sd
+
+
+def nonlinear_table_faults(desc, model, elems, cons, tnode, epos, nptr, nent, sd):
+    """hq_nonlinear_table_faults: the faults the nonlinear plan check counts in the given tables."""
+    nl = _nonlinear_desc(model, elems, cons, "nonlinear_table_faults")
+    tnode, epos, nptr, nent = [np.ascontiguousarray(a, np.int32) for a in (tnode, epos, nptr, nent)]
+    sd = np.ascontiguousarray(sd, np.int32).reshape(-1, 3)
+    if len(nptr) != len(tnode) + 1 or len(nent) != 8 * nl.nelems or len(epos) != nl.nelems:
+        raise HqError("nonlinear_table_faults: tables of %d, %d entries for %d nodes, %d elements" % (len(nptr), len(nent), len(tnode), nl.nelems))
+    faults = ctypes.c_int64()
+    _check(load_library().hq_nonlinear_table_faults(ctypes.byref(desc), ctypes.byref(nl), _ptr(tnode), _ptr(epos), _ptr(nptr), _ptr(nent),
+                                                    _ptr(sd) if len(sd) else None, ctypes.c_int64(len(sd)), ctypes.byref(faults)))
     return int(faults.value)
 
 

@@ -140,6 +140,24 @@ static int64_t hq_split_plan_faults(int64_t E, int64_t N, int64_t Epad, const in
     return bad;
 }
 
+/* hq_k_distribute's tables of a plan's {hanging node, anchor, deps} triples: the entries grouped by the anchor they add to,
+ * inside an anchor in the triples' order (hq_build_distribution's grouping) */
+static void hq_split_group_by_anchor(const std::vector<int32_t>& sd, std::vector<int32_t>* dst, std::vector<int32_t>* ptr,
+                                     std::vector<int32_t>* src, std::vector<int32_t>* deps)
+{
+    const size_t n = sd.size() / 3;
+    std::vector<int32_t> order(n);
+    for (size_t i = 0; i < n; i++) order[i] = (int32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return sd[3 * (size_t)x + 1] < sd[3 * (size_t)y + 1]; });
+    dst->clear(); src->clear(); deps->clear(); ptr->assign(1, 0);
+    for (size_t k = 0; k < n; k++) {
+        const size_t i = (size_t)order[k];
+        if (dst->empty() || dst->back() != sd[3 * i + 1]) { if (!dst->empty()) ptr->push_back((int32_t)src->size()); dst->push_back(sd[3 * i + 1]); }
+        src->push_back(sd[3 * i]); deps->push_back(sd[3 * i + 2]);
+    }
+    ptr->push_back((int32_t)src->size());
+}
+
 #if defined(__HIPCC__)
 /*
  * hq_k_atten_advance in delta form (the text is hq_atten.h's hq_atten_advance_delta): one thread per slot, SoA rows.  Per
@@ -236,6 +254,17 @@ hq_k_atten_apply(int64_t n3, const double* __restrict__ mass, const double* __re
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n3) return;
     un[t] = (hq_real)((double)un[t] + dF[t] / mass[t / 3]);
+}
+
+/* the same over a list of nodes, dF and the mass on the list's indices: un[node[k]] += dF[k] / mass[k] (hq_nonlin_dev.h) */
+__global__ void __launch_bounds__(256)
+hq_k_atten_apply_at(int64_t n3, const int32_t* __restrict__ node, const double* __restrict__ mass, const double* __restrict__ dF,
+                    hq_real* __restrict__ un)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n3) return;
+    const int64_t k = t / 3, at = 3 * (int64_t)node[k] + (t - 3 * k);
+    un[at] = (hq_real)((double)un[at] + dF[t] / mass[k]);
 }
 #endif /* __HIPCC__ */
 

@@ -111,6 +111,7 @@ static int hq_rccl_load(void)
 
 #include "hq_atten_plan.h"
 #include "hq_atten_split.h"
+#include "hq_nonlin_dev.h"
 
 /* ------------------------------------------------------------------------ */
 /* context                                                                  */
@@ -138,6 +139,26 @@ struct hq_atten_dev {
     hq_dbuf<double> d_mv;            /* [HQ_ATTEN_NSTATE][nslots] memory variables         */
     hq_dbuf<double> d_w;             /* [HQ_ATTEN_NW][nslots] damping vectors of this step */
     std::vector<int32_t> h_eslot, h_slot_node;
+};
+
+/* Nonlinear soil of a patch context (hq_nonlinear_set; hq_nonlin.h, hq_nonlin_dev.h): state, constants and tables on the
+ * device over the nonlinear elements and the nodes they touch; the place of every element of the caller's list on the host,
+ * for fetch / load in the caller's order */
+struct hq_nl_dev {
+    bool on = false;
+    int32_t model = 0, nel = 0, Enlpad = 0, nt = 0;
+    int64_t bytes = 0;               /* hq_nl_bytes */
+    hq_dbuf<double> d_st;            /* [7][8][Enlpad] plastic strain (6) and effective plastic strain per point */
+    hq_dbuf<double> d_ef;            /* [3][8][Enlpad] corner forces of this step                                 */
+    hq_dbuf<double> d_cons;          /* [6][Enlpad]                                                               */
+    hq_dbuf<int32_t> d_lnid;         /* [8][Enlpad] device node ids                                               */
+    hq_dbuf<int32_t> d_nptr, d_nent; /* [nt + 1], [8 nel] touched node -> (element, corner)                       */
+    hq_dbuf<double> d_dF;            /* [nt][3]                                                                   */
+    hq_dbuf<double> d_mass;          /* [nt]                                                                      */
+    hq_dbuf<int32_t> d_tnode;        /* [nt] device node ids                                                      */
+    int32_t nSD = 0;
+    hq_dbuf<int32_t> d_sd_dst, d_sd_ptr, d_sd_src, d_sd_deps;
+    std::vector<int32_t> h_epos;     /* [nel] */
 };
 
 struct hq_dev_messenger {
@@ -197,6 +218,7 @@ struct hq_ctx {
     hq_dbuf<double> d_c1, d_c2, d_beta;
     bool etable_damped = false;     /* some c3 or c4 of the caller's eTable is not 0 */
     hq_atten_dev att;
+    hq_nl_dev nl;
     /* patch variant, for hq_attenuation_set_split (which gets no mesh): the element table in device numbering and the caller's
      * element order, c1 / c2 and n_t[n][0], kept on the HOST (48 B per element + 8 B per node; nothing on the device) */
     std::vector<int32_t> h_lnid;
@@ -1309,6 +1331,39 @@ static int hq_atten_split_tail(hq_ctx* c, hq_real* un)
     return HQ_OK;
 }
 
+/*
+ * A nonlinear context's step (hq_nonlin_dev.h), the split pass's shape: the element kernel and the node sum read u(t) only
+ * and fork onto the correction stream; distribution, apply and assignment follow every step kernel on the compute stream.
+ */
+static int hq_nl_head(hq_ctx* c)
+{
+    const hq_nl_dev& L = c->nl;
+    if (!L.nel) return HQ_OK;
+    hipStream_t as = c->astream;
+    HQ_HIP(hipEventRecord(c->ev_att_fork, c->stream));
+    HQ_HIP(hipStreamWaitEvent(as, c->ev_att_fork, 0));
+    hq_k_nl_element<<<hq_blocks(L.nel, 256), 256, 0, as>>>(L.nel, L.Enlpad, L.d_lnid, L.d_cons, c->d_u[c->now], c->dt2, L.d_st, L.d_ef);
+    hq_k_atten_node_sum<<<hq_blocks(L.nt, 256), 256, 0, as>>>(L.nt, L.Enlpad, L.d_nptr, L.d_nent, L.d_ef, L.d_dF);
+    HQ_HIP(hipEventRecord(c->ev_att_done, as));
+    return HQ_OK;
+}
+
+static int hq_nl_tail(hq_ctx* c, hq_real* un)
+{
+    const hq_nl_dev& L = c->nl;
+    if (!L.nel) return HQ_OK;
+    if (c->bstream) HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_bricks, 0));
+    HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_att_done, 0));
+    if (L.nSD)
+        hq_k_distribute<<<hq_blocks(L.nSD * 3, 256), 256, 0, c->stream>>>(L.nSD, L.d_sd_dst, L.d_sd_ptr, L.d_sd_src, L.d_sd_deps, L.d_dF);
+    const int64_t n3 = 3 * (int64_t)L.nt;
+    hq_k_atten_apply_at<<<hq_blocks(n3, 256), 256, 0, c->stream>>>(n3, L.d_tnode, L.d_mass, L.d_dF, un);
+    if (c->ldnnum)
+        hq_k_adjust_assign<<<hq_blocks(c->ldnnum * 3, 256), 256, 0, c->stream>>>(c->ldnnum, c->d_dn_id, c->d_dn_ptr, c->d_dn_anchor, un);
+    if (c->bstream) HQ_HIP(hipEventRecord(c->ev_patches, c->stream));     /* (as hq_atten_split_tail's) */
+    return HQ_OK;
+}
+
 static int hq_phase(hq_ctx* c, int ph)
 {
     const bool patch = (c->variant == HQ_VARIANT_PATCH);
@@ -1338,6 +1393,7 @@ static int hq_phase(hq_ctx* c, int ph)
                 HQ_HIP(hipStreamWaitEvent(c->bstream, c->ev_patches, 0));
             }
             if (c->att.split) HQ_TRY(hq_atten_split_head(c));
+            if (c->nl.on) HQ_TRY(hq_nl_head(c));
             HQ_TRY(hq_outputs_enqueue(c, bs));     /* solver_write_checkpoint / _output_wavefield / _planes / _stations, :4277-4280 */
             auto launch_bricks = [&]() {
                 if (c->bricks.nunits > 0)
@@ -1500,6 +1556,7 @@ static int hq_phase(hq_ctx* c, int ph)
         HQ_TRY(hq_xchg_recv(c, &c->dn, unew, false, false));
         if (patch) {
             if (c->att.split) HQ_TRY(hq_atten_split_tail(c, unew));
+            if (c->nl.on) HQ_TRY(hq_nl_tail(c, unew));
             if (c->overlap) HQ_HIP(hipEventRecord(c->ev_shared, c->cstream));
             if (hq_has_transport(c)) hq_clock(c, hq_ctx::HQ_CLK_CHAIN1, c->overlap ? c->cstream : c->stream);
             int n = c->now, p = c->prev, sp = c->spare;
@@ -2725,6 +2782,8 @@ extern "C" int hq_upload(hq_ctx* c, const hq_real* tm1, const hq_real* tm2, int3
     /* the memory variables after a restart: calloc, psolve.c:3322-3325 (io_checkpoint.c carries tm1 / tm2 only); an exact
      * restart follows with hq_attenuation_load */
     if (c->att.on) HQ_TRY(c->att.d_mv.fill(0, c->stream));
+    /* the plastic strains after a restart: calloc, nonlinear.c:651-664; an exact restart follows with hq_nonlinear_load */
+    if (c->nl.on && c->nl.nel) HQ_TRY(c->nl.d_st.fill(0, c->stream));
     c->step = step;
     return HQ_OK;
 }
@@ -2787,11 +2846,29 @@ static int hq_atten_ktab(const hq_atten_plan& P, double freq, double dt, std::ve
     return HQ_OK;
 }
 
-/* a split context steps alone: no partition, no transport (include/hq_solver.h) */
+/* a split context steps alone: no partition, no transport (include/hq_solver.h); a nonlinear one likewise */
 static int hq_refuse_split(const hq_ctx* c, const char* what)
 {
     if (c && c->att.split)
         return hq_fail(HQ_ERR_STATE, "%s: the context carries split attenuation (hq_attenuation_set_split), which steps one context alone", what);
+    if (c && c->nl.on)
+        return hq_fail(HQ_ERR_STATE, "%s: the context carries nonlinear soil (hq_nonlinear_set), which steps one context alone", what);
+    return HQ_OK;
+}
+
+/* the stream and the two events of a correction chain's head beside the step, from the first call that needs them on */
+static int hq_correction_stream(hq_ctx* c, const char* who)
+{
+    if (c->astream) return HQ_OK;
+    hipStream_t st = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e0, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess) {
+        if (st) hipStreamDestroy(st);
+        if (e0) hipEventDestroy(e0);
+        return hq_fail(HQ_ERR_DEVICE, "%s: no stream or event", who);
+    }
+    c->astream = st; c->ev_att_fork = e0; c->ev_att_done = e1;
     return HQ_OK;
 }
 
@@ -2804,6 +2881,8 @@ extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
         return hq_fail(HQ_ERR_STATE, "split attenuation runs beside the patch variant's step: on a scatter context call hq_attenuation_set%s", "");
     if (c->nranks > 1 || hq_has_transport(c) || c->group)
         return hq_fail(HQ_ERR_STATE, "split attenuation: partitions and transports are out of scope (one context, nranks = 1)%s", "");
+    if (c->nl.on)
+        return hq_fail(HQ_ERR_STATE, "split attenuation: the context carries nonlinear soil (hq_nonlinear_set); the two passes do not combine%s", "");
     if (!(a->freq > 0.0) || !std::isfinite(a->freq)) return hq_fail(HQ_ERR_ARG, "attenuation: freq must be finite and > 0%s", "");
     if (c->etable_damped)
         return hq_fail(HQ_ERR_ARG, "attenuation: the eTable has c3 or c4 != 0; under BKT compute_setab yields a = b = 0 (psolve.c:5869)%s", "");
@@ -2828,17 +2907,7 @@ extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
         hq_split_plan_faults(E, N, P.Epad, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), S.epos.data(),
                              S.nptr.data(), S.nent.data(), S.sd.data(), (int64_t)(S.sd.size() / 3)) != 0)
         return hq_fail(HQ_ERR_STATE, "split attenuation: the plan does not pass its own check%s", "");
-    if (!c->astream) {
-        hipStream_t st = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e0, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess) {
-            if (st) hipStreamDestroy(st);
-            if (e0) hipEventDestroy(e0);
-            return hq_fail(HQ_ERR_DEVICE, "split attenuation: no stream or event%s", "");
-        }
-        c->astream = st; c->ev_att_fork = e0; c->ev_att_done = e1;
-    }
+    HQ_TRY(hq_correction_stream(c, "split attenuation"));
     /* everything is built beside the context's own and moved in at the end: a refusal leaves the context as it was */
     hq_atten_dev A;
     int rc;
@@ -2864,18 +2933,8 @@ extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
                               A.d_w.bytes() + A.d_ef.bytes() + A.d_dF.bytes() + A.d_mass.bytes() + A.d_c1.bytes() + A.d_c2.bytes() +
                               A.d_nptr.bytes() + A.d_nent.bytes());
     if (!S.sd.empty()) {
-        /* hq_build_distribution's grouping by anchor, into A's own tables */
-        const size_t n = S.sd.size() / 3;
-        std::vector<int32_t> order(n);
-        for (size_t i = 0; i < n; i++) order[i] = (int32_t)i;
-        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return S.sd[3 * (size_t)x + 1] < S.sd[3 * (size_t)y + 1]; });
-        std::vector<int32_t> dst, ptr(1, 0), src, deps;
-        for (size_t k = 0; k < n; k++) {
-            const size_t i = (size_t)order[k];
-            if (dst.empty() || dst.back() != S.sd[3 * i + 1]) { if (!dst.empty()) ptr.push_back((int32_t)src.size()); dst.push_back(S.sd[3 * i + 1]); }
-            src.push_back(S.sd[3 * i]); deps.push_back(S.sd[3 * i + 2]);
-        }
-        ptr.push_back((int32_t)src.size());
+        std::vector<int32_t> dst, ptr, src, deps;        /* hq_build_distribution's grouping by anchor, into A's own tables */
+        hq_split_group_by_anchor(S.sd, &dst, &ptr, &src, &deps);
         if ((rc = A.d_sd_dst.put(nullptr, dst, c->stream)) != HQ_OK || (rc = A.d_sd_ptr.put(nullptr, ptr, c->stream)) != HQ_OK ||
             (rc = A.d_sd_src.put(nullptr, src, c->stream)) != HQ_OK || (rc = A.d_sd_deps.put(nullptr, deps, c->stream)) != HQ_OK)
             return rc;
@@ -3051,6 +3110,233 @@ extern "C" int hq_attenuation_split_table_faults(const hq_desc* d, const int32_t
     HQ_TRY(hq_split_plan_of(d, &prep, &Epad, &S));
     const hq_desc& q = prep.desc;
     *faults = hq_split_plan_faults(q.lenum, q.nharbored, Epad, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, epos, nptr, nent, sd, nsd);
+    return HQ_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+/* nonlinear soil (hq_nonlin.h, hq_nonlin_dev.h)                            */
+/* ------------------------------------------------------------------------ */
+
+/* the description's own faults: model, ids, constants (include/hq_solver.h) */
+static int hq_nl_validate(const hq_nonlinear_desc* a, int64_t E)
+{
+    if (a->model != HQ_NL_VONMISES && a->model != HQ_NL_DRUCKERPRAGER)
+        return hq_fail(HQ_ERR_ARG, "nonlinear: unknown model (HQ_NL_VONMISES or HQ_NL_DRUCKERPRAGER)%s", "");
+    if (a->nelems < 0 || (a->nelems > 0 && (!a->elems || !a->cons))) return hq_fail(HQ_ERR_ARG, "nonlinear: nelems < 0 or a null table%s", "");
+    for (int64_t k = 0; k < a->nelems; k++) {
+        if (a->elems[k] < 0 || a->elems[k] >= E) return hq_fail(HQ_ERR_ARG, "nonlinear: an element id is out of range%s", "");
+        if (k && a->elems[k] <= a->elems[k - 1]) return hq_fail(HQ_ERR_ARG, "nonlinear: the element ids are not strictly ascending%s", "");
+        const double* q = a->cons + HQ_NL_NCONS * k;
+        for (int j = 0; j < HQ_NL_NCONS; j++)
+            if (!std::isfinite(q[j])) return hq_fail(HQ_ERR_ARG, "nonlinear: a constant is not finite%s", "");
+        if (!(q[0] > 0.0)) return hq_fail(HQ_ERR_ARG, "nonlinear: h must be > 0%s", "");
+        if (q[1] < 0.0) return hq_fail(HQ_ERR_ARG, "nonlinear: mu must be >= 0%s", "");
+        if (q[4] < 0.0) return hq_fail(HQ_ERR_ARG, "nonlinear: k must be >= 0%s", "");
+        if (a->model == HQ_NL_VONMISES && q[3] != 0.0) return hq_fail(HQ_ERR_ARG, "nonlinear: alpha must be 0 under von Mises%s", "");
+    }
+    return HQ_OK;
+}
+
+extern "C" int hq_nonlinear_clear(hq_ctx* c)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (!c->nl.on) return HQ_OK;
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    c->bytes -= c->nl.bytes;
+    c->nl = hq_nl_dev();
+    return HQ_OK;
+}
+
+extern "C" int hq_nonlinear_set(hq_ctx* c, const hq_nonlinear_desc* a)
+{
+    if (!c || !a) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (sizeof(hq_real) != sizeof(double))
+        return hq_fail(HQ_ERR_STATE, "nonlinear: not in the float library (the plastic strains are double state beside a double step)%s", "");
+    if (c->variant != HQ_VARIANT_PATCH)
+        return hq_fail(HQ_ERR_STATE, "nonlinear soil runs beside the patch variant's step: create the context with HQ_VARIANT_PATCH%s", "");
+    if (c->nranks > 1 || hq_has_transport(c) || c->group)
+        return hq_fail(HQ_ERR_STATE, "nonlinear: partitions and transports are out of scope (one context, nranks = 1)%s", "");
+    if (c->att.on)
+        return hq_fail(HQ_ERR_STATE, "nonlinear: the context carries attenuation; the two passes do not combine (hq_attenuation_clear first)%s", "");
+    HQ_TRY(hq_nl_validate(a, c->E));
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    hq_nl_dev L;                                      /* built beside the context's own: a refusal leaves the context as it was */
+    L.model = a->model;
+    const int64_t nel = a->nelems;
+    int64_t added = 0;
+    if (nel > 0) {
+        std::vector<int32_t> dn_id((size_t)c->ldnnum), dn_ptr((size_t)c->ldnnum + 1, 0), dn_anchor;
+        if (c->ldnnum) {
+            HQ_TRY(hq_copy_wait(dn_id.data(), c->d_dn_id, sizeof(int32_t) * dn_id.size(), hipMemcpyDeviceToHost, c->stream));
+            HQ_TRY(hq_copy_wait(dn_ptr.data(), c->d_dn_ptr, sizeof(int32_t) * dn_ptr.size(), hipMemcpyDeviceToHost, c->stream));
+            dn_anchor.resize((size_t)dn_ptr[(size_t)c->ldnnum]);
+            HQ_TRY(hq_copy_wait(dn_anchor.data(), c->d_dn_anchor, sizeof(int32_t) * dn_anchor.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        hq_nl_plan P;
+        HQ_TRY(hq_nl_plan_build(nel, a->elems, c->N, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), &P));
+        if (hq_nl_plan_faults(nel, a->elems, c->N, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), P, P.S.epos.data(),
+                              P.S.nptr.data(), P.S.nent.data(), P.S.sd.data(), (int64_t)(P.S.sd.size() / 3)) != 0)
+            return hq_fail(HQ_ERR_STATE, "nonlinear: the plan does not pass its own check%s", "");
+        HQ_TRY(hq_correction_stream(c, "nonlinear"));
+        const int64_t Ep = P.Enlpad, nt = P.nt;
+        std::vector<int32_t> lnid_dev((size_t)(8 * Ep), P.tnode[0]);          /* (the padding names a node that exists) */
+        std::vector<double> cons_dev((size_t)(HQ_NL_NCONS * Ep), 0.0), mass((size_t)nt);
+        for (int64_t k = 0; k < nel; k++) {
+            const size_t at = (size_t)P.S.epos[(size_t)k];
+            for (int i = 0; i < 8; i++) lnid_dev[(size_t)(i * Ep) + at] = P.tnode[(size_t)P.lnid[(size_t)(8 * k + i)]];
+            for (int j = 0; j < HQ_NL_NCONS; j++) cons_dev[(size_t)(j * Ep) + at] = a->cons[HQ_NL_NCONS * k + j];
+        }
+        for (int64_t t = 0; t < nt; t++) mass[(size_t)t] = c->h_mass[(size_t)P.tnode[(size_t)t]];
+        int rc;
+        if ((rc = L.d_st.alloc(nullptr, (size_t)(HQ_NL_NSTATE * 8 * Ep))) != HQ_OK || (rc = L.d_st.fill(0, c->stream)) != HQ_OK ||
+            (rc = L.d_ef.alloc(nullptr, (size_t)(24 * Ep))) != HQ_OK || (rc = L.d_ef.fill(0, c->stream)) != HQ_OK ||
+            (rc = L.d_cons.put(nullptr, cons_dev, c->stream)) != HQ_OK || (rc = L.d_lnid.put(nullptr, lnid_dev, c->stream)) != HQ_OK ||
+            (rc = L.d_nptr.put(nullptr, P.S.nptr, c->stream)) != HQ_OK || (rc = L.d_nent.put(nullptr, P.S.nent, c->stream)) != HQ_OK ||
+            (rc = L.d_dF.alloc(nullptr, 3 * (size_t)nt)) != HQ_OK || (rc = L.d_dF.fill(0, c->stream)) != HQ_OK ||
+            (rc = L.d_mass.put(nullptr, mass, c->stream)) != HQ_OK || (rc = L.d_tnode.put(nullptr, P.tnode, c->stream)) != HQ_OK)
+            return rc;
+        added = (int64_t)(L.d_st.bytes() + L.d_ef.bytes() + L.d_cons.bytes() + L.d_lnid.bytes() + L.d_nptr.bytes() + L.d_nent.bytes() +
+                          L.d_dF.bytes() + L.d_mass.bytes() + L.d_tnode.bytes());
+        if (!P.S.sd.empty()) {
+            std::vector<int32_t> dst, ptr, src, deps;
+            hq_split_group_by_anchor(P.S.sd, &dst, &ptr, &src, &deps);
+            if ((rc = L.d_sd_dst.put(nullptr, dst, c->stream)) != HQ_OK || (rc = L.d_sd_ptr.put(nullptr, ptr, c->stream)) != HQ_OK ||
+                (rc = L.d_sd_src.put(nullptr, src, c->stream)) != HQ_OK || (rc = L.d_sd_deps.put(nullptr, deps, c->stream)) != HQ_OK)
+                return rc;
+            L.nSD = (int32_t)dst.size();
+            added += (int64_t)(L.d_sd_dst.bytes() + L.d_sd_ptr.bytes() + L.d_sd_src.bytes() + L.d_sd_deps.bytes());
+        }
+        if (added != hq_nl_bytes(nel, Ep, nt, P.S.nanchors, P.S.npairs))
+            return hq_fail(HQ_ERR_STATE, "nonlinear: the device bytes are not the header's formula%s", "");
+        L.nel = (int32_t)nel; L.Enlpad = (int32_t)Ep; L.nt = (int32_t)nt;
+        L.h_epos = std::move(P.S.epos);
+    }
+    L.bytes = added;
+    L.on = true;
+    hq_nonlinear_clear(c);
+    c->nl = std::move(L);
+    c->bytes += added;
+    return HQ_OK;
+}
+
+extern "C" int hq_nonlinear_info(hq_ctx* c, int64_t out[4])
+{
+    if (!c || !out) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    out[0] = c->nl.nel; out[1] = c->nl.nt;
+    out[2] = c->nl.on ? c->nl.bytes : 0;
+    out[3] = 0;
+    return HQ_OK;
+}
+
+/* pstrain [nelems][8][6], ep [nelems][8]: the caller's element order, the reference's quadrature and tensor order; a NULL one
+ * is left out */
+extern "C" int hq_nonlinear_fetch(hq_ctx* c, double* pstrain, double* ep)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (!c->nl.on) return hq_fail(HQ_ERR_STATE, "nonlinear soil is not set on this context%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    const hq_nl_dev& L = c->nl;
+    if (!L.nel) return HQ_OK;
+    const int64_t Ep = L.Enlpad;
+    std::vector<double> st((size_t)(HQ_NL_NSTATE * 8 * Ep));
+    HQ_TRY(hq_copy_wait(st.data(), L.d_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, c->stream));
+    c->d2h_bytes += (int64_t)(sizeof(double) * st.size());
+    for (int64_t k = 0; k < L.nel; k++) {
+        const int64_t at = L.h_epos[(size_t)k];
+        for (int j = 0; j < 8; j++) {
+            if (pstrain)
+                for (int q = 0; q < 6; q++) pstrain[(8 * k + j) * 6 + q] = st[(size_t)((q * 8 + j) * Ep + at)];
+            if (ep) ep[8 * k + j] = st[(size_t)((6 * 8 + j) * Ep + at)];
+        }
+    }
+    return HQ_OK;
+}
+
+extern "C" int hq_nonlinear_load(hq_ctx* c, const double* pstrain, const double* ep)
+{
+    if (!c) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    if (!c->nl.on) return hq_fail(HQ_ERR_STATE, "nonlinear soil is not set on this context%s", "");
+    const hq_nl_dev& L = c->nl;
+    if (L.nel && (!pstrain || !ep)) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    HQ_HIP(hipSetDevice(c->device));
+    HQ_HIP(hq_quiesce(c));
+    if (!L.nel) return HQ_OK;
+    const int64_t Ep = L.Enlpad;
+    std::vector<double> st((size_t)(HQ_NL_NSTATE * 8 * Ep), 0.0);
+    for (int64_t k = 0; k < L.nel; k++) {
+        const int64_t at = L.h_epos[(size_t)k];
+        for (int j = 0; j < 8; j++) {
+            for (int q = 0; q < 6; q++) {
+                const double x = pstrain[(8 * k + j) * 6 + q];
+                if (!std::isfinite(x)) return hq_fail(HQ_ERR_ARG, "nonlinear: a plastic strain to load is not finite%s", "");
+                st[(size_t)((q * 8 + j) * Ep + at)] = x;
+            }
+            const double x = ep[8 * k + j];
+            if (!std::isfinite(x)) return hq_fail(HQ_ERR_ARG, "nonlinear: a plastic strain to load is not finite%s", "");
+            st[(size_t)((6 * 8 + j) * Ep + at)] = x;
+        }
+    }
+    c->h2d_bytes += (int64_t)(sizeof(double) * st.size());
+    return c->nl.d_st.upload(st.data(), st.size(), c->stream);
+}
+
+/* the description as hq_create would number it, and the nonlinear plan of it */
+static int hq_nl_plan_of(const hq_desc* d, const hq_nonlinear_desc* a, hq_prep* prep, hq_nl_plan* P)
+{
+    if (d->nranks > 1) return hq_fail(HQ_ERR_STATE, "nonlinear: partitions and transports are out of scope (one context, nranks = 1)%s", "");
+    HQ_TRY(hq_nl_validate(a, d->lenum));
+    hq_options opts;
+    hq_options_resolve(&opts, nullptr);
+    HQ_TRY(hq_prepare(d, opts, d->eTable && d->nTable && d->node_xyz ? HQ_PREP_BRICKS : 0, prep));
+    const hq_desc& q = prep->desc;
+    if (a->nelems == 0) { *P = hq_nl_plan(); return HQ_OK; }
+    return hq_nl_plan_build(a->nelems, a->elems, q.nharbored, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, P);
+}
+
+extern "C" int hq_nonlinear_plan_check(const hq_desc* d, const hq_nonlinear_desc* a, int64_t report[4])
+{
+    if (!d || !a || !report) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_prep prep;
+    hq_nl_plan P;
+    HQ_TRY(hq_nl_plan_of(d, a, &prep, &P));
+    const hq_desc& q = prep.desc;
+    report[0] = P.nel; report[1] = P.nt;
+    report[2] = hq_nl_bytes(P.nel, P.Enlpad, P.nt, P.S.nanchors, P.S.npairs);
+    report[3] = P.nel ? hq_nl_plan_faults(P.nel, a->elems, q.nharbored, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, P, P.S.epos.data(),
+                                          P.S.nptr.data(), P.S.nent.data(), P.S.sd.data(), (int64_t)(P.S.sd.size() / 3)) : 0;
+    return HQ_OK;
+}
+
+extern "C" int hq_nonlinear_plan_tables(const hq_desc* d, const hq_nonlinear_desc* a, int32_t* tnode, int32_t* epos, int32_t* nptr,
+                                        int32_t* nent, int32_t* sd, int64_t counts[4])
+{
+    if (!d || !a || !counts) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_prep prep;
+    hq_nl_plan P;
+    HQ_TRY(hq_nl_plan_of(d, a, &prep, &P));
+    counts[0] = P.nt; counts[1] = (int64_t)P.S.nptr.size(); counts[2] = (int64_t)P.S.nent.size(); counts[3] = (int64_t)(P.S.sd.size() / 3);
+    if (tnode && P.nt) memcpy(tnode, P.tnode.data(), sizeof(int32_t) * P.tnode.size());
+    if (epos && P.nel) memcpy(epos, P.S.epos.data(), sizeof(int32_t) * P.S.epos.size());
+    if (nptr && P.nel) memcpy(nptr, P.S.nptr.data(), sizeof(int32_t) * P.S.nptr.size());
+    if (nent && P.nel) memcpy(nent, P.S.nent.data(), sizeof(int32_t) * P.S.nent.size());
+    if (sd && !P.S.sd.empty()) memcpy(sd, P.S.sd.data(), sizeof(int32_t) * P.S.sd.size());
+    return HQ_OK;
+}
+
+extern "C" int hq_nonlinear_table_faults(const hq_desc* d, const hq_nonlinear_desc* a, const int32_t* tnode, const int32_t* epos,
+                                         const int32_t* nptr, const int32_t* nent, const int32_t* sd, int64_t nsd, int64_t* faults)
+{
+    if (!d || !a || !tnode || !epos || !nptr || !nent || !faults || nsd < 0 || (nsd && !sd)) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
+    hq_prep prep;
+    hq_nl_plan P;
+    HQ_TRY(hq_nl_plan_of(d, a, &prep, &P));
+    if (!P.nel) return hq_fail(HQ_ERR_ARG, "nonlinear: no tables without elements%s", "");
+    const hq_desc& q = prep.desc;
+    P.tnode.assign(tnode, tnode + P.nt);              /* the caller's list in the plan's place: the plan's own lnid must still fit it */
+    *faults = hq_nl_plan_faults(P.nel, a->elems, q.nharbored, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, P, epos, nptr, nent, sd, nsd);
     return HQ_OK;
 }
 

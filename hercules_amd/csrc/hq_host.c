@@ -38,6 +38,7 @@
 #include "hq_atten.h"
 #include "hq_cumul.h"
 #include "hq_deform.h"
+#include "hq_nonlin.h"
 #include "hq_sdof.h"
 #include "hq_sample.h"
 
@@ -1592,6 +1593,121 @@ int hqh_deform_fold(int32_t npoints, int32_t quantities, const double* lame, int
             hq_deform_point(quantities, G, G + 9, stress ? lame[2 * (int64_t)p] : 0.0, stress ? lame[2 * (int64_t)p + 1] : 0.0,
                             steps[k], vals + (int64_t)p * nv, 1, when + (int64_t)p * nw, 1);
         }
+    return HQ_OK;
+}
+
+/* interpolate_property_value (nonlinear.c:102-136): column `col` of props [nrows][6] at vs, the Vs limits in column 0 */
+static double nl_interpolate(int32_t nrows, const double* props, int col, double vs)
+{
+    if (vs <= props[0]) return props[col];
+    if (vs > props[6 * (int64_t)(nrows - 1)]) return props[6 * (int64_t)(nrows - 1) + col];
+    double vs0 = 0, vs1 = 0, prop0 = 0, prop1 = 0;
+    for (int32_t i = 0; i < nrows - 1; i++)
+        if (vs > props[6 * (int64_t)i] && vs <= props[6 * (int64_t)(i + 1)]) {
+            vs0 = props[6 * (int64_t)i]; vs1 = props[6 * (int64_t)(i + 1)];
+            prop0 = props[6 * (int64_t)i + col]; prop1 = props[6 * (int64_t)(i + 1) + col];
+        }
+    return prop0 + (vs - vs0) * ((prop1 - prop0) / (vs1 - vs0));
+}
+
+int hqh_nonlinear_constants(int32_t lenum, const float* edata, double threshold_vpvs, int32_t model, int32_t properties, int32_t nrows,
+                            const double* props, double vs_min, double vs_cut, int32_t* elems, double* cons, int32_t* nelems)
+{
+    if (lenum < 0 || nrows < 1 || !props || !nelems || (lenum && !edata)) return HQ_ERR_ARG;
+    if (model != HQ_NL_VONMISES && model != HQ_NL_DRUCKERPRAGER) return HQ_ERR_ARG;
+    if (properties != HQH_NL_ALPHAKAY && properties != HQH_NL_COHEFRICTION) return HQ_ERR_ARG;
+    for (int64_t i = 0; i < 6 * (int64_t)nrows; i++)
+        if (props[i] - props[i] != 0.0) return HQ_ERR_ARG;
+    for (int32_t i = 1; i < nrows; i++)
+        if (!(props[6 * (int64_t)i] > props[6 * (int64_t)(i - 1)])) return HQ_ERR_ARG;      /* the Vs limits rise */
+    const double PI = 3.14159265358979323846264338327;                                       /* psolve.c:70 */
+    int32_t n = 0;
+    for (int32_t e = 0; e < lenum; e++) {
+        const float h = edata[4 * (int64_t)e];
+        float Vp = edata[4 * (int64_t)e + 1];
+        const float Vs = edata[4 * (int64_t)e + 2], rho = edata[4 * (int64_t)e + 3];
+        if (!(Vs <= vs_cut && Vs >= vs_min)) continue;                                       /* isThisElementNonLinear, :82-95 */
+        if (elems && cons) {
+            double mu = rho * Vs * Vs, lambda;                                               /* mu_and_lambda, psolve.c:3236-3272 */
+            if (Vp > (Vs * threshold_vpvs)) lambda = rho * Vs * Vs * threshold_vpvs * threshold_vpvs - 2 * mu;
+            else lambda = rho * Vp * Vp - 2 * mu;
+            if (lambda < 0) {
+                if (Vs < 500) Vp = 2.45 * Vs;
+                else if (Vs < 1200) Vp = 2 * Vs;
+                else Vp = 1.87 * Vs;
+                lambda = rho * Vp * Vp;
+            }
+            if (lambda < 0) return HQ_ERR_ARG;
+            const double vs = (double)Vs;
+            double alpha = 0, k;
+            if (properties == HQH_NL_ALPHAKAY) {                                             /* get_alpha / get_kay, :142-191 */
+                if (model == HQ_NL_DRUCKERPRAGER) alpha = nl_interpolate(nrows, props, 1, vs);
+                k = nl_interpolate(nrows, props, 2, vs);
+            } else {
+                const double phi = nl_interpolate(nrows, props, 2, vs) * PI / 180.0;
+                const double c = nl_interpolate(nrows, props, 1, vs);
+                if (model == HQ_NL_DRUCKERPRAGER) alpha = 2 * sin(phi) / (sqrt(3.0) * (3 - sin(phi)));
+                k = 6 * c * cos(phi) / (sqrt(3.0) * (3 - sin(phi)));
+            }
+            double* q = cons + 6 * (int64_t)n;
+            q[0] = (double)h; q[1] = mu; q[2] = lambda; q[3] = alpha; q[4] = k;
+            q[5] = nl_interpolate(nrows, props, 5, vs);
+            elems[n] = e;
+        }
+        n++;
+    }
+    *nelems = n;
+    return HQ_OK;
+}
+
+static int nl_check(int32_t nelems, const int32_t* lnid, const double* cons, int32_t nnodes, const double* u, const void* a, const void* b)
+{
+    if (nelems < 0 || nnodes < 0) return HQ_ERR_ARG;
+    if (nelems == 0) return HQ_OK;
+    if (!lnid || !cons || !u || !a || !b) return HQ_ERR_ARG;
+    for (int64_t i = 0; i < 8 * (int64_t)nelems; i++)
+        if (lnid[i] < 0 || lnid[i] >= nnodes) return HQ_ERR_ARG;
+    return HQ_OK;
+}
+
+int hqh_nonlinear_advance(int32_t nelems, const int32_t* lnid, const double* cons, int32_t nnodes, const double* u1, double dt,
+                          double* pstrain, double* ep, double* ef)
+{
+    int rc = nl_check(nelems, lnid, cons, nnodes, u1, pstrain, ep);
+    if (rc != HQ_OK || nelems == 0) return rc;
+    const double dt2 = dt * dt;
+    for (int32_t e = 0; e < nelems; e++) {
+        double u[24], st[HQ_NL_NSTATE * 8], f[24];
+        for (int i = 0; i < 8; i++)
+            for (int d = 0; d < 3; d++) u[3 * i + d] = u1[3 * (int64_t)lnid[8 * (int64_t)e + i] + d];
+        for (int j = 0; j < 8; j++) {
+            for (int c = 0; c < 6; c++) st[c * 8 + j] = pstrain[(8 * (int64_t)e + j) * 6 + c];
+            st[6 * 8 + j] = ep[8 * (int64_t)e + j];
+        }
+        hq_nl_element(u, cons + 6 * (int64_t)e, 1, dt2, st, 1, f);
+        for (int j = 0; j < 8; j++) {
+            for (int c = 0; c < 6; c++) pstrain[(8 * (int64_t)e + j) * 6 + c] = st[c * 8 + j];
+            ep[8 * (int64_t)e + j] = st[6 * 8 + j];
+        }
+        if (ef) memcpy(ef + 24 * (int64_t)e, f, sizeof f);
+    }
+    return HQ_OK;
+}
+
+int hqh_nonlinear_force(int32_t nelems, const double* cons, double dt, const double* pstrain, double* ef)
+{
+    if (nelems < 0) return HQ_ERR_ARG;
+    if (nelems == 0) return HQ_OK;
+    if (!cons || !pstrain || !ef) return HQ_ERR_ARG;
+    const double dt2 = dt * dt;
+    for (int32_t e = 0; e < nelems; e++) {
+        const double* q = cons + 6 * (int64_t)e;
+        const double h = q[0], jij = 0.25 / h, h3 = h * h * h, wj = h3 * 0.125;
+        double* f = ef + 24 * (int64_t)e;
+        for (int i = 0; i < 24; i++) f[i] = 0.0;
+        for (int j = 0; j < 8; j++) hq_nl_point_force(j, jij, wj, q[1], q[2], pstrain + (8 * (int64_t)e + j) * 6, f);
+        for (int i = 0; i < 24; i++) f[i] = f[i] * dt2;
+    }
     return HQ_OK;
 }
 

@@ -19,7 +19,7 @@ EXPORTS = ["hqh_box_create", "hqh_box_destroy", "hqh_box_get_info", "hqh_box_des
            "hqh_solver_run_on", "hqh_solver_run_async", "hqh_checkpoint_write_fields", "hqh_wavefield_write_block",
            "hqh_checkpoint_write", "hqh_checkpoint_read", "hqh_station_format", "hqh_station_format_derivs",
            "hqh_gradient_weights", "hqh_station_gradients", "hqh_station_moduli", "hqh_deform_fold",
-           "hqh_station_kinematics", "hqh_peak_fold", "hqh_atten_class_coef", "hqh_atten_advance", "hqh_atten_advance_delta", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
+           "hqh_station_kinematics", "hqh_peak_fold", "hqh_atten_class_coef", "hqh_atten_advance", "hqh_atten_advance_delta", "hqh_nonlinear_constants", "hqh_nonlinear_advance", "hqh_nonlinear_force", "hqh_cum_fold", "hqh_husid_cross", "hqh_sdof_coef", "hqh_spec_fold", "hqh_station_header", "hqh_wavefield_create", "hqh_wavefield_write",
            "hqh_octbox_create", "hqh_octbox_destroy", "hqh_octbox_desc", "hqh_octbox_view",
            "hqh_cvm_open", "hqh_cvm_close", "hqh_cvm_info", "hqh_cvm_query", "hqh_cvm_grid"]
 
@@ -905,6 +905,58 @@ def atten_advance(slot_node, slot_class, k, u1, u2, mv, w=None, delta=False):
     capi._check(fn(ctypes.c_int32(ns), ptr(slot_node), ptr(slot_class), ctypes.c_int32(len(k)), ptr(k),
                    ctypes.c_int32(len(u1)), ptr(u1), ptr(u2), ptr(mv), ptr(w)))
     return mv, w
+
+
+NL_ALPHAKAY, NL_COHEFRICTION = 0, 1                                  # include/hq_host.h
+
+
+def nonlinear_constants(edata, model, props, vs_min, vs_cut, properties=NL_ALPHAKAY, threshold_vpvs=3.0):
+    """hqh_nonlinear_constants: edata [E, 4] float32 (edgesize, Vp, Vs, rho, as the mesh holds them after solver_init) and the
+    property table props [rows, 6] (Vs limit, alpha | cohesion, k | friction angle, strain rate, sensitivity, hardening
+    modulus) -> (elems [n] int32, cons [n, 6]) of the elements with vs_min <= Vs <= vs_cut: Solver.set_nonlinear's arguments."""
+    edata = np.ascontiguousarray(edata, np.float32)
+    props = np.ascontiguousarray(props, np.float64).reshape(-1, 6)
+    if edata.ndim != 2 or edata.shape[1] != 4:
+        raise capi.HqError("nonlinear_constants: edata %r is not [E, 4]" % (edata.shape,))
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data if a is not None and a.size else None)
+    n = ctypes.c_int32()
+    args = [ctypes.c_int32(len(edata)), ptr(edata), ctypes.c_double(threshold_vpvs), ctypes.c_int32(int(model)),
+            ctypes.c_int32(int(properties)), ctypes.c_int32(len(props)), ptr(props), ctypes.c_double(vs_min), ctypes.c_double(vs_cut)]
+    capi._check(load_library().hqh_nonlinear_constants(*args, None, None, ctypes.byref(n)))
+    elems, cons = np.zeros(n.value, np.int32), np.zeros((n.value, 6))
+    if n.value:
+        capi._check(load_library().hqh_nonlinear_constants(*args, ptr(elems), ptr(cons), ctypes.byref(n)))
+    return elems, cons
+
+
+def nonlinear_advance(lnid, cons, u1, dt, pstrain, ep):
+    """hqh_nonlinear_advance: one step of the plastic state of the elements lnid [n, 8] (node ids into u1 [N, 3] = u(t)) with
+    cons [n, 6]; pstrain [n, 8, 6] and ep [n, 8] are advanced IN PLACE (float64, C-contiguous).  Returns ef [n, 8, 3], the
+    corner forces of the correction from the state as it stood before the update."""
+    lnid = np.ascontiguousarray(lnid, np.int32).reshape(-1, 8)
+    cons = np.ascontiguousarray(cons, np.float64).reshape(-1, 6)
+    u1 = np.ascontiguousarray(u1, np.float64)
+    n = len(lnid)
+    if (len(cons) != n or pstrain.dtype != np.float64 or ep.dtype != np.float64 or pstrain.shape != (n, 8, 6) or ep.shape != (n, 8)
+            or not pstrain.flags.c_contiguous or not ep.flags.c_contiguous or u1.ndim != 2 or u1.shape[1] != 3):
+        raise capi.HqError("nonlinear_advance: pstrain / ep / cons are not the state of %d elements" % n)
+    ef = np.zeros((n, 8, 3))
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)
+    capi._check(load_library().hqh_nonlinear_advance(ctypes.c_int32(n), ptr(lnid), ptr(cons), ctypes.c_int32(len(u1)), ptr(u1),
+                                                     ctypes.c_double(dt), ptr(pstrain), ptr(ep), ptr(ef)))
+    return ef
+
+
+def nonlinear_force(cons, dt, pstrain):
+    """hqh_nonlinear_force: ef [n, 8, 3], the corner forces of the correction of the state pstrain [n, 8, 6]."""
+    cons = np.ascontiguousarray(cons, np.float64).reshape(-1, 6)
+    pstrain = np.ascontiguousarray(pstrain, np.float64)
+    if pstrain.shape != (len(cons), 8, 6):
+        raise capi.HqError("nonlinear_force: pstrain %r is not [%d, 8, 6]" % (pstrain.shape, len(cons)))
+    ef = np.zeros((len(cons), 8, 3))
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else None)
+    capi._check(load_library().hqh_nonlinear_force(ctypes.c_int32(len(cons)), ptr(cons), ctypes.c_double(dt), ptr(pstrain), ptr(ef)))
+    return ef
 
 
 def cum_fold(steps, samples, quantities, threshold=0.0, sums=None, span=None):

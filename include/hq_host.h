@@ -349,6 +349,29 @@ HQ_API int hqh_cum_fold(int32_t npoints, int32_t quantities, int32_t nsamples, c
  * that is not finite or a mu < 0. */
 HQ_API int hqh_deform_fold(int32_t npoints, int32_t quantities, const double* lame, int32_t nsamples, const int32_t* steps,
                            const double* gsamples, double* vals, int32_t* when);
+/* Nonlinear soil on the host (csrc/hq_nonlin.h, the text hq_nonlinear_set's kernel compiles; include/hq_solver.h has the model).
+ * hqh_nonlinear_constants: the reference's set-up as numbers (nonlinear_solver_init, nonlinear.c:626-749).  edata [lenum][4] =
+ * edgesize, Vp, Vs, rho as the caller's mesh holds them AFTER solver_init (mu_and_lambda, psolve.c:3236-3272, rewrites Vp where
+ * lambda < 0, and nonlinear_solver_init calls it again on that Vp); threshold_vpvs = Param.theThresholdVpVs.  An element is
+ * nonlinear where vs_min <= Vs <= vs_cut (isThisElementNonLinear).  props [nrows][6] = material_properties_list: Vs limit
+ * (rising), alpha or cohesion, k or the friction angle in degrees, strain rate, sensitivity, hardening modulus, interpolated in
+ * Vs as interpolate_property_value does (clamped outside the limits); `properties` says what columns 1 and 2 are
+ * (HQH_NL_ALPHAKAY, HQH_NL_COHEFRICTION: get_alpha / get_kay); `model` is HQ_NL_VONMISES (alpha = 0) or HQ_NL_DRUCKERPRAGER.
+ * *nelems = the number of nonlinear elements; elems [*nelems] (ascending) and cons [*nelems][6] = h, mu, lambda, alpha, k,
+ * hardening modulus are written where both are given -- call once with NULL to size them.  They are hq_nonlinear_desc's.
+ * hqh_nonlinear_advance: one step of compute_nonlinear_state over host arrays: lnid [nelems][8] node ids into u1 [nnodes][3]
+ * = u(t); pstrain [nelems][8][6] and ep [nelems][8] are advanced in place (hq_nonlinear_fetch's layout); ef (may be NULL)
+ * [nelems][8][3] takes the corner forces of the correction from the state as it stood BEFORE the update, dt^2 included.
+ * hqh_nonlinear_force: those corner forces alone, of a given state.
+ * HQ_ERR_ARG for null pointers (where there is something to read), negative counts, ids out of range, an unknown model or
+ * properties type, a property that is not finite, Vs limits that do not rise, an element whose lambda stays negative. */
+enum { HQH_NL_ALPHAKAY = 0, HQH_NL_COHEFRICTION = 1 };
+HQ_API int hqh_nonlinear_constants(int32_t lenum, const float* edata, double threshold_vpvs, int32_t model, int32_t properties,
+                                   int32_t nrows, const double* props, double vs_min, double vs_cut, int32_t* elems, double* cons,
+                                   int32_t* nelems);
+HQ_API int hqh_nonlinear_advance(int32_t nelems, const int32_t* lnid, const double* cons, int32_t nnodes, const double* u1, double dt,
+                                 double* pstrain, double* ep, double* ef);
+HQ_API int hqh_nonlinear_force(int32_t nelems, const double* cons, double dt, const double* pstrain, double* ef);
 /* Where Husid curves cross fractions of their totals (significant durations: D5-95 is the difference of the crossings of
  * 0.05 and 0.95, times dt).  curve [nslots][nseries] holds the running sum of every series as it stood at curve_steps[k]
  * (increasing) -- hq_cum_fetch's curve seen as [nfilled][np nq 3] -- and total [nseries] the final sums; (step0, 0) stands

@@ -856,6 +856,84 @@ HQ_API int hq_attenuation_split_table_faults(const hq_desc* desc, const int32_t*
                                              const int32_t* sd, int64_t nsd, int64_t* faults);
 
 /*
+ * Nonlinear soil (include_nonlinear_analysis = yes, plasticity_model = rate_independant: nonlinear.c) on a context of the PATCH
+ * variant: rate-independent von Mises and Drucker-Prager plasticity with linear hardening at the eight quadrature points of
+ * every nonlinear element, as a correction pass beside the unchanged step (csrc/hq_nonlin.h has the text, point by point;
+ * csrc/hq_nonlin_dev.h the plan and the kernel).  Double library, one context alone.
+ *
+ * In a nonlinear element the reference applies -dt^2 sum_qp B^T sigma(e - ep) h^3 / 8 instead of the stiffness force.
+ * point_stress is linear, so that is the elastic force the patch and brick kernels already apply plus
+ *     dF = +dt^2 h^3 / 8 sum_qp B^T sigma(ep),
+ * ep the plastic strain as it stood BEFORE this step's update (the reference's pstrains1).  Everything behind the force is
+ * linear in it, Rayleigh terms included, so the step is the unchanged step,
+ *     (patches, bricks)  ||  hq_k_nl_element -> hq_k_atten_node_sum              (a stream of its own)
+ * followed on the compute stream by
+ *     hq_k_distribute (dF's hanging nodes) -> hq_k_atten_apply_at (u_new += dF / n_t[0]) -> hq_k_adjust_assign (u_new),
+ * over the nonlinear elements and the nodes they touch only.  dF is summed per node through a host-built table in the
+ * caller's element order, without atomics: wherever the elastic step leaves identical bits, two runs do.
+ *
+ * desc: model HQ_NL_VONMISES or HQ_NL_DRUCKERPRAGER; elems [nelems], the nonlinear elements in the caller's numbering,
+ * strictly ascending (the reference's myNonlinElementsMapping); cons [nelems][6] = h (edgesize), mu, lambda, alpha, k, hardening
+ * modulus per element (hqh_nonlinear_constants derives them as nonlinear_solver_init does).
+ * State: ONE copy of the plastic strain (6 values: xx yy zz xy yz xz) and of the effective plastic strain per quadrature
+ * point, double -- 448 B per element where the reference keeps 1664 B (strains, stresses, two plastic strains, two ep).
+ *
+ * Two rules of the reference, and one deviation: an element whose eight nodes are all "zero" (every |component| <= 1e-20,
+ * get_displacements) is not advanced.  Where the plastic multiplier dLambda == 0 the state is KEPT AS IT IS: the reference
+ * adds 0 * dfds there, the same number wherever J2 > 0 but NaN where J2 == 0 (a rigid translation poisons its plastic
+ * strain); the library does not reproduce that NaN.
+ *
+ * hq_nonlinear_set: between steps; the state starts at 0; set again replaces plan and state; nelems == 0 is valid (the context
+ * then enqueues what it did before, and refuses what a nonlinear context refuses).  It refuses, the context left as it was:
+ * a scatter context, the float library, a context with nranks > 1, a linked group or any transport, a context with
+ * attenuation of either kind (all HQ_ERR_STATE); an unknown model, ids out of range or not strictly ascending, a constant
+ * that is not finite, h <= 0, mu < 0, k < 0, alpha != 0 under von Mises (all HQ_ERR_ARG).  On a nonlinear context
+ * hq_comm_init*, hq_group_link and hq_attenuation_set* refuse (HQ_ERR_STATE).
+ * hq_nonlinear_info: out = {nonlinear elements, touched nodes, device bytes added, 0}; all 0 without.
+ * hq_nonlinear_fetch / _load: pstrain [nelems][8][6] and ep [nelems][8] in the caller's element order and the reference's
+ * quadrature order (point j at xi[.][j] qc); fetch leaves out an array passed as NULL, load needs both and refuses a value
+ * that is not finite (HQ_ERR_ARG).  hq_upload zeroes the state, as the reference's restart does (calloc, nonlinear.c:651-664);
+ * an exact restart is hq_upload followed by hq_nonlinear_load.
+ * hq_nonlinear_clear: the added bytes go; the context steps as it did before.
+ * Device bytes added, exactly (hq_info.device_bytes grows by it); 0 for nelems == 0, else with Enlpad = nelems rounded up to 64,
+ * T = touched nodes (the nodes of the nonlinear elements and the anchors of the hanging ones among them), A = distinct anchors
+ * and H = (hanging node, anchor) pairs of the touched hanging nodes:
+ *     448 Enlpad            (state, double [7][8][Enlpad])
+ *   + 192 Enlpad            (corner forces, double [3][8][Enlpad])
+ *   +  48 Enlpad + 32 Enlpad (constants [6][Enlpad], node ids [8][Enlpad])
+ *   +   4 (T + 1) + 32 nelems (the node -> (element, corner) table)
+ *   +  36 T                 (dF [T][3], the mass n_t[n][0], the node id)
+ *   +   8 A + 4 + 8 H       (dF's distribution tables; nothing where no touched node hangs)
+ * hq_nonlinear_plan_check: host only -- report = {nonlinear elements, touched nodes, the bytes above, faults}: the touched-node
+ * list (ascending, every corner under its own node, every listed node needed), the touched hanging nodes against the mesh's
+ * table, and hq_attenuation_split_plan_check's counts on the tables.  hq_nonlinear_plan_tables hands out the tables in the
+ * numbering hq_create gives `desc` (counts = {T, T + 1, 8 nelems, H}; tnode [T], epos [nelems], nptr, nent, sd [H][3] on
+ * touched-node indices; a NULL array is left out) and hq_nonlinear_table_faults counts the faults of tables given to it.
+ * Not here: rate-dependent plasticity (compute_dLambdaII's pow branch); geostatic loading, gravity and bottom reactions;
+ * nonlinear station files and yield statistics; the scatter variant, the float library, partitions and the reference-link
+ * stub.
+ */
+#ifndef HQ_NL_MODELS
+#define HQ_NL_MODELS
+enum { HQ_NL_VONMISES = 1, HQ_NL_DRUCKERPRAGER = 2 };
+#endif
+typedef struct {
+    int32_t model, nelems;
+    const int32_t* elems;            /* nonlinear elements, caller's numbering, strictly ascending */
+    const double* cons;              /* [nelems][6] h, mu, lambda, alpha, k, hardening modulus     */
+} hq_nonlinear_desc;
+HQ_API int hq_nonlinear_set(hq_ctx* ctx, const hq_nonlinear_desc* desc);
+HQ_API int hq_nonlinear_info(hq_ctx* ctx, int64_t out[4]);
+HQ_API int hq_nonlinear_fetch(hq_ctx* ctx, double* pstrain, double* ep);
+HQ_API int hq_nonlinear_load(hq_ctx* ctx, const double* pstrain, const double* ep);
+HQ_API int hq_nonlinear_clear(hq_ctx* ctx);
+HQ_API int hq_nonlinear_plan_check(const hq_desc* desc, const hq_nonlinear_desc* nl, int64_t report[4]);
+HQ_API int hq_nonlinear_plan_tables(const hq_desc* desc, const hq_nonlinear_desc* nl, int32_t* tnode, int32_t* epos, int32_t* nptr,
+                                    int32_t* nent, int32_t* sd, int64_t counts[4]);
+HQ_API int hq_nonlinear_table_faults(const hq_desc* desc, const hq_nonlinear_desc* nl, const int32_t* tnode, const int32_t* epos,
+                                     const int32_t* nptr, const int32_t* nent, const int32_t* sd, int64_t nsd, int64_t* faults);
+
+/*
  * Single phases, for per-function parity tests against the reference loops
  * (scatter variant only; the patch variant fuses them):
  *   hq_phase_force : force += stiffness + damping element forces of the
