@@ -30,7 +30,7 @@ def _newer(target, sources):
 def _build_solver(lib, defines, force):
     srcs = [os.path.join(CSRC, f) for f in ("hq_engine.hip", "hq_devmem.h", "hq_kernels.h", "hq_opts.h", "hq_patch.h",
                                            "hq_brick.h", "hq_prepare.h", "hq_plan_check.h", "hq_cadence.h", "hq_peak.h", "hq_cumul.h", "hq_deform.h", "hq_sample.h", "hq_sdof.h",
-                                           "hq_outputs.h", "hq_state_table.h", "hq_atten.h", "hq_atten_plan.h", "hq_atten_split.h", "hq_nonlin.h", "hq_nonlin_dev.h")]
+                                           "hq_outputs.h", "hq_state_table.h", "hq_atten.h", "hq_atten_plan.h", "hq_correction.h", "hq_atten_split.h", "hq_nonlin.h", "hq_nonlin_dev.h")]
     srcs.append(os.path.join(ROOT, "include", "hq_solver.h"))
     if force or _newer(lib, srcs):
         cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared"] + defines + \

@@ -109,7 +109,68 @@ static int hq_rccl_load(void)
         if (r_ != ncclSuccess) return hq_fail(HQ_ERR_COMM, "%s: %s", #call, g_rccl.GetErrorString(r_)); \
     } while (0)
 
+static inline unsigned hq_blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+
+/*
+ * compute_adjust DISTRIBUTION (psolve.c:5942-5987) without atomics and in ONE summation order: the entries are
+ * grouped by the anchor they add to (CSR, host-built), inside an anchor in the order of the reference's loop --
+ * hanging nodes in table order, their anchors in list order -- so an anchor several hanging nodes hang on gets its
+ * parts in the same order on every run.  Anchors are never hanging nodes themselves (hq_create refuses that), so no
+ * row is read and written in the same launch.  ids: node ids (scatter variant, force table), interface slots or the
+ * rows of a correction pass.
+ */
+__global__ void hq_k_distribute(int32_t ndst, const int32_t* __restrict__ dst, const int32_t* __restrict__ ptr,
+                                const int32_t* __restrict__ src, const int32_t* __restrict__ deps, double* __restrict__ table)
+{
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ndst * 3) return;
+    int k = t / 3, d = t - 3 * k;
+    double* p = &table[3 * (int64_t)dst[k] + d];
+    double v = *p;
+    for (int32_t q = ptr[k]; q < ptr[k + 1]; q++) v += table[3 * (int64_t)src[q] + d] / (double)(uint32_t)deps[q];
+    *p = v;
+}
+
+/* hq_k_distribute's tables, grouped by the anchor (destination) the entries add to, and their launch: the shared hanging nodes
+ * of the patch variant on the interface table (slots), all hanging nodes of the scatter variant on the force table (nodes),
+ * the hanging nodes of a correction pass on its dF (hq_correction.h) */
+struct hq_distribution {
+    int32_t n = 0;                    /* destinations (anchors)                              */
+    hq_dbuf<int32_t> d_dst;           /* [n]                                                 */
+    hq_dbuf<int32_t> d_ptr;           /* [n + 1]                                             */
+    hq_dbuf<int32_t> d_src;           /* [entries] hanging node (slot / id)                  */
+    hq_dbuf<int32_t> d_deps;          /* [entries] its number of anchors                     */
+    int64_t bytes() const { return (int64_t)(d_dst.bytes() + d_ptr.bytes() + d_src.bytes() + d_deps.bytes()); }
+    /* {src, dst, deps} triples in the reference's loop order; inside an anchor the entries keep that order.  The tables are
+     * counted in *ledger (NULL: uncounted); no triples: n = 0 and nothing is allocated */
+    int build(const std::vector<int32_t>& sd, int64_t* ledger, hipStream_t st)
+    {
+        const size_t cnt = sd.size() / 3;
+        *this = hq_distribution();
+        if (!cnt) return HQ_OK;
+        std::vector<int32_t> order(cnt);
+        for (size_t i = 0; i < cnt; i++) order[i] = (int32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return sd[3 * (size_t)a + 1] < sd[3 * (size_t)b + 1]; });
+        std::vector<int32_t> dst, ptr(1, 0), src, deps;
+        for (size_t k = 0; k < cnt; k++) {
+            const size_t i = (size_t)order[k];
+            if (dst.empty() || dst.back() != sd[3 * i + 1]) { if (!dst.empty()) ptr.push_back((int32_t)src.size()); dst.push_back(sd[3 * i + 1]); }
+            src.push_back(sd[3 * i]); deps.push_back(sd[3 * i + 2]);
+        }
+        ptr.push_back((int32_t)src.size());
+        HQ_TRY(d_dst.put(ledger, dst, st)); HQ_TRY(d_ptr.put(ledger, ptr, st));
+        HQ_TRY(d_src.put(ledger, src, st)); HQ_TRY(d_deps.put(ledger, deps, st));
+        n = (int32_t)dst.size();
+        return HQ_OK;
+    }
+    void launch(double* table, hipStream_t st) const
+    {
+        if (n) hq_k_distribute<<<hq_blocks(n * 3, 256), 256, 0, st>>>(n, d_dst, d_ptr, d_src, d_deps, table);
+    }
+};
+
 #include "hq_atten_plan.h"
+#include "hq_correction.h"
 #include "hq_atten_split.h"
 #include "hq_nonlin_dev.h"
 
@@ -119,19 +180,13 @@ static int hq_rccl_load(void)
 
 /* BKT attenuation of a scatter context (hq_attenuation_set; hq_atten.h, hq_atten_plan.h): the slot plan and the state on the
  * device, the plan's corner table on the host for fetch / load in the reference's per-corner layout.  split: of a patch
- * context (hq_attenuation_set_split; hq_atten_split.h) -- d_w then holds the delta vectors, and the tables below exist */
+ * context (hq_attenuation_set_split; hq_atten_split.h) -- d_w then holds the delta vectors, and c1 / c2 and the correction
+ * pass exist */
 struct hq_atten_dev {
     bool on = false, split = false;
     int32_t nclasses = 0, nslots = 0;
-    int64_t bytes = 0;               /* the device bytes of everything below (the header's formulas)   */
-    hq_dbuf<double> d_ef;            /* [3][8][Epad] corner forces of this step                         */
-    hq_dbuf<double> d_dF;            /* [N][3] their sums per node                                      */
-    hq_dbuf<double> d_mass;          /* [N] n_t[n][0], device numbering                                 */
-    hq_dbuf<double> d_c1, d_c2;      /* [E]                                                             */
-    hq_dbuf<int32_t> d_nptr, d_nent; /* [N + 1], [8 E] node -> (element, corner), element order         */
-    int32_t nSD = 0;                 /* hq_k_distribute's tables over ALL hanging nodes, on node ids    */
-    hq_dbuf<int32_t> d_sd_dst, d_sd_ptr, d_sd_src, d_sd_deps;
-    int64_t nanchors = 0, npairs = 0;
+    int32_t Epad = 0;                /* the stride of eslot (split: of the correction pass as well)    */
+    int64_t bytes = 0;               /* the device bytes of everything below (the headers' formulas)   */
     hq_dbuf<int32_t> d_eslot;        /* [8][Epad]                                          */
     hq_dbuf<int32_t> d_slot_node;    /* [nslots]                                           */
     hq_dbuf<int32_t> d_slot_class;   /* [nslots]                                           */
@@ -139,25 +194,21 @@ struct hq_atten_dev {
     hq_dbuf<double> d_mv;            /* [HQ_ATTEN_NSTATE][nslots] memory variables         */
     hq_dbuf<double> d_w;             /* [HQ_ATTEN_NW][nslots] damping vectors of this step */
     std::vector<int32_t> h_eslot, h_slot_node;
+    hq_dbuf<double> d_c1, d_c2;      /* split: [E], the correction's element order         */
+    hq_correction corr;              /* split: over all E elements and all N nodes         */
 };
 
-/* Nonlinear soil of a patch context (hq_nonlinear_set; hq_nonlin.h, hq_nonlin_dev.h): state, constants and tables on the
- * device over the nonlinear elements and the nodes they touch; the place of every element of the caller's list on the host,
- * for fetch / load in the caller's order */
+/* Nonlinear soil of a patch context (hq_nonlinear_set; hq_nonlin.h, hq_nonlin_dev.h): state, constants and node ids on the
+ * device over the nonlinear elements, the correction pass over them and the nodes they touch; the place of every element of
+ * the caller's list on the host, for fetch / load in the caller's order */
 struct hq_nl_dev {
     bool on = false;
     int32_t model = 0, nel = 0, Enlpad = 0, nt = 0;
     int64_t bytes = 0;               /* hq_nl_bytes */
     hq_dbuf<double> d_st;            /* [7][8][Enlpad] plastic strain (6) and effective plastic strain per point */
-    hq_dbuf<double> d_ef;            /* [3][8][Enlpad] corner forces of this step                                 */
     hq_dbuf<double> d_cons;          /* [6][Enlpad]                                                               */
     hq_dbuf<int32_t> d_lnid;         /* [8][Enlpad] device node ids                                               */
-    hq_dbuf<int32_t> d_nptr, d_nent; /* [nt + 1], [8 nel] touched node -> (element, corner)                       */
-    hq_dbuf<double> d_dF;            /* [nt][3]                                                                   */
-    hq_dbuf<double> d_mass;          /* [nt]                                                                      */
-    hq_dbuf<int32_t> d_tnode;        /* [nt] device node ids                                                      */
-    int32_t nSD = 0;
-    hq_dbuf<int32_t> d_sd_dst, d_sd_ptr, d_sd_src, d_sd_deps;
+    hq_correction corr;              /* over the nel elements and the nt touched nodes, listed in corr.d_tnode    */
     std::vector<int32_t> h_epos;     /* [nel] */
 };
 
@@ -268,13 +319,9 @@ struct hq_ctx {
     hq_dbuf<int32_t> d_oi_ptr;        /* [nOI+1] CSR: records of an.d_s_in to add, in       */
     hq_dbuf<int32_t> d_oi_pos;        /*         messenger order (fixed summation order)    */
     hq_dbuf<int32_t> d_oi_fc;         /* [nOI] first record | number of records << 24       */
-    /* compute_adjust DISTRIBUTION grouped by destination (hq_k_distribute): the shared hanging nodes of the patch
-     * variant on the interface table (slots), all hanging nodes of the scatter variant on the force table (nodes) */
-    int32_t  nSD = 0;                 /* destinations (anchors)                              */
-    hq_dbuf<int32_t> d_sd_dst;        /* [nSD]                                               */
-    hq_dbuf<int32_t> d_sd_ptr;        /* [nSD + 1]                                           */
-    hq_dbuf<int32_t> d_sd_src;        /* [entries] hanging node (slot / id)                  */
-    hq_dbuf<int32_t> d_sd_deps;       /* [entries] its number of anchors                     */
+    /* compute_adjust DISTRIBUTION: the shared hanging nodes of the patch variant on the interface table (slots), all
+     * hanging nodes of the scatter variant on the force table (nodes) */
+    hq_distribution dist;
     /* patch variant */
     hq_patch_plan plan;
     /* bricks (hq_brick.h): the device numbers the nodes its own way -- tile columns first -- and every entry point
@@ -504,25 +551,6 @@ hq_k_update(int64_t n3, const double* __restrict__ nt, const hq_real* __restrict
     force[t] = 0.0;
 }
 
-/*
- * compute_adjust DISTRIBUTION (psolve.c:5942-5987) without atomics and in ONE summation order: the entries are
- * grouped by the anchor they add to (CSR, host-built), inside an anchor in the order of the reference's loop --
- * hanging nodes in table order, their anchors in list order -- so an anchor several hanging nodes hang on gets its
- * parts in the same order on every run.  Anchors are never hanging nodes themselves (hq_create refuses that), so no
- * row is read and written in the same launch.  ids: node ids (scatter variant, force table) or interface slots.
- */
-__global__ void hq_k_distribute(int32_t ndst, const int32_t* __restrict__ dst, const int32_t* __restrict__ ptr,
-                                const int32_t* __restrict__ src, const int32_t* __restrict__ deps, double* __restrict__ table)
-{
-    int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ndst * 3) return;
-    int k = t / 3, d = t - 3 * k;
-    double* p = &table[3 * (int64_t)dst[k] + d];
-    double v = *p;
-    for (int32_t q = ptr[k]; q < ptr[k + 1]; q++) v += table[3 * (int64_t)src[q] + d] / (double)(uint32_t)deps[q];
-    *p = v;
-}
-
 /* compute_adjust ASSIGNMENT (psolve.c:5992-6035) */
 __global__ void hq_k_adjust_assign(int32_t ldnnum, const int32_t* __restrict__ dn_id,
                                    const int32_t* __restrict__ dn_ptr,
@@ -736,8 +764,6 @@ __global__ void hq_k_gather(int32_t n, const int32_t* __restrict__ ids,
 /* ------------------------------------------------------------------------ */
 /* helpers                                                                  */
 /* ------------------------------------------------------------------------ */
-
-static inline unsigned hq_blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 static int hq_build_schedule(hq_ctx* c, const hq_schedule* in, hq_dev_schedule* out)
 {
@@ -1282,86 +1308,79 @@ static bool hq_use_brick_stream(hq_ctx* c)
 #include "hq_outputs.h"
 
 /*
- * A split context's step (hq_atten_split.h).  Head: the delta advance and the correction force read u(t) and u(t - dt)
- * only, so they fork onto the attenuation stream behind everything the compute stream has seen so far -- the last step's
- * apply kernels, which read dF and wrote u(t) -- and run beside this step's patches and bricks.
+ * A correction pass in the step (hq_correction.h), and where its launches stand among the step's streams.
+ * Head (phase 0: fork, the pass's own element kernels, sum): it may read u(t) and u(t - dt), the pass's own state and nothing
+ * this step writes.  So it forks onto the correction stream behind everything the compute stream has seen so far -- the last
+ * step's join, which read dF and wrote what is now u(t) -- and runs beside this step's patches and bricks.
+ * Tail (phase 8: join): it adds to un, so it waits for every step kernel of this step -- the compute stream's own, which it
+ * follows in stream order, and the bricks' through their event where they run on a stream of their own -- and for the head.
+ * un is the buffer this step's head-of-step outputs read as u(t - 2 dt): the step kernels that wrote it waited for them
+ * (hq_outputs_enqueue), and the join's launches lie behind those kernels.  The next step's bricks read and overwrite what the
+ * join touches, and on their own stream they wait for ev_patches: it is recorded again behind the join (as behind the
+ * assignment of phase 6).
+ * HQ_ATTEN_SPLIT_INLINE (profiles/tools/atten_split_step.py): the whole chain ON the compute stream, to price the overlap.
  */
-static int hq_atten_split_head(hq_ctx* c)
+static int hq_correction_fork(hq_ctx* c, hipStream_t* as)
 {
-    const hq_atten_dev& A = c->att;
-#ifdef HQ_ATTEN_SPLIT_INLINE        /* profiles/tools/atten_split_step.py: the chain ON the compute stream, to price the overlap */
-    hipStream_t as = c->stream;
+#ifdef HQ_ATTEN_SPLIT_INLINE
+    *as = c->stream;
 #else
-    hipStream_t as = c->astream;
+    *as = c->astream;
     HQ_HIP(hipEventRecord(c->ev_att_fork, c->stream));
-    HQ_HIP(hipStreamWaitEvent(as, c->ev_att_fork, 0));
+    HQ_HIP(hipStreamWaitEvent(*as, c->ev_att_fork, 0));
 #endif
-    hq_k_atten_advance_delta<<<hq_blocks(A.nslots, 256), 256, 0, as>>>(
-        A.nslots, A.d_slot_node, A.d_slot_class, A.d_ktab, c->d_u[c->now], c->d_u[c->prev], A.d_mv, A.d_w);
-    hq_k_atten_corner_force<<<hq_blocks(c->E, 256), 256, 0, as>>>(c->E, c->Epad, A.nslots, A.d_eslot, A.d_c1, A.d_c2, A.d_w, A.d_ef);
-    hq_k_atten_node_sum<<<hq_blocks(c->N, 256), 256, 0, as>>>(c->N, c->Epad, A.d_nptr, A.d_nent, A.d_ef, A.d_dF);
+    return HQ_OK;
+}
+
+/* the end of the head: the corner forces the pass's kernels left in ef, summed per row */
+static int hq_correction_sum(hq_ctx* c, const hq_correction& K, hipStream_t as)
+{
+    hq_k_atten_node_sum<<<hq_blocks(K.rows, 256), 256, 0, as>>>(K.rows, K.stride, K.d_nptr, K.d_nent, K.d_ef, K.d_dF);
 #ifndef HQ_ATTEN_SPLIT_INLINE
     HQ_HIP(hipEventRecord(c->ev_att_done, as));
 #endif
     return HQ_OK;
 }
 
-/*
- * Tail: behind every step kernel of this step -- the compute stream's own, and the bricks' where they run on their stream --
- * and behind the head above: dF's hanging nodes to their anchors, un += dF / n_t[0], the hanging nodes of un assigned again.
- * un is the buffer this step's head-of-step outputs read as u(t - 2 dt): the step kernels that wrote it waited for them
- * (hq_outputs_enqueue), and these launches lie behind those kernels.
- */
-static int hq_atten_split_tail(hq_ctx* c, hq_real* un)
+/* dF's hanging nodes to their anchors, un += dF / n_t[0], the hanging nodes of un assigned again */
+static int hq_correction_join(hq_ctx* c, const hq_correction& K, hq_real* un)
 {
-    const hq_atten_dev& A = c->att;
+    if (!K.nelem) return HQ_OK;
     if (c->bstream) HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_bricks, 0));
 #ifndef HQ_ATTEN_SPLIT_INLINE
     HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_att_done, 0));
 #endif
-    if (A.nSD)
-        hq_k_distribute<<<hq_blocks(A.nSD * 3, 256), 256, 0, c->stream>>>(A.nSD, A.d_sd_dst, A.d_sd_ptr, A.d_sd_src, A.d_sd_deps, A.d_dF);
-    const int64_t n3 = 3 * (int64_t)c->N;
-    hq_k_atten_apply<<<hq_blocks(n3, 256), 256, 0, c->stream>>>(n3, A.d_mass, A.d_dF, un);
+    K.dist.launch(K.d_dF, c->stream);
+    const int64_t n3 = 3 * (int64_t)K.rows;
+    if (K.d_tnode) hq_k_atten_apply_at<<<hq_blocks(n3, 256), 256, 0, c->stream>>>(n3, K.d_tnode, K.d_mass, K.d_dF, un);
+    else hq_k_atten_apply<<<hq_blocks(n3, 256), 256, 0, c->stream>>>(n3, K.d_mass, K.d_dF, un);
     if (c->ldnnum)
         hq_k_adjust_assign<<<hq_blocks(c->ldnnum * 3, 256), 256, 0, c->stream>>>(c->ldnnum, c->d_dn_id, c->d_dn_ptr, c->d_dn_anchor, un);
-    /* the next step's bricks, on their own stream, read and overwrite what these launches touch: the event they wait for
-     * must lie behind them (as behind the assignment of phase 6) */
     if (c->bstream) HQ_HIP(hipEventRecord(c->ev_patches, c->stream));
     return HQ_OK;
 }
 
-/*
- * A nonlinear context's step (hq_nonlin_dev.h), the split pass's shape: the element kernel and the node sum read u(t) only
- * and fork onto the correction stream; distribution, apply and assignment follow every step kernel on the compute stream.
- */
+/* a split context's head (hq_atten_split.h): the delta advance and the corner force */
+static int hq_atten_split_head(hq_ctx* c)
+{
+    const hq_atten_dev& A = c->att;
+    hipStream_t as;
+    HQ_TRY(hq_correction_fork(c, &as));
+    hq_k_atten_advance_delta<<<hq_blocks(A.nslots, 256), 256, 0, as>>>(
+        A.nslots, A.d_slot_node, A.d_slot_class, A.d_ktab, c->d_u[c->now], c->d_u[c->prev], A.d_mv, A.d_w);
+    hq_k_atten_corner_force<<<hq_blocks(c->E, 256), 256, 0, as>>>(c->E, A.Epad, A.nslots, A.d_eslot, A.d_c1, A.d_c2, A.d_w, A.corr.d_ef);
+    return hq_correction_sum(c, A.corr, as);
+}
+
+/* a nonlinear context's head (hq_nonlin_dev.h): the element kernel; nothing without elements */
 static int hq_nl_head(hq_ctx* c)
 {
     const hq_nl_dev& L = c->nl;
     if (!L.nel) return HQ_OK;
-    hipStream_t as = c->astream;
-    HQ_HIP(hipEventRecord(c->ev_att_fork, c->stream));
-    HQ_HIP(hipStreamWaitEvent(as, c->ev_att_fork, 0));
-    hq_k_nl_element<<<hq_blocks(L.nel, 256), 256, 0, as>>>(L.nel, L.Enlpad, L.d_lnid, L.d_cons, c->d_u[c->now], c->dt2, L.d_st, L.d_ef);
-    hq_k_atten_node_sum<<<hq_blocks(L.nt, 256), 256, 0, as>>>(L.nt, L.Enlpad, L.d_nptr, L.d_nent, L.d_ef, L.d_dF);
-    HQ_HIP(hipEventRecord(c->ev_att_done, as));
-    return HQ_OK;
-}
-
-static int hq_nl_tail(hq_ctx* c, hq_real* un)
-{
-    const hq_nl_dev& L = c->nl;
-    if (!L.nel) return HQ_OK;
-    if (c->bstream) HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_bricks, 0));
-    HQ_HIP(hipStreamWaitEvent(c->stream, c->ev_att_done, 0));
-    if (L.nSD)
-        hq_k_distribute<<<hq_blocks(L.nSD * 3, 256), 256, 0, c->stream>>>(L.nSD, L.d_sd_dst, L.d_sd_ptr, L.d_sd_src, L.d_sd_deps, L.d_dF);
-    const int64_t n3 = 3 * (int64_t)L.nt;
-    hq_k_atten_apply_at<<<hq_blocks(n3, 256), 256, 0, c->stream>>>(n3, L.d_tnode, L.d_mass, L.d_dF, un);
-    if (c->ldnnum)
-        hq_k_adjust_assign<<<hq_blocks(c->ldnnum * 3, 256), 256, 0, c->stream>>>(c->ldnnum, c->d_dn_id, c->d_dn_ptr, c->d_dn_anchor, un);
-    if (c->bstream) HQ_HIP(hipEventRecord(c->ev_patches, c->stream));     /* (as hq_atten_split_tail's) */
-    return HQ_OK;
+    hipStream_t as;
+    HQ_TRY(hq_correction_fork(c, &as));
+    hq_k_nl_element<<<hq_blocks(L.nel, 256), 256, 0, as>>>(L.nel, L.Enlpad, L.d_lnid, L.d_cons, c->d_u[c->now], c->dt2, L.d_st, L.corr.d_ef);
+    return hq_correction_sum(c, L.corr, as);
 }
 
 static int hq_phase(hq_ctx* c, int ph)
@@ -1467,12 +1486,9 @@ static int hq_phase(hq_ctx* c, int ph)
         HQ_TRY(hq_xchg_recv(c, &c->dn, ftab, true, true));
         if (patch) {
             /* hanging nodes nobody shares were distributed inside the patches; the shared ones here */
-            if (c->nSD)
-                hq_k_distribute<<<hq_blocks(c->nSD * 3, 256), 256, 0, c->overlap ? c->cstream : c->stream>>>(
-                    c->nSD, c->d_sd_dst, c->d_sd_ptr, c->d_sd_src, c->d_sd_deps, c->d_iforce);
-        } else if (c->nSD) {                                               /* :4299 */
-            hq_k_distribute<<<hq_blocks(c->nSD * 3, 256), 256, 0, c->stream>>>(
-                c->nSD, c->d_sd_dst, c->d_sd_ptr, c->d_sd_src, c->d_sd_deps, c->d_force);
+            c->dist.launch(c->d_iforce, c->overlap ? c->cstream : c->stream);
+        } else {                                                           /* :4299 */
+            c->dist.launch(c->d_force, c->stream);
         }
         return HQ_OK;
     case 3: return hq_xchg_send(c, &c->an, ftab, true, true);                        /* :4301 */
@@ -1555,8 +1571,8 @@ static int hq_phase(hq_ctx* c, int ph)
     case 8:
         HQ_TRY(hq_xchg_recv(c, &c->dn, unew, false, false));
         if (patch) {
-            if (c->att.split) HQ_TRY(hq_atten_split_tail(c, unew));
-            if (c->nl.on) HQ_TRY(hq_nl_tail(c, unew));
+            if (c->att.split) HQ_TRY(hq_correction_join(c, c->att.corr, unew));
+            if (c->nl.on) HQ_TRY(hq_correction_join(c, c->nl.corr, unew));
             if (c->overlap) HQ_HIP(hipEventRecord(c->ev_shared, c->cstream));
             if (hq_has_transport(c)) hq_clock(c, hq_ctx::HQ_CLK_CHAIN1, c->overlap ? c->cstream : c->stream);
             int n = c->now, p = c->prev, sp = c->spare;
@@ -1587,28 +1603,6 @@ static int hq_step(hq_ctx* c)
  * contribution exchange adds the neighbours' partials to the owner's slot, the
  * owner updates the node (hq_k_interface_update) and shares the result.
  */
-/* {src, dst, deps} entries in the reference's loop order -> the tables of hq_k_distribute */
-static int hq_build_distribution(hq_ctx* c, const std::vector<int32_t>& sd)
-{
-    const size_t n = sd.size() / 3;
-    c->nSD = 0;
-    if (!n) return HQ_OK;
-    std::vector<int32_t> order(n);
-    for (size_t i = 0; i < n; i++) order[i] = (int32_t)i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return sd[3 * (size_t)a + 1] < sd[3 * (size_t)b + 1]; });
-    std::vector<int32_t> dst, ptr(1, 0), src, deps;
-    for (size_t k = 0; k < n; k++) {
-        const size_t i = (size_t)order[k];
-        if (dst.empty() || dst.back() != sd[3 * i + 1]) { if (!dst.empty()) ptr.push_back((int32_t)src.size()); dst.push_back(sd[3 * i + 1]); }
-        src.push_back(sd[3 * i]); deps.push_back(sd[3 * i + 2]);
-    }
-    ptr.push_back((int32_t)src.size());
-    HQ_TRY(c->d_sd_dst.put(&c->bytes, dst, c->stream)); HQ_TRY(c->d_sd_ptr.put(&c->bytes, ptr, c->stream));
-    HQ_TRY(c->d_sd_src.put(&c->bytes, src, c->stream)); HQ_TRY(c->d_sd_deps.put(&c->bytes, deps, c->stream));
-    c->nSD = (int32_t)dst.size();
-    return HQ_OK;
-}
-
 static int hq_setup_interface(hq_ctx* c, const hq_desc* d)
 {
     if (c->an.ctotal == 0 && c->an.stotal == 0 && c->dn.ctotal == 0 && c->dn.stotal == 0) return HQ_OK;
@@ -1669,7 +1663,7 @@ static int hq_setup_interface(hq_ctx* c, const hq_desc* d)
     HQ_TRY(slots(an_ss, c->an.d_sslot, &c->an.d_smap_f));
     HQ_TRY(slots(dn_cs, c->dn.d_cslot, &c->dn.d_cmap_f));
     HQ_TRY(slots(dn_ss, c->dn.d_sslot, &c->dn.d_smap_f));
-    HQ_TRY(hq_build_distribution(c, sd));
+    HQ_TRY(c->dist.build(sd, &c->bytes, c->stream));
     if (c->nOI) {
         /* records of the anchored-node contribution receive buffer per owned interface node,
          * messenger order */
@@ -1926,7 +1920,7 @@ static int hq_create_impl(const hq_desc* d, int device, const hq_options& opts, 
                 for (int32_t a = d->dn_ptr[k]; a < d->dn_ptr[k + 1]; a++) {
                     sd.push_back(d->dn_ldnid[k]); sd.push_back(d->dn_lanid[a]); sd.push_back(d->dn_ptr[k + 1] - d->dn_ptr[k]);
                 }
-            if ((rc = hq_build_distribution(c, sd)) != HQ_OK) return bail(rc);
+            if ((rc = c->dist.build(sd, &c->bytes, c->stream)) != HQ_OK) return bail(rc);
         }
     } else {
         c->plan.ragged_default = true;
@@ -2792,6 +2786,37 @@ extern "C" int hq_upload(hq_ctx* c, const hq_real* tm1, const hq_real* tm2, int3
 /* BKT attenuation (hq_atten.h, hq_atten_plan.h)                            */
 /* ------------------------------------------------------------------------ */
 
+/* the class doubles of a plan, refused where one is not finite */
+static int hq_atten_ktab(const hq_atten_plan& P, double freq, double dt, std::vector<double>* ktab)
+{
+    ktab->assign((size_t)P.nclasses * HQ_ATTEN_NCOEF, 0.0);
+    for (int32_t k = 0; k < P.nclasses; k++) {
+        hq_atten_class_coef(P.rows.data() + HQ_ATTEN_NROW * (size_t)k, freq, dt, ktab->data() + HQ_ATTEN_NCOEF * (size_t)k);
+        for (int j = 0; j < HQ_ATTEN_NCOEF; j++)
+            if (!std::isfinite((*ktab)[HQ_ATTEN_NCOEF * (size_t)k + j])) return hq_fail(HQ_ERR_ARG, "attenuation: a class coefficient is not finite%s", "");
+    }
+    return HQ_OK;
+}
+
+/* A plan's slot state on the device and its corner table on the host, in *A beside the context's own (no ledger: the arrays
+ * move, hq_ctx.bytes takes their sum at the end).  eslot: the table the device gets -- the plan's own, or a split context's
+ * in the correction's element order */
+static int hq_atten_slots_build(hq_atten_plan& P, const std::vector<int32_t>& eslot, const std::vector<double>& ktab, hipStream_t st,
+                                hq_atten_dev* A)
+{
+    HQ_TRY(A->d_eslot.put(nullptr, eslot, st)); HQ_TRY(A->d_slot_node.put(nullptr, P.slot_node, st));
+    HQ_TRY(A->d_slot_class.put(nullptr, P.slot_class, st)); HQ_TRY(A->d_ktab.put(nullptr, ktab, st));
+    HQ_TRY(A->d_mv.alloc(nullptr, (size_t)HQ_ATTEN_NSTATE * P.nslots)); HQ_TRY(A->d_mv.fill(0, st));
+    HQ_TRY(A->d_w.alloc(nullptr, (size_t)HQ_ATTEN_NW * P.nslots)); HQ_TRY(A->d_w.fill(0, st));
+    A->bytes = (int64_t)(A->d_eslot.bytes() + A->d_slot_node.bytes() + A->d_slot_class.bytes() + A->d_ktab.bytes() + A->d_mv.bytes() +
+                         A->d_w.bytes());
+    if (A->bytes != hq_atten_bytes(P.nslots, P.Epad, P.nclasses)) return hq_fail(HQ_ERR_STATE, "attenuation: the device bytes are not the header's formula%s", "");
+    A->nclasses = P.nclasses; A->nslots = P.nslots; A->Epad = (int32_t)P.Epad;
+    A->h_eslot = std::move(P.eslot); A->h_slot_node = std::move(P.slot_node);
+    A->on = true;
+    return HQ_OK;
+}
+
 extern "C" int hq_attenuation_set(hq_ctx* c, const hq_attenuation_desc* a)
 {
     if (!c || !a || !a->coef) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
@@ -2808,41 +2833,14 @@ extern "C" int hq_attenuation_set(hq_ctx* c, const hq_attenuation_desc* a)
     HQ_TRY(hq_copy_wait(soa.data(), c->d_lnid, sizeof(int32_t) * soa.size(), hipMemcpyDeviceToHost, c->stream));
     hq_atten_plan P;
     HQ_TRY(hq_atten_plan_build(c->E, c->N, soa.data(), c->Epad, a->coef, &P));
-    std::vector<double> ktab((size_t)P.nclasses * HQ_ATTEN_NCOEF);
-    for (int32_t k = 0; k < P.nclasses; k++) {
-        hq_atten_class_coef(P.rows.data() + HQ_ATTEN_NROW * (size_t)k, a->freq, c->dt, ktab.data() + HQ_ATTEN_NCOEF * (size_t)k);
-        for (int j = 0; j < HQ_ATTEN_NCOEF; j++)
-            if (!std::isfinite(ktab[HQ_ATTEN_NCOEF * (size_t)k + j])) return hq_fail(HQ_ERR_ARG, "attenuation: a class coefficient is not finite%s", "");
-    }
+    std::vector<double> ktab;
+    HQ_TRY(hq_atten_ktab(P, a->freq, c->dt, &ktab));
     /* everything is built beside the context's own and moved in at the end: a refusal leaves the context as it was */
     hq_atten_dev A;
-    int rc;                                          /* (no ledger: the arrays move; hq_ctx.bytes takes their sum below) */
-    if ((rc = A.d_eslot.put(nullptr, P.eslot, c->stream)) != HQ_OK || (rc = A.d_slot_node.put(nullptr, P.slot_node, c->stream)) != HQ_OK ||
-        (rc = A.d_slot_class.put(nullptr, P.slot_class, c->stream)) != HQ_OK || (rc = A.d_ktab.put(nullptr, ktab, c->stream)) != HQ_OK ||
-        (rc = A.d_mv.alloc(nullptr, (size_t)HQ_ATTEN_NSTATE * P.nslots)) != HQ_OK || (rc = A.d_mv.fill(0, c->stream)) != HQ_OK ||
-        (rc = A.d_w.alloc(nullptr, (size_t)HQ_ATTEN_NW * P.nslots)) != HQ_OK || (rc = A.d_w.fill(0, c->stream)) != HQ_OK)
-        return rc;                                   /* (A's arrays go with it) */
-    const int64_t added = (int64_t)(A.d_eslot.bytes() + A.d_slot_node.bytes() + A.d_slot_class.bytes() + A.d_ktab.bytes() +
-                                    A.d_mv.bytes() + A.d_w.bytes());
-    if (added != hq_atten_bytes(P.nslots, P.Epad, P.nclasses)) return hq_fail(HQ_ERR_STATE, "attenuation: the device bytes are not the header's formula%s", "");
-    A.nclasses = P.nclasses; A.nslots = P.nslots; A.bytes = added;
-    A.h_eslot = std::move(P.eslot); A.h_slot_node = std::move(P.slot_node);
-    A.on = true;
+    HQ_TRY(hq_atten_slots_build(P, P.eslot, ktab, c->stream, &A));       /* (on a refusal A's arrays go with it) */
     hq_attenuation_clear(c);
+    c->bytes += A.bytes;
     c->att = std::move(A);
-    c->bytes += added;
-    return HQ_OK;
-}
-
-/* the class doubles of a plan, refused where one is not finite */
-static int hq_atten_ktab(const hq_atten_plan& P, double freq, double dt, std::vector<double>* ktab)
-{
-    ktab->assign((size_t)P.nclasses * HQ_ATTEN_NCOEF, 0.0);
-    for (int32_t k = 0; k < P.nclasses; k++) {
-        hq_atten_class_coef(P.rows.data() + HQ_ATTEN_NROW * (size_t)k, freq, dt, ktab->data() + HQ_ATTEN_NCOEF * (size_t)k);
-        for (int j = 0; j < HQ_ATTEN_NCOEF; j++)
-            if (!std::isfinite((*ktab)[HQ_ATTEN_NCOEF * (size_t)k + j])) return hq_fail(HQ_ERR_ARG, "attenuation: a class coefficient is not finite%s", "");
-    }
     return HQ_OK;
 }
 
@@ -2872,6 +2870,17 @@ static int hq_correction_stream(hq_ctx* c, const char* who)
     return HQ_OK;
 }
 
+/* the hanging-node table in device numbering: the context's own arrays, read back */
+static int hq_hanging_to_host(hq_ctx* c, std::vector<int32_t>* id, std::vector<int32_t>* ptr, std::vector<int32_t>* anchor)
+{
+    id->assign((size_t)c->ldnnum, 0); ptr->assign((size_t)c->ldnnum + 1, 0); anchor->clear();
+    if (!c->ldnnum) return HQ_OK;
+    HQ_TRY(hq_copy_wait(id->data(), c->d_dn_id, sizeof(int32_t) * id->size(), hipMemcpyDeviceToHost, c->stream));
+    HQ_TRY(hq_copy_wait(ptr->data(), c->d_dn_ptr, sizeof(int32_t) * ptr->size(), hipMemcpyDeviceToHost, c->stream));
+    anchor->resize((size_t)ptr->back());
+    return hq_copy_wait(anchor->data(), c->d_dn_anchor, sizeof(int32_t) * anchor->size(), hipMemcpyDeviceToHost, c->stream);
+}
+
 extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
 {
     if (!c || !a || !a->coef) return hq_fail(HQ_ERR_ARG, "null argument%s", "");
@@ -2893,14 +2902,8 @@ extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
     HQ_TRY(hq_atten_plan_build(E, N, c->h_lnid.data(), 0, a->coef, &P));
     std::vector<double> ktab;
     HQ_TRY(hq_atten_ktab(P, a->freq, c->dt, &ktab));
-    /* the hanging-node table in device numbering: the context's own arrays */
-    std::vector<int32_t> dn_id((size_t)c->ldnnum), dn_ptr((size_t)c->ldnnum + 1, 0), dn_anchor;
-    if (c->ldnnum) {
-        HQ_TRY(hq_copy_wait(dn_id.data(), c->d_dn_id, sizeof(int32_t) * dn_id.size(), hipMemcpyDeviceToHost, c->stream));
-        HQ_TRY(hq_copy_wait(dn_ptr.data(), c->d_dn_ptr, sizeof(int32_t) * dn_ptr.size(), hipMemcpyDeviceToHost, c->stream));
-        dn_anchor.resize((size_t)dn_ptr[(size_t)c->ldnnum]);
-        HQ_TRY(hq_copy_wait(dn_anchor.data(), c->d_dn_anchor, sizeof(int32_t) * dn_anchor.size(), hipMemcpyDeviceToHost, c->stream));
-    }
+    std::vector<int32_t> dn_id, dn_ptr, dn_anchor;
+    HQ_TRY(hq_hanging_to_host(c, &dn_id, &dn_ptr, &dn_anchor));
     hq_split_plan S;
     HQ_TRY(hq_split_plan_build(E, N, P.Epad, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), &S));
     if (hq_atten_plan_faults(E, c->h_lnid.data(), P) != 0 ||
@@ -2910,7 +2913,6 @@ extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
     HQ_TRY(hq_correction_stream(c, "split attenuation"));
     /* everything is built beside the context's own and moved in at the end: a refusal leaves the context as it was */
     hq_atten_dev A;
-    int rc;
     std::vector<double> cc1((size_t)E), cc2((size_t)E);                 /* the device's element order (hq_split_plan.epos) */
     std::vector<int32_t> eslot_dev(P.eslot.size(), 0);
 #pragma omp parallel for schedule(static)
@@ -2919,44 +2921,21 @@ extern "C" int hq_attenuation_set_split(hq_ctx* c, const hq_attenuation_desc* a)
         cc1[at] = c->h_c1[(size_t)e]; cc2[at] = c->h_c2[(size_t)e];
         for (int i = 0; i < 8; i++) eslot_dev[(size_t)(i * P.Epad) + at] = P.eslot[(size_t)(i * P.Epad + e)];
     }
-    if ((rc = A.d_eslot.put(nullptr, eslot_dev, c->stream)) != HQ_OK || (rc = A.d_slot_node.put(nullptr, P.slot_node, c->stream)) != HQ_OK ||
-        (rc = A.d_slot_class.put(nullptr, P.slot_class, c->stream)) != HQ_OK || (rc = A.d_ktab.put(nullptr, ktab, c->stream)) != HQ_OK ||
-        (rc = A.d_mv.alloc(nullptr, (size_t)HQ_ATTEN_NSTATE * P.nslots)) != HQ_OK || (rc = A.d_mv.fill(0, c->stream)) != HQ_OK ||
-        (rc = A.d_w.alloc(nullptr, (size_t)HQ_ATTEN_NW * P.nslots)) != HQ_OK || (rc = A.d_w.fill(0, c->stream)) != HQ_OK ||
-        (rc = A.d_ef.alloc(nullptr, (size_t)(24 * P.Epad))) != HQ_OK || (rc = A.d_ef.fill(0, c->stream)) != HQ_OK ||
-        (rc = A.d_dF.alloc(nullptr, 3 * (size_t)N)) != HQ_OK || (rc = A.d_dF.fill(0, c->stream)) != HQ_OK ||
-        (rc = A.d_mass.put(nullptr, c->h_mass, c->stream)) != HQ_OK ||
-        (rc = A.d_c1.put(nullptr, cc1, c->stream)) != HQ_OK || (rc = A.d_c2.put(nullptr, cc2, c->stream)) != HQ_OK ||
-        (rc = A.d_nptr.put(nullptr, S.nptr, c->stream)) != HQ_OK || (rc = A.d_nent.put(nullptr, S.nent, c->stream)) != HQ_OK)
-        return rc;
-    int64_t added = (int64_t)(A.d_eslot.bytes() + A.d_slot_node.bytes() + A.d_slot_class.bytes() + A.d_ktab.bytes() + A.d_mv.bytes() +
-                              A.d_w.bytes() + A.d_ef.bytes() + A.d_dF.bytes() + A.d_mass.bytes() + A.d_c1.bytes() + A.d_c2.bytes() +
-                              A.d_nptr.bytes() + A.d_nent.bytes());
-    if (!S.sd.empty()) {
-        std::vector<int32_t> dst, ptr, src, deps;        /* hq_build_distribution's grouping by anchor, into A's own tables */
-        hq_split_group_by_anchor(S.sd, &dst, &ptr, &src, &deps);
-        if ((rc = A.d_sd_dst.put(nullptr, dst, c->stream)) != HQ_OK || (rc = A.d_sd_ptr.put(nullptr, ptr, c->stream)) != HQ_OK ||
-            (rc = A.d_sd_src.put(nullptr, src, c->stream)) != HQ_OK || (rc = A.d_sd_deps.put(nullptr, deps, c->stream)) != HQ_OK)
-            return rc;
-        A.nSD = (int32_t)dst.size();
-        added += (int64_t)(A.d_sd_dst.bytes() + A.d_sd_ptr.bytes() + A.d_sd_src.bytes() + A.d_sd_deps.bytes());
-    }
-    A.nanchors = S.nanchors; A.npairs = S.npairs;
-    if (added != hq_atten_bytes(P.nslots, P.Epad, P.nclasses) + hq_split_bytes(E, P.Epad, N, S.nanchors, S.npairs))
+    HQ_TRY(hq_atten_slots_build(P, eslot_dev, ktab, c->stream, &A));
+    HQ_TRY(A.d_c1.put(nullptr, cc1, c->stream)); HQ_TRY(A.d_c2.put(nullptr, cc2, c->stream));
+    HQ_TRY(hq_correction_build(S, E, A.Epad, c->h_mass, nullptr, c->stream, &A.corr));
+    if ((int64_t)(A.d_c1.bytes() + A.d_c2.bytes()) + A.corr.bytes != hq_split_bytes(E, A.Epad, N, S.nanchors, S.npairs))
         return hq_fail(HQ_ERR_STATE, "attenuation: the device bytes are not the header's formula%s", "");
-    A.nclasses = P.nclasses; A.nslots = P.nslots; A.bytes = added;
-    A.h_eslot = std::move(P.eslot);
-    A.h_slot_node = std::move(P.slot_node);
+    A.bytes += hq_split_bytes(E, A.Epad, N, S.nanchors, S.npairs);
     if (!c->perm.empty()) {                          /* fetch / load name nodes as the caller numbers them */
         std::vector<int32_t> inv((size_t)N);
         for (int64_t n = 0; n < N; n++) inv[(size_t)c->perm[(size_t)n]] = (int32_t)n;
         for (int32_t& n : A.h_slot_node) n = inv[(size_t)n];
     }
-    A.on = true; A.split = true;
+    A.split = true;
     hq_attenuation_clear(c);
-    c->Epad = (int32_t)P.Epad;                       /* (a patch context has no element SoA of its own: the stride of eslot and ef) */
+    c->bytes += A.bytes;
     c->att = std::move(A);
-    c->bytes += added;
     return HQ_OK;
 }
 
@@ -2998,7 +2977,7 @@ extern "C" int hq_attenuation_fetch(hq_ctx* c, double* shear1, double* shear2, d
 #pragma omp parallel for schedule(static)
         for (int64_t e = 0; e < c->E; e++)
             for (int i = 0; i < 8; i++) {
-                const int64_t s = A.h_eslot[(size_t)(i * (int64_t)c->Epad + e)];
+                const int64_t s = A.h_eslot[(size_t)(i * (int64_t)A.Epad + e)];
                 for (int d = 0; d < 3; d++) out[v][3 * (8 * e + i) + d] = mv[(size_t)((3 * v + d) * ns + s)];
             }
     }
@@ -3018,7 +2997,7 @@ extern "C" int hq_attenuation_load(hq_ctx* c, const double* shear1, const double
     std::vector<char> have((size_t)ns, 0);
     for (int64_t e = 0; e < c->E; e++)
         for (int i = 0; i < 8; i++) {
-            const int64_t s = A.h_eslot[(size_t)(i * (int64_t)c->Epad + e)];
+            const int64_t s = A.h_eslot[(size_t)(i * (int64_t)A.Epad + e)];
             for (int v = 0; v < HQ_ATTEN_NVAR; v++)
                 for (int d = 0; d < 3; d++) {
                     const double x = in[v][3 * (8 * e + i) + d];
@@ -3054,12 +3033,25 @@ extern "C" int hq_attenuation_plan_check(const hq_desc* d, const float* coef, in
     return HQ_OK;
 }
 
-/* the description as hq_create would number it, and the split tables of it */
-static int hq_split_plan_of(const hq_desc* d, hq_prep* prep, int64_t* Epad, hq_split_plan* S)
+/* the description as hq_create would number it: behind the bricks' numbering where it would build bricks (host-only: the
+ * library defaults, the environment where HQ_ALLOW_ENV=1) */
+static int hq_prepare_as_created(const hq_desc* d, hq_prep* prep)
 {
     hq_options opts;
     hq_options_resolve(&opts, nullptr);
-    HQ_TRY(hq_prepare(d, opts, d->eTable && d->nTable && d->node_xyz ? HQ_PREP_BRICKS : 0, prep));
+    return hq_prepare(d, opts, d->eTable && d->nTable && d->node_xyz ? HQ_PREP_BRICKS : 0, prep);
+}
+
+/* a plan's table into the caller's array, where there is one */
+static void hq_export(int32_t* out, const std::vector<int32_t>& v)
+{
+    if (out && !v.empty()) memcpy(out, v.data(), sizeof(int32_t) * v.size());
+}
+
+/* ... and the split tables of it */
+static int hq_split_plan_of(const hq_desc* d, hq_prep* prep, int64_t* Epad, hq_split_plan* S)
+{
+    HQ_TRY(hq_prepare_as_created(d, prep));
     const hq_desc& q = prep->desc;
     *Epad = ((int64_t)q.lenum + 63) & ~(int64_t)63;
     return hq_split_plan_build(q.lenum, q.nharbored, *Epad, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, S);
@@ -3093,10 +3085,7 @@ extern "C" int hq_attenuation_split_plan_tables(const hq_desc* d, int32_t* epos,
     int64_t Epad = 0;
     HQ_TRY(hq_split_plan_of(d, &prep, &Epad, &S));
     counts[0] = (int64_t)S.nptr.size(); counts[1] = (int64_t)S.nent.size(); counts[2] = (int64_t)(S.sd.size() / 3);
-    if (epos) memcpy(epos, S.epos.data(), sizeof(int32_t) * S.epos.size());
-    if (nptr) memcpy(nptr, S.nptr.data(), sizeof(int32_t) * S.nptr.size());
-    if (nent) memcpy(nent, S.nent.data(), sizeof(int32_t) * S.nent.size());
-    if (sd && !S.sd.empty()) memcpy(sd, S.sd.data(), sizeof(int32_t) * S.sd.size());
+    hq_export(epos, S.epos); hq_export(nptr, S.nptr); hq_export(nent, S.nent); hq_export(sd, S.sd);
     return HQ_OK;
 }
 
@@ -3165,15 +3154,9 @@ extern "C" int hq_nonlinear_set(hq_ctx* c, const hq_nonlinear_desc* a)
     hq_nl_dev L;                                      /* built beside the context's own: a refusal leaves the context as it was */
     L.model = a->model;
     const int64_t nel = a->nelems;
-    int64_t added = 0;
     if (nel > 0) {
-        std::vector<int32_t> dn_id((size_t)c->ldnnum), dn_ptr((size_t)c->ldnnum + 1, 0), dn_anchor;
-        if (c->ldnnum) {
-            HQ_TRY(hq_copy_wait(dn_id.data(), c->d_dn_id, sizeof(int32_t) * dn_id.size(), hipMemcpyDeviceToHost, c->stream));
-            HQ_TRY(hq_copy_wait(dn_ptr.data(), c->d_dn_ptr, sizeof(int32_t) * dn_ptr.size(), hipMemcpyDeviceToHost, c->stream));
-            dn_anchor.resize((size_t)dn_ptr[(size_t)c->ldnnum]);
-            HQ_TRY(hq_copy_wait(dn_anchor.data(), c->d_dn_anchor, sizeof(int32_t) * dn_anchor.size(), hipMemcpyDeviceToHost, c->stream));
-        }
+        std::vector<int32_t> dn_id, dn_ptr, dn_anchor;
+        HQ_TRY(hq_hanging_to_host(c, &dn_id, &dn_ptr, &dn_anchor));
         hq_nl_plan P;
         HQ_TRY(hq_nl_plan_build(nel, a->elems, c->N, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), &P));
         if (hq_nl_plan_faults(nel, a->elems, c->N, c->h_lnid.data(), c->ldnnum, dn_id.data(), dn_ptr.data(), dn_anchor.data(), P, P.S.epos.data(),
@@ -3189,35 +3172,19 @@ extern "C" int hq_nonlinear_set(hq_ctx* c, const hq_nonlinear_desc* a)
             for (int j = 0; j < HQ_NL_NCONS; j++) cons_dev[(size_t)(j * Ep) + at] = a->cons[HQ_NL_NCONS * k + j];
         }
         for (int64_t t = 0; t < nt; t++) mass[(size_t)t] = c->h_mass[(size_t)P.tnode[(size_t)t]];
-        int rc;
-        if ((rc = L.d_st.alloc(nullptr, (size_t)(HQ_NL_NSTATE * 8 * Ep))) != HQ_OK || (rc = L.d_st.fill(0, c->stream)) != HQ_OK ||
-            (rc = L.d_ef.alloc(nullptr, (size_t)(24 * Ep))) != HQ_OK || (rc = L.d_ef.fill(0, c->stream)) != HQ_OK ||
-            (rc = L.d_cons.put(nullptr, cons_dev, c->stream)) != HQ_OK || (rc = L.d_lnid.put(nullptr, lnid_dev, c->stream)) != HQ_OK ||
-            (rc = L.d_nptr.put(nullptr, P.S.nptr, c->stream)) != HQ_OK || (rc = L.d_nent.put(nullptr, P.S.nent, c->stream)) != HQ_OK ||
-            (rc = L.d_dF.alloc(nullptr, 3 * (size_t)nt)) != HQ_OK || (rc = L.d_dF.fill(0, c->stream)) != HQ_OK ||
-            (rc = L.d_mass.put(nullptr, mass, c->stream)) != HQ_OK || (rc = L.d_tnode.put(nullptr, P.tnode, c->stream)) != HQ_OK)
-            return rc;
-        added = (int64_t)(L.d_st.bytes() + L.d_ef.bytes() + L.d_cons.bytes() + L.d_lnid.bytes() + L.d_nptr.bytes() + L.d_nent.bytes() +
-                          L.d_dF.bytes() + L.d_mass.bytes() + L.d_tnode.bytes());
-        if (!P.S.sd.empty()) {
-            std::vector<int32_t> dst, ptr, src, deps;
-            hq_split_group_by_anchor(P.S.sd, &dst, &ptr, &src, &deps);
-            if ((rc = L.d_sd_dst.put(nullptr, dst, c->stream)) != HQ_OK || (rc = L.d_sd_ptr.put(nullptr, ptr, c->stream)) != HQ_OK ||
-                (rc = L.d_sd_src.put(nullptr, src, c->stream)) != HQ_OK || (rc = L.d_sd_deps.put(nullptr, deps, c->stream)) != HQ_OK)
-                return rc;
-            L.nSD = (int32_t)dst.size();
-            added += (int64_t)(L.d_sd_dst.bytes() + L.d_sd_ptr.bytes() + L.d_sd_src.bytes() + L.d_sd_deps.bytes());
-        }
-        if (added != hq_nl_bytes(nel, Ep, nt, P.S.nanchors, P.S.npairs))
+        HQ_TRY(L.d_st.alloc(nullptr, (size_t)(HQ_NL_NSTATE * 8 * Ep))); HQ_TRY(L.d_st.fill(0, c->stream));
+        HQ_TRY(L.d_cons.put(nullptr, cons_dev, c->stream)); HQ_TRY(L.d_lnid.put(nullptr, lnid_dev, c->stream));
+        HQ_TRY(hq_correction_build(P.S, nel, Ep, mass, &P.tnode, c->stream, &L.corr));
+        L.bytes = (int64_t)(L.d_st.bytes() + L.d_cons.bytes() + L.d_lnid.bytes()) + L.corr.bytes;
+        if (L.bytes != hq_nl_bytes(nel, Ep, nt, P.S.nanchors, P.S.npairs))
             return hq_fail(HQ_ERR_STATE, "nonlinear: the device bytes are not the header's formula%s", "");
         L.nel = (int32_t)nel; L.Enlpad = (int32_t)Ep; L.nt = (int32_t)nt;
         L.h_epos = std::move(P.S.epos);
     }
-    L.bytes = added;
     L.on = true;
     hq_nonlinear_clear(c);
+    c->bytes += L.bytes;
     c->nl = std::move(L);
-    c->bytes += added;
     return HQ_OK;
 }
 
@@ -3288,9 +3255,7 @@ static int hq_nl_plan_of(const hq_desc* d, const hq_nonlinear_desc* a, hq_prep* 
 {
     if (d->nranks > 1) return hq_fail(HQ_ERR_STATE, "nonlinear: partitions and transports are out of scope (one context, nranks = 1)%s", "");
     HQ_TRY(hq_nl_validate(a, d->lenum));
-    hq_options opts;
-    hq_options_resolve(&opts, nullptr);
-    HQ_TRY(hq_prepare(d, opts, d->eTable && d->nTable && d->node_xyz ? HQ_PREP_BRICKS : 0, prep));
+    HQ_TRY(hq_prepare_as_created(d, prep));
     const hq_desc& q = prep->desc;
     if (a->nelems == 0) { *P = hq_nl_plan(); return HQ_OK; }
     return hq_nl_plan_build(a->nelems, a->elems, q.nharbored, q.lnid, q.ldnnum, q.dn_ldnid, q.dn_ptr, q.dn_lanid, P);
@@ -3318,11 +3283,7 @@ extern "C" int hq_nonlinear_plan_tables(const hq_desc* d, const hq_nonlinear_des
     hq_nl_plan P;
     HQ_TRY(hq_nl_plan_of(d, a, &prep, &P));
     counts[0] = P.nt; counts[1] = (int64_t)P.S.nptr.size(); counts[2] = (int64_t)P.S.nent.size(); counts[3] = (int64_t)(P.S.sd.size() / 3);
-    if (tnode && P.nt) memcpy(tnode, P.tnode.data(), sizeof(int32_t) * P.tnode.size());
-    if (epos && P.nel) memcpy(epos, P.S.epos.data(), sizeof(int32_t) * P.S.epos.size());
-    if (nptr && P.nel) memcpy(nptr, P.S.nptr.data(), sizeof(int32_t) * P.S.nptr.size());
-    if (nent && P.nel) memcpy(nent, P.S.nent.data(), sizeof(int32_t) * P.S.nent.size());
-    if (sd && !P.S.sd.empty()) memcpy(sd, P.S.sd.data(), sizeof(int32_t) * P.S.sd.size());
+    hq_export(tnode, P.tnode); hq_export(epos, P.S.epos); hq_export(nptr, P.S.nptr); hq_export(nent, P.S.nent); hq_export(sd, P.S.sd);
     return HQ_OK;
 }
 

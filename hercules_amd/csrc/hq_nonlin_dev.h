@@ -1,25 +1,20 @@
-/* hq_nonlin_dev.h -- nonlinear soil beside the patch and brick step (hq_nonlinear_set): the plan and the kernels.
+/* hq_nonlin_dev.h -- nonlinear soil beside the patch and brick step (hq_nonlinear_set): the plan and the pass's own kernel.
  *
- * hq_nonlin.h has the physics and why it may enter as a correction.  The pass is hq_atten_split.h's, over the nonlinear
- * elements and the nodes they touch ONLY -- a run with 5 % of its elements nonlinear pays for 5 %:
+ * hq_nonlin.h has the physics and why it may enter as a correction.  The pass is hq_correction.h's, over the nonlinear
+ * elements and the nodes they touch ONLY -- a run with 5 % of its elements nonlinear pays for 5 %.  The pass's own:
  *   hq_k_nl_element        one thread per nonlinear element: gathers its 24 values of u(t), and for each of its eight points
  *                          reads the old plastic strain, adds the point's share to the 24 corner forces, advances the point
  *                          and writes it back; the corner forces go to ef [3][8][Enlpad]              (no atomics)
- *   hq_k_atten_node_sum    (hq_atten_split.h's) one thread per TOUCHED node: dF[t] = the sum of its (element, corner) entries
- *                          in the caller's element order
- *   hq_k_distribute        (the engine's) the touched hanging nodes of dF to their anchors, on touched-node indices
- *   hq_k_atten_apply_at    un[node[t]] += dF[t] / mass[t]
- *   hq_k_adjust_assign     (the engine's) on un, all hanging nodes
- * The first two read u(t) only and run on a stream of their own beside the step; the last three follow every step kernel on
- * the compute stream.  The touched nodes are the nodes of the nonlinear elements and the anchors of the hanging ones among
- * them, in ascending device numbering; the tables are hq_split_plan's (hq_split_plan_build, hq_split_plan_faults) over that
- * sub-mesh: the elements renumbered 0 .. nel - 1 in the caller's (ascending) order, the nodes by their place in the list.
+ * It reads u(t) only.  The correction's rows are the touched nodes, a list (hq_k_atten_apply_at): the nodes of the nonlinear
+ * elements and the anchors of the hanging ones among them, in ascending device numbering; the tables are hq_split_plan's
+ * (hq_split_plan_build, hq_split_plan_faults) over that sub-mesh: the elements renumbered 0 .. nel - 1 in the caller's
+ * (ascending) order, the nodes by their place in the list.
  *
  * Traffic model per nonlinear element (docs/LABNOTES.md has the measurement): 896 B of state read and written, 192 B of
  * corner forces written and read again, 48 B of constants, 32 B of node ids, the gathered fields (192 B requested, 24 B from
  * HBM in a uniform region), the node table 32 + 4 B, and per touched node 24 B of dF written and read again, 12 + 8 + 24 +
  * 24 B of the apply: 1536 B per element where every element has a node of its own.
- * Included by hq_engine.hip (one translation unit): uses its hq_fail and hq_real. */
+ * Included by hq_engine.hip (one translation unit) behind hq_correction.h: uses its hq_fail and hq_real. */
 #ifndef HQ_NONLIN_DEV_H
 #define HQ_NONLIN_DEV_H
 
@@ -33,12 +28,12 @@ struct hq_nl_plan {
     hq_split_plan S;
 };
 
-/* the device bytes hq_nonlinear_set adds: state, corner forces, constants and node ids per padded element; the node table;
- * dF, the mass and the node id per touched node; the distribution tables (none without touched hanging nodes) */
+/* the device bytes hq_nonlinear_set adds: state, constants and node ids per padded element, and the correction over the
+ * nonlinear elements and the listed touched nodes */
 static int64_t hq_nl_bytes(int64_t nel, int64_t Enlpad, int64_t nt, int64_t nanchors, int64_t npairs)
 {
     if (nel == 0) return 0;
-    return (448 + 192 + 48 + 32) * Enlpad + 4 * (nt + 1) + 32 * nel + (24 + 8 + 4) * nt + (npairs ? 8 * nanchors + 4 + 8 * npairs : 0);
+    return (448 + 48 + 32) * Enlpad + hq_correction_bytes(nel, Enlpad, nt, true, nanchors, npairs);
 }
 
 /* elems [nel] strictly ascending in 0 .. E - 1 (checked by the caller); lnid [E][8] and the hanging-node table in the
